@@ -12,8 +12,10 @@ binary values).  --preset selects the other single-GPU lines of SURVEY.md 8(d):
     c3-refdefaults   C3 with the reference's default hyper-parameters (l1 = 1, V_threshold = 10)
     c5-slice         one GPU's share of C5: V_dim 128, l1 = 1, as many ids as fit the HBM (~2e8)
     c2               rcv1-shaped: 100 rows x ~75 real-valued features over 47 236 ids, V_dim 8
-The timed region of K steps (sync + barrier on both sides) is repeated until at least --min-time
-seconds have been measured; the line reports the MEDIAN repetition and the spread.
+The timed region is K steps (sync + barrier on both sides); with --min-time S it is repeated until at
+least S seconds have been measured and the line reports the MEDIAN repetition and the spread.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) for output-for-output
+comparisons of two builds: the inputs are seeded, so the same arguments give the same inputs.
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
 """
 import argparse
@@ -72,7 +74,8 @@ def parse_args():
     ap.add_argument("--no-auc", action="store_true",
                     help="A/B: leave BinClassMetric::AUC out of the step (the reference computes it for every minibatch, "
                          "sgd_learner.cc:153-155; the default step does too)")
-    ap.add_argument("--min-time", type=float, default=3.0, help="repeat the K-step region until this many seconds are timed")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the K-step region until this many seconds are timed (0: one region, exactly --steps timed steps)")
     ap.add_argument("--max-reps", type=int, default=20000)
     ap.add_argument("--no-secondary", action="store_true",
                     help="N=1, preset c3: skip the `secondary` block (c3-refdefaults and c5-slice, each run as a child process "
@@ -134,6 +137,8 @@ def parse_args():
                          "when step t starts and travel at once; 1: round 4's loop)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the N>1 code path (key-range shards + RCCL all_to_all_v) even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the logits and the updated model rows of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
     pre = PRESETS[args.preset]
     args.rows = args.rows if args.rows is not None else pre.get("rows", 10000)
@@ -151,6 +156,43 @@ def parse_args():
     if args.key_ranges is None:
         args.key_ranges = "blend" if args.preset == "c5-slice" else "data"
     return args
+
+
+DUMP_BYTES = (64 << 20) - 4096   # --dump-outputs writes at most 64 MB, the .npy headers included
+
+
+def _seeded_rows(n, cap, seed):
+    """None (keep all n rows) or a fixed, sorted sample of cap of them"""
+    return None if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, bt, table, k):
+    """--dump-outputs: what a caller of the step receives from the last timed one, in float32 — `pred`, the minibatch's
+    logits, and the model rows of its keys after the update, in the Localizer's (ascending) key order: `w`, and with
+    V_dim > 0 `V` (zero where a key has none) and `has_V`.  Past DUMP_BYTES a fixed, seeded sample of rows is kept:
+    a quarter of the budget for the logits, the rest for the keys; `pred_rows` / `key_rows` (float64) say which."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    pred = bt.pred()
+    rows = _seeded_rows(len(pred), DUMP_BYTES // 4 // 12, 1)
+    if rows is not None:
+        pred, out["pred_rows"] = pred[rows], rows.astype(np.float64)
+    out["pred"] = pred
+    keys = bt.get_localized()["feaids"]
+    rows = _seeded_rows(len(keys), DUMP_BYTES * 3 // 4 // (4 * (k + 2) + 8), 2)
+    if rows is not None:
+        keys, out["key_rows"] = keys[rows], rows.astype(np.float64)
+    vals, lens = table.pull(keys)
+    if k:
+        start = np.cumsum(lens) - lens
+        has = lens > 1
+        V = np.zeros((len(keys), k), np.float32)
+        V[has] = vals[(start[has] + 1)[:, None] + np.arange(k)]
+        out.update(w=vals[start], V=V, has_V=has.astype(np.float32))
+    else:
+        out["w"] = vals
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 TIMING_EVERY = int(os.environ.get("DFH_TIMING_EVERY", "8"))  # forward/backward are timed on every n-th step of the timed region
@@ -371,6 +413,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or args.force_sharded or args.emulate_world > 1):
+        raise SystemExit("--dump-outputs: the single-GPU path only")
     if args.gpus > 1 and "RANK" not in os.environ:
         # started by hand without a launcher: re-launch under torch.distributed.run, one rank per GPU
         import socket
@@ -545,6 +589,8 @@ def main():
     order = np.argsort(reps)
     dt = float(reps[order[len(reps) // 2]])  # the median repetition
     t_enqueued = float(enq[order[len(reps) // 2]])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bts[(done - 1) % len(bts)], table, k)
     progs = [b.progress(reset=True) for b in bts]
     loss_sum = sum(p.loss for p in progs)
     rows_sum = sum(p.nrows for p in progs)

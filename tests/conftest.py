@@ -48,11 +48,39 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def ref():
+def ref_build():
+    """the reference build itself, for the tests that check IT (not the project) against the reference's own numbers"""
     from oracle import bindings
     if not bindings.have_ref():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+        pytest.skip("oracle/_ref not built (needs the reference's sources)")
     return bindings.Ref()
+
+
+_RECORDED = {}   # DIFACTO_REF_RECORD=1: node id -> the reference calls of that test, saved at the end of the session
+
+
+@pytest.fixture
+def ref(request):
+    """the reference build (oracle/_ref) where it is built; elsewhere the answers it gave this test when they were
+    recorded (oracle/replay.py, tests/golden/ref_replay.pkl.gz)"""
+    from oracle import bindings, replay
+    nodeid = os.path.relpath(str(request.node.fspath), ROOT).replace(os.sep, "/") + "::" + request.node.name
+    if bindings.have_ref():
+        live = bindings.Ref()
+        if not os.environ.get("DIFACTO_REF_RECORD"):
+            return live
+        _RECORDED[nodeid] = []
+        return replay.Recorder(live, _RECORDED[nodeid])
+    calls = replay.load().get(nodeid)
+    if calls is None:
+        pytest.fail("oracle/_ref is not built and the reference's answers to this test are not recorded")
+    return replay.Replay(calls, nodeid)
+
+
+def pytest_sessionfinish(session):
+    if _RECORDED:
+        from oracle import replay
+        replay.save(_RECORDED)
 
 
 def random_batch(rng, nrows, nfeat_space, max_nnz_row, binary=False, empty_rows=True):

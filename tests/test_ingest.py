@@ -580,14 +580,12 @@ def test_adfea_reader_on_the_reference_parsers_output(ing, tmp_path):
     assert np.array_equal(np.concatenate([p["label"] for p in parts]), lab)
 
 
-def test_reference_format_code_live_when_built(ing, tmp_path):
-    """in the build container (oracle/_ref with the data-format half): random row blocks through the reference's
+def test_reference_format_code_live_when_built(ing, ref, tmp_path):
+    """the reference's data-format half (oracle/_ref where it is built, its recorded answers elsewhere): random row blocks through the reference's
     Compress -> product reader, oracle/ingest.py's writer -> the reference's Decompress, random criteo text through
     both parsers, and the checker-side CityHash64 against the product's"""
-    from oracle import bindings as ob, ingest as oi
-    if not ob.have_ref():
-        pytest.skip("oracle/_ref not built here")
-    R = ob.Ref()
+    from oracle import ingest as oi
+    R = ref
     if not R.has_ingest:
         pytest.skip("oracle/_ref built without the data-format half (no lz4.h)")
     rng = np.random.default_rng(11)

@@ -96,7 +96,9 @@ PURE_MIN = {
     'fused/c2_rcv1_k8/l1=0': {'logits': 0.98},
     'fused/c2_rcv1_k8/l1=0.05': {'logits': 0.98},
     'fused/c3_full_k128/l1=0': {'logits': 0.974},
+    'fused/c3_full_k128/l1=0.05': {'logits': 0.974},
     'fused/c3_full_k64/l1=0': {'logits': 0.976},
+    'fused/c3_full_k64/l1=0.05': {'logits': 0.976},
     'fused/hot_k64/l1=0': {'logits': 0.979},
     'fused/hot_k64/l1=0.05': {'logits': 0.979},
     'fused/ragged_k0/l1=0': {'logits': 0.981},
@@ -245,8 +247,6 @@ def test_fused_first_step_vs_oracle(capi, ctx, oracle, rcv1, name, l1):
     """k_lookup + k_forward<L,5> (table rows) + k_backward_all<L,true,true,*> (in-place FTRL / AdaGrad /
     lazy InitV): the first step on an imported model"""
     from oracle import bindings as ob, tolerance as T
-    if name.startswith("c3_full") and l1 != 0.0:
-        pytest.skip("full-size case runs once")
     b, k, scale = _case(name, rcv1)
     rng = np.random.default_rng(23)
     kw = dict(l1=l1, l2=0.01, lr=0.05, lr_beta=1.0, V_lr=0.02, V_lr_beta=1.0, V_l2=0.02, V_threshold=3, V_init_scale=0.1, seed=5)

@@ -28,9 +28,7 @@ def _localized(chk, rcv1, max_index=U64MAX):
 def chk(request, oracle):
     if request.param == "oracle":
         return oracle
-    if not ob.have_ref():
-        pytest.skip("oracle/_ref not built")
-    return ob.Ref()
+    return request.getfixturevalue("ref_build")
 
 
 # ---- tests/cpp/localizer_test.cc:12-29 (Base) and :31-49 (BaseHash)
@@ -129,8 +127,9 @@ def test_sgd_learner_basic_oracle(oracle, rcv1):
         assert prog.nrows == 100
 
 
-def test_sgd_learner_basic_ref(ref, oracle, rcv1):
+def test_sgd_learner_basic_ref(ref_build, oracle, rcv1):
     """same trajectory driven through the reference's StoreLocal/SGDUpdater/FMLoss"""
+    ref = ref_build
     loc = ref.localize(rcv1["offset"], rcv1["index"])
     st = ref.store_create(V_dim=0, l1=1, l2=1, lr=1)
     for epoch in range(20):
@@ -249,7 +248,7 @@ def test_penalty_and_getpos(oracle):
 @pytest.mark.parametrize("case", ["basic", "withv"])
 def test_golden_lbfgs_trajectories(request, rcv1, impl, case):
     from oracle import lbfgs_driver as LB
-    P = request.getfixturevalue(impl)
+    P = request.getfixturevalue("ref_build" if impl == "ref" else impl)
     oracle = request.getfixturevalue("oracle")
     loc = oracle.localize(rcv1["offset"], rcv1["index"])
     V_dim = 0 if case == "basic" else 5

@@ -3,7 +3,7 @@ the exchange runs inside libdifacto_hip.so — RCCL ncclSend / ncclRecv in produ
 calls one entry point per minibatch.
 
   * world 1 over the real RCCL transport: the step must equal the fused single-GPU step;
-  * 2 and 4 ranks sharing the one GPU of the test box through the host-callback transport (gloo
+  * 2, 4 and 5 ranks sharing the one GPU of the test box through the host-callback transport (gloo
     carries the bytes; RCCL cannot put two ranks on one device), with UNEVEN numbers of minibatches
     per rank (a rank whose data is exhausted keeps serving its shard), uniform and balanced key
     ranges: per-rank logits, loss, penalty and the union of the shards against ONE oracle store that
@@ -277,10 +277,11 @@ def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
 
 
 @pytest.mark.gpu
+# the widest jobs run 5 ranks: with the test process itself, no more than six processes hold the GPU at once
 @pytest.mark.parametrize("WORLD,balanced,prefetch,exchange", [(2, False, False, "sync"), (2, True, True, "sync"), (4, True, False, "sync"),
                                                               (4, False, True, "sync"), (2, True, True, "overlap"),
-                                                              (4, False, True, "overlap"), (8, True, True, "overlap"),
-                                                              (8, False, False, "sync")])
+                                                              (4, False, True, "overlap"), (5, True, True, "overlap"),
+                                                              (5, False, False, "sync")])
 def test_shard_step_ranks_share_one_gpu(tmp_path, oracle, WORLD, balanced, prefetch, exchange):
     port = 29700 + (os.getpid() % 80) + WORLD + (10 if prefetch else 0) + (20 if exchange == "overlap" else 0)
     mp.spawn(_worker, args=(WORLD, port, str(tmp_path), balanced, prefetch, exchange), nprocs=WORLD, join=True)
