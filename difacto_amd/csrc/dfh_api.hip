@@ -2769,7 +2769,7 @@ void launch_loc_stage(dfh_batch* b, int stage, hipStream_t s, dfh_table* probe =
       else hipLaunchKernelGGL(k_loc_scatter<LOC_MAX_BUCKETS>, dim3(v.ntiles), dim3(LOC_TILE_THREADS), 0, s, v);
       break;
     case RID_SORT:
-      hipLaunchKernelGGL(k_loc_sort, dim3(b->loc_gsort), dim3(LOC_SORT_THREADS), 0, s, v);
+      hipLaunchKernelGGL(k_loc_sort, dim3(b->loc_gsort), dim3(LOC_SORT_THREADS), loc_sort_smem(), s, v);   // (dynamic LDS: k_loc_sort)
       break;
     default:
       if (probe) hipLaunchKernelGGL(k_loc_emit<true>, dim3(b->loc_gsort), dim3(LOC_EMIT_THREADS), 0, s, v, b->loc_o, probe->v, b->d_urow);

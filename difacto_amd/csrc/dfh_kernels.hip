@@ -504,9 +504,12 @@ __global__ void __launch_bounds__(256) k_auc_finalize(AucFin f) { auc_finalize_b
 // ---------------------------------------------------------------------------
 // The parts of the keys with more than HOT_SPLIT_MIN occurrences in the minibatch (SegLists::split_ent), listed by the pass that
 // visits every unique key before the update and has its segment at hand (col_ptr): one atomic on the list's counter per such key —
-// a handful per minibatch at most.  (Round 6's first form listed them in k_loc_emit: the inlined loop took that kernel from 28 to
-// 36 registers, and an emit wave of 36 no longer fits in the 32 registers five 96-register waves of k_update_fused leave free on
-// a SIMD: the first epoch's steps, where emit runs beside the update, lost 15 % — profiles/r06r_*.)
+// a handful per minibatch at most.  (Round 6's first form listed them in k_loc_emit: the inlined loop took that kernel's allocation
+// from 56 to 72 registers, and the first epoch's steps, where emit runs beside the update, lost 15 % — profiles/r06r_*.  Those
+// profiles quote rocprofv3's `vgpr` column, 28 -> 36, which is HALF the allocation for every kernel of this library; the allocation
+// is the kernel descriptor's next free VGPR in granules of 8.  Emit did not fit in the 32 registers five 96-register waves of
+// k_update_fused leave free on a SIMD at either size; since the register fit of the preparation kernels it is allocated 32 —
+// tests/test_prep_registers.py.)
 struct SplitOut {
   SegEnt* ent;        // NULL: no list (the update's hot role takes every key whole)
   uint32_t* n;        // entries so far (zeroed by the Localizer's count pass)

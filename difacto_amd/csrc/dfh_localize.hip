@@ -145,54 +145,52 @@ __device__ __forceinline__ bool comp_less(uint64_t ka, uint32_t pa, uint64_t kb,
   return ka < kb || (ka == kb && pa < pb);
 }
 
-// block-wide exclusive scan helper: returns the exclusive prefix of `val` over
-// the block's threads; *total (optional) receives the block sum
-template <int NWAVES>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t val, uint32_t* wsum /* [NWAVES] shared */, uint32_t* total) {
-  uint32_t s = val;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(s, o, 64);
-    if ((int)(threadIdx.x & 63) >= o) s += y;
+// In-wave inclusive scan (sum or running maximum) over the 64 lanes with DPP row shifts and row broadcasts (GFX9 DPP): no LDS
+// round trip and no lane-address registers.  The __shfl_up form (ds_bpermute) kept six loop-invariant address registers live
+// through k_loc_emit's element loop.  Lanes a DPP step does not reach receive 0, the identity of both operations on uint32_t.
+template <bool MAX>
+__device__ __forceinline__ uint32_t wave_inclusive(uint32_t x) {
+#define DFH_DPP_STEP(ctrl, row_mask)                                                                      \
+  {                                                                                                       \
+    const uint32_t y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, row_mask, 0xf, false);    \
+    x = MAX ? max(x, y) : x + y;                                                                          \
   }
-  __syncthreads();  // wsum may still be read from a previous call
-  if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = s;
-  __syncthreads();
-  uint32_t woff = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NWAVES; ++w) {
-    const uint32_t x = wsum[w];
-    if (w < (int)(threadIdx.x >> 6)) woff += x;
-    tot += x;
-  }
-  if (total) *total = tot;
-  return woff + s - val;
+  DFH_DPP_STEP(0x111, 0xf)  // row_shr:1
+  DFH_DPP_STEP(0x112, 0xf)  // row_shr:2
+  DFH_DPP_STEP(0x114, 0xf)  // row_shr:4
+  DFH_DPP_STEP(0x118, 0xf)  // row_shr:8: every row of 16 lanes is scanned
+  DFH_DPP_STEP(0x142, 0xa)  // row_bcast:15: lane 15 of rows 0 / 2 into rows 1 / 3
+  DFH_DPP_STEP(0x143, 0xc)  // row_bcast:31: lane 31 into rows 2 and 3
+#undef DFH_DPP_STEP
+  return x;
 }
 
-// the same for a running maximum: returns max over the threads BEFORE this one (0 if none)
+// block-wide exclusive scan (sum or maximum) helper: returns the combination of `val` over the threads BEFORE this one (0 if
+// none); *total (optional) receives the whole block's.  The wave totals are combined lane-parallel (lane w < NWAVES holds wave
+// w's, a second in-wave scan): reading all NWAVES of them into every lane kept NWAVES registers live (16 in k_loc_scatter)
+template <bool MAX, int NWAVES>
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t val, uint32_t* wtot /* [NWAVES] shared */, uint32_t* total) {
+  static_assert(NWAVES <= 64, "one lane per wave");
+  const int lane = (int)(threadIdx.x & 63);
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t s = wave_inclusive<MAX>(val);
+  __syncthreads();  // wtot may still be read from a previous call
+  if (lane == 63) wtot[w] = s;
+  __syncthreads();
+  const uint32_t x = wave_inclusive<MAX>(lane < NWAVES ? wtot[lane] : 0u);
+  const uint32_t before = w ? (uint32_t)__builtin_amdgcn_readlane((int)x, w - 1) : 0u;
+  if (total) *total = (uint32_t)__builtin_amdgcn_readlane((int)x, NWAVES - 1);
+  // exclusive inside the wave: the inclusive value of the previous lane (wave_shr:1; lane 0 receives 0)
+  const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x138, 0xf, 0xf, false);
+  return MAX ? max(before, prev) : before + prev;
+}
+template <int NWAVES>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t val, uint32_t* wsum /* [NWAVES] shared */, uint32_t* total) {
+  return block_exclusive<false, NWAVES>(val, wsum, total);
+}
 template <int NWAVES>
 __device__ __forceinline__ uint32_t block_exclusive_max(uint32_t val, uint32_t* wmax /* [NWAVES] shared */, uint32_t* total) {
-  uint32_t s = val;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(s, o, 64);
-    if ((int)(threadIdx.x & 63) >= o) s = max(s, y);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 63) wmax[threadIdx.x >> 6] = s;
-  __syncthreads();
-  uint32_t before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < NWAVES; ++w) {
-    const uint32_t x = wmax[w];
-    if (w < (int)(threadIdx.x >> 6)) before = max(before, x);
-    tot = max(tot, x);
-  }
-  if (total) *total = tot;
-  // exclusive inside the wave: the inclusive value of the previous lane
-  uint32_t prev = __shfl_up(s, 1, 64);
-  if ((threadIdx.x & 63) == 0) prev = 0;
-  return max(before, prev);
+  return block_exclusive<true, NWAVES>(val, wmax, total);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -447,15 +445,6 @@ __device__ __forceinline__ void loc_scatter_block(const LocView& v, const uint32
   const int P = v.P;
   const uint32_t xcd = bid & (LOC_XCDS - 1);
   const uint32_t base = bid * LOC_TILE;
-  uint64_t raw[PER];
-  uint32_t pk[PER], rw[PER];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) {
-    const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1);  // clamped: the loads stay unconditional
-    raw[e] = v.raw[i];
-    pk[e] = v.packed[i];
-    rw[e] = v.rowid[i];
-  }
   // exclusive scan of the bucket totals: LOC_BPT consecutive buckets per thread
   const int b0 = threadIdx.x * LOC_BPT;
   uint32_t tt[LOC_BPT], ro[LOC_BPT];
@@ -488,6 +477,16 @@ __device__ __forceinline__ void loc_scatter_block(const LocView& v, const uint32
     ex += tt[q];
   }
   if (bid == 0 && threadIdx.x == 0) v.bstart[P] = total;
+  // the tile's pairs are loaded only now: held across the scan they kept the kernel above 32 registers
+  uint64_t raw[PER];
+  uint32_t pk[PER], rw[PER];
+#pragma unroll
+  for (int e = 0; e < PER; ++e) {
+    const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1);  // clamped: the loads stay unconditional
+    raw[e] = v.raw[i];
+    pk[e] = v.packed[i];
+    rw[e] = v.rowid[i];
+  }
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
@@ -529,7 +528,9 @@ __device__ __forceinline__ bool loc_sort_bucket(const LocView& v, uint32_t beg, 
       const uint32_t mp = valid ? gp[idx] : ~0u;
       const int klo = (int)(uint32_t)mk, khi = (int)(uint32_t)(mk >> 32);
       uint32_t rank = 0;
-#pragma unroll 8  // (fully unrolled, the compiler reads all 192 words first and spills them)
+      // (4 at a time: at 8 the 24 SGPRs of broadcasts spilled into a VGPR; fully unrolled, the compiler reads all 192 words first
+      // and spills them)
+#pragma unroll 4
       for (int j = 0; j < 64; ++j) {
         const uint64_t ok = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(khi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane(klo, j);
         const uint32_t op = (uint32_t)__builtin_amdgcn_readlane((int)mp, j);
@@ -541,57 +542,58 @@ __device__ __forceinline__ bool loc_sort_bucket(const LocView& v, uint32_t beg, 
       }
     }
     __syncthreads();
-    // merge rounds: element's slot = its offset in its run + (# smaller elements in the sibling run).  A thread carries its
-    // (up to) LOC_LDS_CAP / LOC_SORT_THREADS elements through the search together: one LDS latency per step, not one per
-    // element and step.  The count is built from descending powers of two (the sibling run has at most L elements).
+    // merge rounds: element's slot = its offset in its run + (# smaller elements in the sibling run).  A thread carries G of its
+    // (up to) LOC_LDS_CAP / LOC_SORT_THREADS elements through the search together: one LDS latency per step for G elements, not
+    // one per element and step.  The count is built from descending powers of two (the sibling run has at most L elements).
+    // G = 2 and the sibling run's bounds recomputed from the index at every step keep the kernel in 32 registers (all four
+    // elements carried at once took 60, which no longer fit beside the training step's kernels); a bucket of up to
+    // 2 * LOC_SORT_THREADS pairs (all but the rare oversize ones) still takes one pass per round.
     constexpr int E = LOC_LDS_CAP / LOC_SORT_THREADS;
-    static_assert(E * LOC_SORT_THREADS == LOC_LDS_CAP && LOC_SORT_THREADS % 64 == 0, "a thread carries E elements of a full bucket");
+    constexpr int G = 2;
+    static_assert(E * LOC_SORT_THREADS == LOC_LDS_CAP && E % G == 0 && LOC_SORT_THREADS % 64 == 0,
+                  "a thread carries E elements of a full bucket, G at a time");
     uint64_t* dk = ak;
     uint32_t* dp = ap;
     uint32_t sh = 6;
     for (uint32_t L = 64; L < n; L <<= 1, ++sh) {
-      uint64_t mk[E];
-      uint32_t mp[E], cnt[E], sb[E], len[E];
+      for (int g = 0; g < E && g * LOC_SORT_THREADS < (int)n; g += G) {  // block-uniform
+        // per element: the pair, and the search state as slots of the sibling run [at, end): `at` advances by the powers of two
+        // whose last slot is smaller than the pair (two registers; a count plus the run's start and length took three)
+        uint64_t mk[G];
+        uint32_t mp[G], at[G], end[G];
 #pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const uint32_t idx = threadIdx.x + e * LOC_SORT_THREADS;
-        const bool valid = idx < n;
-        len[e] = 0;
-        cnt[e] = 0;
-        if (e * LOC_SORT_THREADS >= n) continue;  // block-uniform: a bucket of n <= 256 e costs e elements' work
-        mk[e] = valid ? sk[idx] : 0ULL;
-        mp[e] = valid ? sp[idx] : 0u;
-        const uint32_t sib = ((idx >> sh) ^ 1u) << sh;
-        sb[e] = min(sib, n);
-        len[e] = valid ? min(sib + L, n) - sb[e] : 0u;
-        cnt[e] = 0;
-      }
-      for (uint32_t step = L; step; step >>= 1) {
-        uint64_t ok[E];
-        uint32_t op[E];
+        for (int e = 0; e < G; ++e) {
+          const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
+          const bool valid = idx < n;
+          const uint32_t sib = ((idx >> sh) ^ 1u) << sh;
+          mk[e] = valid ? sk[idx] : 0ULL;
+          mp[e] = valid ? sp[idx] : 0u;
+          at[e] = min(sib, n);
+          end[e] = valid ? min(sib + L, n) : at[e];  // (a slot past the bucket tests nothing)
+        }
+        for (uint32_t step = L; step; step >>= 1) {
+          uint64_t ok[G];
+          uint32_t op[G];
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-          if (e * LOC_SORT_THREADS >= n) continue;
-          const uint32_t t = cnt[e] + step;
-          const uint32_t at = t <= len[e] ? sb[e] + t - 1u : 0u;  // slot 0 when there is nothing to test: always readable
-          ok[e] = sk[at];
-          op[e] = sp[at];
+          for (int e = 0; e < G; ++e) {
+            const uint32_t q = at[e] + step <= end[e] ? at[e] + step - 1u : 0u;  // slot 0 when there is nothing to test: always readable
+            ok[e] = sk[q];
+            op[e] = sp[q];
+          }
+#pragma unroll
+          for (int e = 0; e < G; ++e)
+            if (at[e] + step <= end[e] && comp_less(ok[e], op[e], mk[e], mp[e])) at[e] += step;
         }
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-          if (e * LOC_SORT_THREADS >= n) continue;
-          const uint32_t t = cnt[e] + step;
-          if (t <= len[e] && comp_less(ok[e], op[e], mk[e], mp[e])) cnt[e] = t;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const uint32_t idx = threadIdx.x + e * LOC_SORT_THREADS;
-        if (idx < n) {
-          const uint32_t r = idx >> sh;
-          const uint32_t dst = ((r & ~1u) << sh) + (idx - (r << sh)) + cnt[e];
-          dk[dst] = mk[e];
-          dp[dst] = mp[e];
+        for (int e = 0; e < G; ++e) {
+          const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
+          if (idx < n) {
+            // slot = start of the run pair + offset in the own run + smaller pairs in the sibling run (at - sibling start)
+            //      = idx + at - (start of the pair's SECOND run, capped at n), whichever of the two runs the pair is in
+            const uint32_t dst = idx + at[e] - min((idx & ~(L - 1u)) | L, n);
+            dk[dst] = mk[e];
+            dp[dst] = mp[e];
+          }
         }
       }
       __syncthreads();
@@ -675,11 +677,9 @@ __device__ __forceinline__ BucketSummary loc_bucket_summary(const uint64_t* sk, 
       last = t;  // ascending t per thread
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    last = max(last, (uint32_t)__shfl_xor(last, o, 64));
-  }
+  // wave totals: lane 63 of the in-wave scans (the __shfl_xor butterfly kept six lane-address registers live through the kernel)
+  cnt = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive<false>(cnt), 63);
+  last = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive<true>(last), 63);
   if ((threadIdx.x & 63) == 0) {
     red[0][threadIdx.x >> 6] = cnt;
     red[1][threadIdx.x >> 6] = last;
@@ -740,8 +740,11 @@ __device__ __forceinline__ void loc_sort_block(const LocView& v, const uint32_t 
     }
   }
 }
+// The LDS is DYNAMIC (launched with loc_sort_smem() bytes): with 24.6 KB declared statically the compiler knows that LDS alone
+// limits the kernel to 6 waves per SIMD and pads its register count to what 6 waves may take (.amdhsa_next_free_vgpr 73: 80
+// registers allocated per wave, whatever the code uses) — room it never needs on its own, taken from the training step beside it
 __global__ void __launch_bounds__(LOC_SORT_THREADS) k_loc_sort(LocView v) {
-  __shared__ __attribute__((aligned(16))) char smem[loc_sort_smem()];
+  extern __shared__ __attribute__((aligned(16))) char smem[];
   loc_sort_block(v, blockIdx.x, gridDim.x, smem);
 }
 
@@ -829,17 +832,25 @@ __device__ __forceinline__ void loc_emit_bucket(const LocView& v, uint32_t b, ui
         else if (len > BWD_SMALL) sl.mid_ent[moff + atomicAdd(n_mid, 1u)] = e;
         else if (len > 1) sl.few_ent[foff + atomicAdd(n_few, 1u)] = e;
       }
-      // the splitters of the next call: the exact P-quantiles of this sorted order
-      if (P > 1) {
-        const uint64_t m = ((uint64_t)i * P + v.n - 1) / v.n;  // smallest m with m * n / P >= i
-        if (m >= 1 && m <= P - 1 && (m * v.n) / P == i) {
-          v.spl_key[m - 1] = key;
-          v.spl_pos[m - 1] = tag;
-        }
-      }
     }
     run_heads += nh;
     run_max1 = max(run_max1, mx);
+  }
+  // the splitters of the next call: the exact P-quantiles of this sorted order.  Splitter m - 1 is the pair at i = m * n / P, written
+  // when m is the smallest m' with m' * n / P >= i; the m whose i falls into this bucket form the range [m0, m1) — outside the
+  // per-element loop, whose registers the 64-bit divisions would raise
+  if (P > 1) {
+    const uint64_t N = v.n;
+    const uint64_t m0 = max((uint64_t)beg * P / N + ((uint64_t)beg * P % N ? 1u : 0u), (uint64_t)1);    // ceil(beg P / n)
+    const uint64_t e1 = (uint64_t)(beg + n) * P;
+    const uint64_t m1 = min(e1 / N + (e1 % N ? 1u : 0u), (uint64_t)P);                                  // ceil(end P / n), capped: m <= P - 1
+    for (uint64_t m = m0 + threadIdx.x; m < m1; m += blockDim.x) {
+      const uint32_t i = (uint32_t)(m * N / P);
+      if ((i * (uint64_t)P + N - 1) / N == m) {
+        v.spl_key[m - 1] = sk[i - beg];
+        v.spl_pos[m - 1] = sp[i - beg];
+      }
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
