@@ -33,6 +33,9 @@ SYMBOLS = [
     "dfh_shard_pull_host", "dfh_shard_push_host", "dfh_comm_allgather", "dfh_shard_balanced_splits", "dfh_shard_set_exchange", "dfh_shard_set_timing", "dfh_shard_get_timing",
     "dfh_comm_stats", "dfh_comm_info", "dfh_comm_selfcheck", "dfh_comm_wire_probe", "dfh_table_capacity", "dfh_batch_prepare_rows", "dfh_rowbuf_load_host_slices",
     "dfh_batch_create_many", "dfh_shard_multi_words", "dfh_shard_reserve", "dfh_comm_create_loopback", "dfh_comm_loopback_feed", "dfh_comm_loopback_wire", "dfh_comm_loopback_wire_time",
+    "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
+    "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
+    "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -204,6 +207,22 @@ def lib():
     L.dfh_comm_loopback_wire_time.argtypes = [vp, i32, PP(C.c_double)]
     L.dfh_shard_set_timing.argtypes = [vp, i32]
     L.dfh_shard_get_timing.argtypes = [vp, i32, vp, PP(u64)]
+    dp = PP(C.c_double)
+    L.dfh_vec_inner_multi.argtypes = [vp, u64, i32, vp, i32, vp, dp]
+    L.dfh_vec_combine.argtypes = [vp, u64, i32, vp, vp, f32, vp, vp, dp]
+    L.dfh_vec_line_step.argtypes = [vp, u64, vp, vp, f32, vp, f32, f32, dp]
+    L.dfh_lbfgs_create.argtypes = [vp, i32, i32, PP(vp)]
+    L.dfh_lbfgs_destroy.argtypes = [vp]
+    L.dfh_lbfgs_add_chunk.argtypes = [vp, i32, sz, vp, vp, vp, vp]
+    L.dfh_lbfgs_init_model.argtypes = [vp, f32, i32, f32, f32, f32, PP(u64), PP(u64)]
+    L.dfh_lbfgs_shape.argtypes = [vp, PP(u64), PP(u64), PP(i32), PP(i32)]
+    L.dfh_lbfgs_get_model.argtypes = [vp, vp, vp, vp, vp]
+    L.dfh_lbfgs_set_weights.argtypes = [vp, vp]
+    L.dfh_lbfgs_calc_grad.argtypes = [vp, f32, PP(f32), PP(f32)]
+    L.dfh_lbfgs_prepare_direction.argtypes = [vp, vp, PP(i32)]
+    L.dfh_lbfgs_calc_direction.argtypes = [vp, vp, PP(f32)]
+    L.dfh_lbfgs_line_search.argtypes = [vp, f32, f32, PP(f32), PP(f32), PP(f32)]
+    L.dfh_lbfgs_evaluate.argtypes = [vp, PP(f32), PP(f32), PP(f32)]
     _lib = L
     return L
 
@@ -670,6 +689,108 @@ class DeviceBuffer:
         if self.ptr:
             lib().dfh_free(self.ctx.h, self.ptr)
             self.ptr = None
+
+
+def _ptrs(ptrs):
+    """a host array of device pointers (DeviceBuffer, int, c_void_p or torch tensors)"""
+    arr = (C.c_void_p * max(len(ptrs), 1))()
+    for i, x in enumerate(ptrs):
+        arr[i] = (x.ptr if isinstance(x, DeviceBuffer) else _dp(x)).value
+    return arr
+
+
+def vec_inner_multi(ctx, n, a, b):
+    """[len(a) x len(b)] inner products of device vectors (fp32 products summed in fp64)"""
+    out = np.zeros(len(a) * len(b), np.float64)
+    _ck(lib().dfh_vec_inner_multi(ctx.h, n, len(a), _ptrs(a), len(b), _ptrs(b), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.reshape(len(a), len(b))
+
+
+def vec_combine(ctx, n, vecs, coef, out, dot=None, clamp=5.0):
+    """out = clamp(sum of lbfgs::Add(coef[k], vecs[k]) in order); returns <dot, out> (None without dot)"""
+    c = np.ascontiguousarray(coef, np.float32)
+    d = C.c_double(0)
+    _ck(lib().dfh_vec_combine(ctx.h, n, len(vecs), _ptrs(vecs), _p(c), clamp, _ptrs([out])[0],
+                              _ptrs([dot])[0] if dot is not None else None, C.byref(d)))
+    return d.value if dot is not None else None
+
+
+def vec_line_step(ctx, n, w, p, x, vmask=None, l2=0.0, V_l2=0.0):
+    """w += x p (lbfgs::Add); returns (r(w), <grad r(w), p>, nnz(w))"""
+    out = np.zeros(3, np.float64)
+    _ck(lib().dfh_vec_line_step(ctx.h, n, _ptrs([w])[0], _ptrs([p])[0] if p is not None else None, x,
+                                _ptrs([vmask])[0] if vmask is not None else None, l2, V_l2,
+                                out.ctypes.data_as(C.POINTER(C.c_double))))
+    return tuple(out)
+
+
+class Lbfgs:
+    """the full-batch L-BFGS state resident in HBM (dfh_lbfgs): data chunks, model, gradients, s / y history"""
+
+    def __init__(self, ctx, V_dim, m):
+        self.ctx, self.V_dim, self.m = ctx, V_dim, m
+        self.h = C.c_void_p()
+        _ck(lib().dfh_lbfgs_create(ctx.h, V_dim, m, C.byref(self.h)))
+
+    def add_chunk(self, offset, index, value, label, is_val=False):
+        offset = np.ascontiguousarray(offset, np.uint64)
+        index = np.ascontiguousarray(index, np.uint64)
+        value = None if value is None else np.ascontiguousarray(value, np.float32)
+        label = np.ascontiguousarray(label, np.float32)
+        _ck(lib().dfh_lbfgs_add_chunk(self.h, int(is_val), len(offset) - 1, _p(offset), _p(index), _p(value), _p(label)))
+
+    def init_model(self, tail_feature_filter=0, V_threshold=0, V_init_scale=0.01, l2=0.0, V_l2=0.0):
+        k, n = C.c_uint64(0), C.c_uint64(0)
+        _ck(lib().dfh_lbfgs_init_model(self.h, tail_feature_filter, V_threshold, V_init_scale, l2, V_l2, C.byref(k), C.byref(n)))
+        self.nkeys, self.n = k.value, n.value
+        return self.nkeys, self.n
+
+    def get_model(self):
+        keys = np.zeros(max(self.nkeys, 1), np.uint64)
+        lens = np.zeros(max(self.nkeys, 1), np.int32)
+        cnt = np.zeros(max(self.nkeys, 1), np.float32)
+        w = np.zeros(max(self.n, 1), np.float32)
+        _ck(lib().dfh_lbfgs_get_model(self.h, _p(keys), _p(lens), _p(cnt), _p(w)))
+        return dict(keys=keys[:self.nkeys], lens=lens[:self.nkeys], cnt=cnt[:self.nkeys], w=w[:self.n])
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, np.float32)
+        _ck(lib().dfh_lbfgs_set_weights(self.h, _p(w)))
+
+    def calc_grad(self, gamma=1.0):
+        loss, auc = C.c_float(0), C.c_float(0)
+        _ck(lib().dfh_lbfgs_calc_grad(self.h, gamma, C.byref(loss), C.byref(auc)))
+        return loss.value, auc.value
+
+    def prepare_direction(self):
+        """-> incr_B [6 mcur + 1] (float32), or None at the first epoch"""
+        incr = np.zeros(6 * self.m + 1, np.float32)
+        mc = C.c_int(0)
+        _ck(lib().dfh_lbfgs_prepare_direction(self.h, _p(incr), C.byref(mc)))
+        return incr[:6 * mc.value + 1] if mc.value else None
+
+    def calc_direction(self, coef=None):
+        pg = C.c_float(0)
+        c = None if coef is None else np.ascontiguousarray(coef, np.float32)
+        _ck(lib().dfh_lbfgs_calc_direction(self.h, _p(c), C.byref(pg)))
+        return pg.value
+
+    def line_search(self, alpha, gamma=1.0):
+        """-> (f(w + alpha p), <grad f, p>, AUC x n)"""
+        f, pg, auc = C.c_float(0), C.c_float(0), C.c_float(0)
+        _ck(lib().dfh_lbfgs_line_search(self.h, alpha, gamma, C.byref(f), C.byref(pg), C.byref(auc)))
+        return f.value, pg.value, auc.value
+
+    def evaluate(self, val=False):
+        """-> (validation AUC x n or None, nnz(w), r(w))"""
+        va, nnz, r = C.c_float(0), C.c_float(0), C.c_float(0)
+        _ck(lib().dfh_lbfgs_evaluate(self.h, C.byref(va) if val else None, C.byref(nnz), C.byref(r)))
+        return (va.value if val else None), nnz.value, r.value
+
+    def close(self):
+        if self.h:
+            lib().dfh_lbfgs_destroy(self.h)
+            self.h = None
 
 
 def row_stride(V_dim):

@@ -3629,3 +3629,4 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 }  // extern "C"
 
 #include "dfh_shard.hip"
+#include "dfh_lbfgs.hip"

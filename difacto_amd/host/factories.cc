@@ -5,6 +5,7 @@
  */
 #include "./device_store.h"
 #include "./hip_fm_loss.h"
+#include "./lbfgs_learner.h"
 #include "./local_tracker.h"
 #include "./sgd_learner.h"
 #include "./sharded_store.h"
@@ -41,7 +42,8 @@ Tracker* Tracker::Create() { return new LocalTracker(); }
 
 Learner* Learner::Create(const std::string& type) {
   if (type == "sgd") return new SGDLearner();
-  LOG(FATAL) << "learner type " << type << " is not part of this build (sgd only)";
+  if (type == "lbfgs") return new LBFGSLearner();
+  LOG(FATAL) << "learner type " << type << " is not part of this build (sgd and lbfgs)";
   return nullptr;
 }
 

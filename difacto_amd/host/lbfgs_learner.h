@@ -1,0 +1,92 @@
+/**
+ * lbfgs_learner.h — LBFGSLearner: the reference's full-batch L-BFGS learner (src/lbfgs/lbfgs_learner.{h,cc}) with the
+ * training data, the model and the whole optimiser state resident in HBM (dfh_lbfgs, include/difacto_hip.h).
+ *
+ * The scheduler loop (RunScheduler: direction, Wolfe line search, stop criteria, epoch-end callbacks) follows
+ * lbfgs_learner.cc:14-126 line by line.  The jobs it issues there to workers and servers are calls on one dfh_lbfgs
+ * object here: one process, one GPU.  The (2m+1)^2 B-matrix algebra of the two-loop recursion stays on the host
+ * (lbfgs_mini::Twoloop), the vectors never leave the device.
+ *
+ * Differences from the reference:
+ *   - no tile store on disk (data_cache is accepted and unused) and no thread pool (num_threads is accepted and unused)
+ *   - model_out is written (the reference declares it and never writes it): the final weights in the format of
+ *     learner = sgd's model_out, without optimiser state, so that task = predict learner = sgd model_in = ... scores them
+ *   - a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) and task = predict are refused with a message
+ */
+#ifndef DIFACTO_HOST_LBFGS_LEARNER_H_
+#define DIFACTO_HOST_LBFGS_LEARNER_H_
+#include <functional>
+#include <string>
+#include <vector>
+#include "./lbfgs_mini.h"
+#include "./lbfgs_param.h"
+#include "difacto/learner.h"
+#include "difacto/sarray.h"
+#include "difacto_hip.h"
+
+namespace difacto {
+namespace lbfgs {
+
+/*! \brief lbfgs_utils.h:46-60 */
+struct Progress {
+  real_t objv;     // objective value on training data
+  real_t auc;      // auc on training data
+  real_t val_auc;  // auc on validation data
+  real_t nnz_w;    // number of nonzero entries in the model
+};
+
+}  // namespace lbfgs
+
+/*! \brief what the reference's LBFGSUpdater exposes to a learner's user (lbfgs_updater.h:12-33): its parameters and the
+ * weight initializer; the state itself lives in the dfh_lbfgs object */
+class LBFGSUpdater {
+ public:
+  KWArgs Init(const KWArgs& kwargs) { return param_.InitAllowUnknown(kwargs); }
+  const LBFGSUpdaterParam& param() const { return param_; }
+  typedef std::function<void(const SArray<int>& weight_lens, SArray<real_t>* weights)> WeightInitializer;
+  void SetWeightInitializer(const WeightInitializer& initer) { weight_initializer_ = initer; }
+  const WeightInitializer& weight_initializer() const { return weight_initializer_; }
+
+ private:
+  LBFGSUpdaterParam param_;
+  WeightInitializer weight_initializer_ = nullptr;
+};
+
+class LBFGSLearner : public Learner {
+ public:
+  LBFGSLearner() {}
+  virtual ~LBFGSLearner();
+  KWArgs Init(const KWArgs& kwargs) override;
+
+  void AddEpochEndCallback(const std::function<void(int epoch, const lbfgs::Progress& prog)>& callback) {
+    epoch_end_callback_.push_back(callback);
+  }
+  LBFGSUpdater* GetUpdater() { return &updater_; }
+
+ protected:
+  void RunScheduler() override;
+  void Process(const std::string& args, std::string* rets) override {}
+
+ private:
+  /*! \brief PrepareData (lbfgs_learner.cc:165-210): read the data into chunks resident on the device; returns
+   * {ntrain, train chunks, train nnz, nval, val chunks, val nnz} */
+  void PrepareData(std::vector<real_t>* rets);
+  /*! \brief InitWeight (lbfgs_updater.h:33-76) with the weight initializer; returns {r(w), number of parameters} */
+  void InitServer(std::vector<real_t>* rets);
+  /*! \brief the epoch's search direction, written into the s history; returns <p, g> */
+  float Direction();
+  /*! \brief the Wolfe line search from objective objv along p (<p, g> = pg), starting at step; returns the accepted
+   * objective, *auc = AUC x n of the last gradient pass */
+  real_t LineSearch(real_t step, real_t objv, float pg, float* auc);
+  void SaveModel();
+
+  LBFGSLearnerParam param_;
+  LBFGSUpdater updater_;
+  int nthreads_ = 1;
+  dfh_lbfgs* obj_ = nullptr;
+  lbfgs_mini::Twoloop twoloop_;
+  std::vector<std::function<void(int epoch, const lbfgs::Progress& prog)>> epoch_end_callback_;
+};
+
+}  // namespace difacto
+#endif  // DIFACTO_HOST_LBFGS_LEARNER_H_

@@ -104,6 +104,26 @@ class Twoloop {
     for (int i = 0; i < m_; ++i) Add(static_cast<real_t>(d[i + m_]), y[i], p);
     Add(static_cast<real_t>(d[2 * m_]), grad, p);
   }
+  /*! \brief CalcDirection's 2m+1 coefficients alone (the B-matrix algebra, lbfgs_twoloop.h:86-102), for a caller that
+   * keeps s, y and grad elsewhere: p = Add(coef[i], s_i) for i < m, then Add(coef[m+i], y_i), then Add(coef[2m], grad) */
+  void CalcCoefficients(std::vector<real_t>* coef) const {
+    std::vector<double> d(2 * m_ + 1, 0.0), alpha(m_, 0.0);
+    d[2 * m_] = -1;
+    for (int i = m_ - 1; i >= 0; --i) {
+      for (int l = 0; l < 2 * m_ + 1; ++l) alpha[i] += d[l] * B_[l][i];
+      alpha[i] /= B_[i][m_ + i] + 1e-10;
+      d[m_ + i] -= alpha[i];
+    }
+    for (int i = 0; i < 2 * m_ + 1; ++i) d[i] *= B_[m_ - 1][2 * m_ - 1] / (B_[2 * m_ - 1][2 * m_ - 1] + 1e-10);
+    for (int i = 0; i < m_; ++i) {
+      double beta = 0;
+      for (int l = 0; l < 2 * m_ + 1; ++l) beta += d[l] * B_[m_ + i][l];
+      beta /= B_[i][m_ + i] + 1e-10;
+      d[i] += alpha[i] - beta;
+    }
+    coef->resize(2 * m_ + 1);
+    for (int i = 0; i < 2 * m_ + 1; ++i) (*coef)[i] = static_cast<real_t>(d[i]);
+  }
 
  private:
   int m_ = 0;

@@ -498,6 +498,55 @@ int dfh_shard_pull_host(dfh_shard* s, const uint64_t* keys, size_t n, float* val
 int dfh_shard_push_host(dfh_shard* s, const uint64_t* keys, size_t n, int val_type, const float* vals, size_t nvals, const int* lens,
                         size_t nlens);
 
+/* ------------------------------------------------ full-batch L-BFGS (learner = lbfgs) */
+/* Vector kernels of LBFGSUpdater on DEVICE pointers (16-byte aligned), fp32 elements; every reduction runs in a fixed
+ * order (the same answer on every run) and synchronises.
+ * dfh_vec_inner_multi: out[i * nb + j] = <a_i, b_j> as lbfgs::Inner (src/lbfgs/lbfgs_utils.h:62-72): fp32 products summed
+ * in fp64, one pass that reads every distinct vector once (Twoloop::CalcIncreB, lbfgs_twoloop.h:19-43); na <= 3, nb <= 33. */
+int dfh_vec_inner_multi(dfh_ctx* ctx, uint64_t n, int na, const float* const* a, int nb, const float* const* b, double* out);
+/* dfh_vec_combine: per element p = 0; lbfgs::Add(coef[k], v[k], &p) for k = 0 .. nv-1 in order (coef 0 skipped, coef 1 a
+ * plain add, lbfgs_utils.h:74-88); p clamped to +-clampv (lbfgs_updater.h:117); out = p (out may be one of v); *out_dot =
+ * <dot, p> when dot is not NULL (LBFGSUpdater::CalcDirection, lbfgs_updater.h:107-123).  nv <= 33. */
+int dfh_vec_combine(dfh_ctx* ctx, uint64_t n, int nv, const float* const* v, const float* coef, float clampv, float* out,
+                    const float* dot, double* out_dot);
+/* dfh_vec_line_step: lbfgs::Add(x, p, &w) (p may be NULL: no step), then out3 = { r(w) = sum .5 coef w^2, <coef w, p>,
+ * nnz(w) } with coef = V_l2 where bit i of vmask is set and l2 elsewhere (vmask NULL: l2 everywhere) —
+ * LBFGSUpdater::LineSearch / Evaluate / AddRegularizerGrad (lbfgs_updater.h:125-133, 170-203) */
+int dfh_vec_line_step(dfh_ctx* ctx, uint64_t n, float* w, const float* p, float x, const uint32_t* vmask, float l2, float V_l2,
+                      double* out3);
+
+/* The learner's state, resident in HBM from load to finish: the localized training and validation chunks (one dfh_batch
+ * each, plus its key -> model map), the model (keys ascending, lens, w: per key w [, V]) and w, g_new, g and the s / y
+ * history of m pairs (1 <= m <= 16).  One process, one GPU.  Calls follow the jobs of LBFGSLearner::Process
+ * (src/lbfgs/lbfgs_learner.cc:128-163); each synchronises.  Data or state that does not fit in HBM fails with
+ * DFH_ERR_CAPACITY and the bytes needed. */
+typedef struct dfh_lbfgs dfh_lbfgs;
+int dfh_lbfgs_create(dfh_ctx* ctx, int V_dim, int m, dfh_lbfgs** out);
+int dfh_lbfgs_destroy(dfh_lbfgs* o);
+/* a chunk of raw rows (Reader::Value()), localized on the device with Localizer(-1) (TileBuilder::Add) and kept */
+int dfh_lbfgs_add_chunk(dfh_lbfgs* o, int is_val, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,
+                        const float* label);
+/* InitWeight (lbfgs_updater.h:33-76) + InitWorker's filter and colmap (lbfgs_learner.cc:189-212): merged training counts,
+ * keys with cnt > tail_feature_filter survive (filter <= 0: all), lens = 1 + (cnt > V_threshold ? V_dim : 0), w = 0 and
+ * V from the rand_r(seed = 0) chain in key order */
+int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshold, float V_init_scale, float l2, float V_l2,
+                         uint64_t* nkeys, uint64_t* nparams);
+int dfh_lbfgs_shape(dfh_lbfgs* o, uint64_t* nkeys, uint64_t* nparams, int* ntrain_chunks, int* nval_chunks);
+/* read the model back (any pointer may be NULL): keys [nkeys], lens [nkeys], merged counts [nkeys], w [nparams] */
+int dfh_lbfgs_get_model(dfh_lbfgs* o, uint64_t* keys, int* lens, float* feacnt, float* w);
+/* SetWeightInitializer: replace w [nparams] before training starts */
+int dfh_lbfgs_set_weights(dfh_lbfgs* o, const float* w);
+/* CalcGrad (lbfgs_learner.cc:246-305) into g_new: loss and AUC x n summed per chunk as the reference sums them */
+int dfh_lbfgs_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n);
+/* PrepareCalcDirection: *mcur = history pairs in use (0 at epoch 0: nothing is returned), incr_B [6 mcur + 1] */
+int dfh_lbfgs_prepare_direction(dfh_lbfgs* o, float* incr_B, int* mcur);
+/* CalcDirection with the two-loop coefficients d [2 mcur + 1] (NULL at epoch 0: p = -g); *p_g = <p, g> */
+int dfh_lbfgs_calc_direction(dfh_lbfgs* o, const float* d, float* p_g);
+/* LineSearch(alpha): w += (alpha - alpha_) p, CalcGrad; *objv = f(w + alpha p), *p_g = <grad f, p>, *auc_n (may be NULL) */
+int dfh_lbfgs_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, float* p_g, float* auc_n);
+/* Evaluate: validation AUC x n (NULL: skipped), nnz(w), r(w) */
+int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w);
+
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
 int dfh_free(dfh_ctx* ctx, void* dptr);
