@@ -16,6 +16,9 @@ The timed region is K steps (sync + barrier on both sides); with --min-time S it
 least S seconds have been measured and the line reports the MEDIAN repetition and the spread.
 --dump-outputs DIR writes what the last timed step computed (see dump_outputs) for output-for-output
 comparisons of two builds: the inputs are seeded, so the same arguments give the same inputs.
+A plain run does only what the headline needs: set up, warm up, time the steps, dump, print.  --full adds
+what takes runs of its own: the per-kernel breakdown pass (`kernel_ms_per_step`), the CPU baseline
+(`cpu_baseline`, --cpu-batches) and, for the default preset, the `secondary` lines (--no-secondary drops them).
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
 """
 import argparse
@@ -77,13 +80,20 @@ def parse_args():
     ap.add_argument("--min-time", type=float, default=0.0,
                     help="repeat the K-step region until this many seconds are timed (0: one region, exactly --steps timed steps)")
     ap.add_argument("--max-reps", type=int, default=20000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the per-kernel breakdown pass, the CPU "
+                         "baseline and (N=1, preset c3) the `secondary` lines.  Off: the line carries the headline and what the "
+                         "timed region itself measured")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N=1, preset c3: skip the `secondary` block (c3-refdefaults and c5-slice, each run as a child process "
-                         "after the headline measurement has released the GPU)")
+                    help="with --full, N=1, preset c3: skip the `secondary` block (c3-refdefaults and c5-slice, each run as a "
+                         "child process after the headline measurement has released the GPU)")
     ap.add_argument("--secondary-min-time", type=float, default=1.0)
     ap.add_argument("--no-prefill", action="store_true", help="start from an empty model instead of a warm one")
-    ap.add_argument("--cpu-batches", type=int, default=-1, help="batches in the CPU baseline sample (-1: auto, 0: skip)")
-    ap.add_argument("--no-timing", action="store_true", help="skip per-kernel HIP-event timing")
+    ap.add_argument("--cpu-batches", type=int, default=-1,
+                    help="with --full: batches in the CPU baseline sample (-1: auto, 0: skip)")
+    ap.add_argument("--no-timing", action="store_true",
+                    help="skip per-kernel HIP-event timing (the live events inside the timed region and, with --full, the "
+                         "breakdown pass)")
     ap.add_argument("--no-pipeline", action="store_true", help="prepare and train on one stream")
     ap.add_argument("--prep-streams", type=int, default=1,
                     help="preparation streams = minibatches localized ahead of the one training (sgd_learner.cc:219-223 "
@@ -265,7 +275,7 @@ def secondary_lines(args):
             ("c2", ["--preset", "c2", "--cpu-batches", "100"])]
     for name, extra in runs:
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--min-time", str(args.secondary_min_time), "--no-secondary"] + extra   # (later flags win: c3-cold sets its own steps)
+               "--min-time", str(args.secondary_min_time), "--full", "--no-secondary"] + extra   # (later flags win: c3-cold sets its own steps)
         t0 = time.time()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -431,8 +441,8 @@ def main():
     if args.gpus > 1 or world > 1 or args.force_sharded:
         if args.transport == "native":
             from difacto_amd import sharded
-            return sharded.bench_main_native(args, rank, world, local_rank, args.hyper,
-                                             cpu_baseline_fn=lambda hb, k_, nb_, hy_: cpu_baseline(hb, k_, nb_, hy_, with_auc=not args.no_auc),
+            cpu_fn = (lambda hb, k_, nb_, hy_: cpu_baseline(hb, k_, nb_, hy_, with_auc=not args.no_auc)) if args.full else None
+            return sharded.bench_main_native(args, rank, world, local_rank, args.hyper, cpu_baseline_fn=cpu_fn,
                                              pmc_traffic_fn=pmc_traffic)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import sharded_harness   # the torch.distributed transport: test infrastructure, not the product path
@@ -595,9 +605,9 @@ def main():
     loss_sum = sum(p.loss for p in progs)
     rows_sum = sum(p.nrows for p in progs)
     timing = {} if args.no_timing else ctx.get_timing(reset=True)
-    # per-kernel breakdown from a separate, fully instrumented pass (NOT part of the timed region)
+    # --full: per-kernel breakdown from a separate, fully instrumented pass (NOT part of the timed region)
     breakdown = {}
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         nb_steps = min(args.steps, 50)
         ctx.set_timing(True)
         for i in range(nb_steps):
@@ -644,7 +654,7 @@ def main():
                             frac_hbm_necessary=nec / (bwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                             avg_launch_ms=bwd_ms, launches_timed=int(timing["backward"][1]))
     secondary = None
-    if args.preset == "c3" and not args.no_secondary:
+    if args.full and args.preset == "c3" and not args.no_secondary:
         # release the headline run's table and batches first: the C5 slice takes most of the HBM
         for b in bts:
             b.close()
@@ -659,7 +669,7 @@ def main():
         secondary = secondary_lines(args)
     else:
         tbytes = table.bytes()
-    nb = args.cpu_batches
+    nb = args.cpu_batches if args.full else 0
     cpu = None
     if nb != 0:
         if nb < 0:
@@ -708,7 +718,8 @@ def main():
         "secondary": secondary,
         "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3,
         "kernel_ms_per_step": breakdown,
-        "kernel_ms_per_step_note": "separate instrumented pass after the timed region (HIP events around every kernel group)",
+        "kernel_ms_per_step_note": "--full: separate instrumented pass after the timed region (HIP events around every kernel group)",
+        "full": args.full,
         "train_logloss_per_example": loss_sum / max(rows_sum, 1),
         "hbm_gbps_step_algorithmic": ex_per_s * r_g / 1e9,
         "prefill_seconds": t_prefill,

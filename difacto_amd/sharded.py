@@ -296,10 +296,10 @@ def bench_main_native(args, rank, world, local_rank, hyper, cpu_baseline_fn=None
     x_steps = len(reps) * args.steps
     fwd_t = ctx.get_timing(reset=True).get("forward", (0.0, 0)) if mask else (0.0, 0)
     table.check()
-    # per-stage device time from a separate, instrumented pass (NOT part of the timed region): HIP events around the
-    # stages of dfh_shard_step on the stream each stage runs on; max over the ranks per stage
+    # --full: per-stage device time from a separate, instrumented pass (NOT part of the timed region): HIP events around
+    # the stages of dfh_shard_step on the stream each stage runs on; max over the ranks per stage
     stage_ms = None
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         shard.set_timing(True)
         shard.get_timing(reset=True)
         n_inst = min(args.steps, 40)
@@ -384,7 +384,7 @@ def bench_main_native(args, rank, world, local_rank, hyper, cpu_baseline_fn=None
             "lr_divided_by_world": world,
             "wire_probe": wire_probe,
             "stage_ms_per_step": stage_ms,
-            "stage_ms_per_step_note": "separate instrumented pass; max over ranks per stage; counts/K/G/RW run on the "
+            "stage_ms_per_step_note": "--full: separate instrumented pass; max over ranks per stage; counts/K/G/RW run on the "
                                       "collectives' stream in overlap mode and overlap F/R/P on the main stream",
             "roofline": roofline, "roofline_exchange": roofline_x, "cpu_baseline": cpu,
             "train_logloss_per_example": tot[0] / max(tot[1], 1.0),

@@ -1,5 +1,5 @@
 """The bench line contract, checked on the line committed under profiles/ (produced by
-`python bench.py` on the MI355X box): every key the driver and the judge read is there, with the
+`python bench.py --full` on an MI355X): every key a reader of the line relies on is there, with the
 types and the relations the contract states."""
 import glob
 import json

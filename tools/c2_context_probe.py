@@ -25,4 +25,4 @@ tb = capi.Table(ctx, 1 << 20, V_dim=8)
 child("parent: + a dfh context and a table alive")
 tb.close(); ctx.close(); torch.cuda.empty_cache()
 child("parent: context closed again")
-child("parent: context closed, child with --cpu-batches 100", extra=["--cpu-batches", "100"])
+child("parent: context closed, child with --cpu-batches 100", extra=["--full", "--cpu-batches", "100"])

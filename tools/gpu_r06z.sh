@@ -8,7 +8,7 @@ python -c "from difacto_amd.build import build_hip, build_host; build_hip(); bui
 ( time DFH_PARITY_RECORD=$O/parity.json DFH_PARITY_RECORD_STEPS=$O/parity_steps.json timeout 1800 python -m pytest tests -m gpu -q ) > $O/pytest_gpu.log 2>&1
 grep -E "passed|failed" $O/pytest_gpu.log | tail -2 | cut -c1-300; grep -E "^E |^FAILED" $O/pytest_gpu.log | head -30
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-( time timeout 900 python bench.py ) > $O/bench_c3.json 2> $O/bench_c3.err; tail -3 $O/bench_c3.err
+( time timeout 900 python bench.py --full ) > $O/bench_c3.json 2> $O/bench_c3.err; tail -3 $O/bench_c3.err
 python -c "
 import json
 d=json.loads(open('$O/bench_c3.json').read().strip().splitlines()[-1])
@@ -18,7 +18,7 @@ print(' cpu', d['cpu_baseline']['value'], d['cpu_baseline'].get('scaled_threads'
 "
 line() {  # name args...
   n=$1; shift
-  timeout 400 python bench.py --cpu-batches 0 --min-time 1 --no-secondary "$@" > $O/bench_$n.json 2> $O/bench_$n.err
+  timeout 400 python bench.py --full --cpu-batches 0 --min-time 1 --no-secondary "$@" > $O/bench_$n.json 2> $O/bench_$n.err
   python -c "
 import json
 try:
@@ -37,7 +37,7 @@ line c2 --preset c2
 line c2_single_queue --preset c2 --single-queue
 line sharded_w1_native_overlap --force-sharded --exchange overlap
 line sharded_w1_native_sync --force-sharded --exchange sync
-( time timeout 600 python bench.py --force-sharded --min-time 1 ) > $O/bench_sharded_w1_full.json 2> $O/bench_sharded_w1_full.err; tail -2 $O/bench_sharded_w1_full.err
+( time timeout 600 python bench.py --force-sharded --full --min-time 1 ) > $O/bench_sharded_w1_full.json 2> $O/bench_sharded_w1_full.err; tail -2 $O/bench_sharded_w1_full.err
 timeout 900 python bench.py --emulate-world 8 --emulate-rank auto --cpu-batches 0 --min-time 1 > $O/emul_c4_w8.json 2> $O/emul_c4_w8.err
 python -c "
 import json

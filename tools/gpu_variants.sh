@@ -8,7 +8,7 @@ for v in "$@"; do
   cp $R/tools/var_$v.so $R/difacto_amd/libdifacto_hip.so
   for mode in "${MODES[@]}"; do
     n=$(echo "${v}_x$mode" | tr -d ' -')
-    timeout 200 python bench.py --cpu-batches 0 --min-time 0.3 $mode > $O/b_${n}.json 2> $O/b_${n}.err
+    timeout 200 python bench.py --full --cpu-batches 0 --min-time 0.3 $mode > $O/b_${n}.json 2> $O/b_${n}.err
     python -c "
 import json
 try:
