@@ -36,6 +36,8 @@ SYMBOLS = [
     "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
     "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate",
+    "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
+    "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -223,6 +225,16 @@ def lib():
     L.dfh_lbfgs_calc_direction.argtypes = [vp, vp, PP(f32)]
     L.dfh_lbfgs_line_search.argtypes = [vp, f32, f32, PP(f32), PP(f32), PP(f32)]
     L.dfh_lbfgs_evaluate.argtypes = [vp, PP(f32), PP(f32), PP(f32)]
+    L.dfh_bcd_create.argtypes = [vp, PP(vp)]
+    L.dfh_bcd_destroy.argtypes = [vp]
+    L.dfh_bcd_add_chunk.argtypes = [vp, i32, sz, vp, vp, vp, vp]
+    L.dfh_bcd_build.argtypes = [vp, f32, i32, vp, vp, f32, f32, PP(u64)]
+    L.dfh_bcd_shape.argtypes = [vp, PP(u64), PP(i32), PP(i32), PP(i32)]
+    L.dfh_bcd_block_info.argtypes = [vp, i32, PP(i32), PP(i32), PP(u64), PP(u64)]
+    L.dfh_bcd_epoch.argtypes = [vp, vp, i32, vp]
+    L.dfh_bcd_step.argtypes = [vp, i32, vp, vp, vp]
+    L.dfh_bcd_get_model.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.dfh_bcd_get_pred.argtypes = [vp, i32, i32, vp, PP(sz)]
     _lib = L
     return L
 
@@ -790,6 +802,76 @@ class Lbfgs:
     def close(self):
         if self.h:
             lib().dfh_lbfgs_destroy(self.h)
+            self.h = None
+
+
+class Bcd:
+    """the block coordinate descent state resident in HBM (dfh_bcd): data chunks with their per-block layouts,
+    predictions, and the model w / delta / delta w"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.nkeys = 0
+        _ck(lib().dfh_bcd_create(ctx.h, C.byref(self.h)))
+
+    def add_chunk(self, offset, index, value, label, is_val=False):
+        offset = np.ascontiguousarray(offset, np.uint64)
+        index = np.ascontiguousarray(index, np.uint64)
+        value = None if value is None else np.ascontiguousarray(value, np.float32)
+        label = np.ascontiguousarray(label, np.float32)
+        _ck(lib().dfh_bcd_add_chunk(self.h, int(is_val), len(offset) - 1, _p(offset), _p(index), _p(value), _p(label)))
+
+    def build(self, ranges, tail_feature_filter=0, l1=1.0, lr=0.9):
+        """ranges: [(begin, end)] of ReverseBytes keys, sorted and disjoint (PartitionFeature); -> number of keys"""
+        beg = np.ascontiguousarray([r[0] for r in ranges], np.uint64)
+        end = np.ascontiguousarray([r[1] for r in ranges], np.uint64)
+        k = C.c_uint64(0)
+        _ck(lib().dfh_bcd_build(self.h, tail_feature_filter, len(ranges), _p(beg), _p(end), l1, lr, C.byref(k)))
+        self.nkeys = k.value
+        self.nblk = len(ranges)
+        return self.nkeys
+
+    def block_info(self, blk):
+        """-> (model positions [begin, end), training entries, touched rows)"""
+        b, e, z, r = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        _ck(lib().dfh_bcd_block_info(self.h, blk, C.byref(b), C.byref(e), C.byref(z), C.byref(r)))
+        return b.value, e.value, z.value, r.value
+
+    def epoch(self, order):
+        """-> progress {count, objv, AUC x n, accuracy} as float32 [4]"""
+        order = np.ascontiguousarray(order, np.int32)
+        prog = np.zeros(4, np.float32)
+        _ck(lib().dfh_bcd_epoch(self.h, _p(order), len(order), _p(prog)))
+        return prog
+
+    def step(self, blk, grad=False, progress=False):
+        """one block; -> (g, h) in fp64 before the update when grad, and the progress [4] when progress"""
+        b, e, _, _ = self.block_info(blk)
+        g = np.zeros(max(e - b, 1), np.float64) if grad else None
+        h = np.zeros(max(e - b, 1), np.float64) if grad else None
+        prog = np.zeros(4, np.float32) if progress else None
+        _ck(lib().dfh_bcd_step(self.h, blk, _p(g), _p(h), _p(prog)))
+        return (g[:e - b] if grad else None), (h[:e - b] if grad else None), prog
+
+    def get_model(self):
+        n = max(self.nkeys, 1)
+        keys, cnt = np.zeros(n, np.uint64), np.zeros(n, np.float32)
+        w, delta, dw = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        _ck(lib().dfh_bcd_get_model(self.h, _p(keys), _p(cnt), _p(w), _p(delta), _p(dw)))
+        k = self.nkeys
+        return dict(keys=keys[:k], cnt=cnt[:k], w=w[:k], delta=delta[:k], dw=dw[:k])
+
+    def get_pred(self, chunk=0, is_val=False):
+        n = C.c_size_t(0)
+        _ck(lib().dfh_bcd_get_pred(self.h, int(is_val), chunk, None, C.byref(n)))
+        out = np.zeros(n.value, np.float32)
+        _ck(lib().dfh_bcd_get_pred(self.h, int(is_val), chunk, _p(out), None))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().dfh_bcd_destroy(self.h)
             self.h = None
 
 

@@ -3630,3 +3630,4 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 
 #include "dfh_shard.hip"
 #include "dfh_lbfgs.hip"
+#include "dfh_bcd.hip"

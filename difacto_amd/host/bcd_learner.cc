@@ -1,0 +1,177 @@
+/**
+ * bcd_learner.cc — BCDLearner (bcd_learner.h).  Reference: src/bcd/bcd_learner.cc, src/bcd/bcd_utils.h.
+ */
+#include "./bcd_learner.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <limits>
+#include <mutex>
+#include "./batch_reader.h"
+#include "./device_context.h"
+
+namespace difacto {
+
+DMLC_REGISTER_PARAMETER(BCDLearnerParam);
+DMLC_REGISTER_PARAMETER(BCDUpdaterParam);
+
+namespace bcd {
+
+void PartitionFeature(int feagrp_nbits, const std::vector<std::pair<int, int>>& feagrps, std::vector<Range>* feablks) {
+  CHECK_EQ(feagrp_nbits % 4, 0) << "should be 0, 4, 8, ...";
+  feablks->clear();
+  for (auto f : feagrps) {
+    const int gid = f.first;
+    Range rg(ReverseBytes(EncodeFeaGrpID(0, gid, feagrp_nbits)),
+             ReverseBytes(EncodeFeaGrpID(std::numeric_limits<feaid_t>::max(), gid, feagrp_nbits)));
+    for (int i = 0; i < f.second; ++i) {
+      feablks->push_back(rg.Segment(i, f.second));
+      CHECK(feablks->back().Valid());
+    }
+  }
+  std::sort(feablks->begin(), feablks->end(), [](const Range& a, const Range& b) { return a.begin < b.begin; });
+  for (size_t i = 1; i < feablks->size(); ++i) {
+    auto& before = feablks->at(i - 1);
+    const auto& after = feablks->at(i);
+    if (before.end < after.begin) ++before.end;
+    CHECK_LE(before.end, after.begin);
+  }
+}
+
+FeaGroupStats::FeaGroupStats(int nbits) {
+  CHECK_LE(nbits, 16);
+  nbits_ = nbits;
+  value_.resize((1 << nbits_) + 2);
+}
+
+void FeaGroupStats::Add(size_t nrows, const size_t* offset, const feaid_t* index) {
+  real_t n = 0;
+  for (size_t i = 0; i < nrows; i += skip_) {
+    for (size_t j = offset[i]; j < offset[i + 1]; ++j) ++value_[DecodeFeaGrpID(index[j], nbits_)];
+    ++n;
+  }
+  value_[1 << nbits_] += n;
+  value_[(1 << nbits_) + 1] += nrows;
+}
+
+}  // namespace bcd
+
+BCDLearner::~BCDLearner() {
+  if (obj_) dfh_bcd_destroy(obj_);
+}
+
+KWArgs BCDLearner::Init(const KWArgs& kwargs) {
+  for (const auto& kw : kwargs)
+    CHECK(!(kw.first == "task" && kw.second == "predict"))
+        << "learner = bcd has no prediction task: train with model_out=<file>, then score with "
+           "task=predict learner=sgd model_in=<file> V_dim=0 pred_out=<file>";
+  const char* nw = getenv("DMLC_NUM_WORKER");
+  CHECK(!IsDistributed() && !(nw && atoi(nw) > 1))
+      << "learner = bcd runs in one process on one GPU: a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is not supported";
+  // bcd_learner.cc:15-34: the learner's, then the updater's keys; the loss (logit_delta) and the tile store take none
+  auto remain = Learner::Init(kwargs);
+  remain = param_.InitAllowUnknown(remain);
+  remain = updater_param_.InitAllowUnknown(remain);
+  CHECK_EQ(param_.num_feature_group_bits % 4, 0) << "num_feature_group_bits should be 0, 4, 8, ...";
+  CHECK(param_.num_feature_group_bits >= 0 && param_.num_feature_group_bits <= 16) << "num_feature_group_bits <= 16";
+  DFH_CALL(dfh_bcd_create(DeviceContext::Get(), &obj_));
+  return remain;
+}
+
+void BCDLearner::PrepareData(std::vector<real_t>* fea_stats) {
+  // Reader blocks of data_chunk_size bytes (bcd_learner.cc:98-108); a block beyond the batch object's 32-bit positions is
+  // cut by rows
+  const size_t chunk_bytes = std::max<size_t>(64, static_cast<size_t>(param_.data_chunk_size));
+  const size_t kMaxNnz = size_t(1) << 31;
+  bcd::FeaGroupStats stats(param_.num_feature_group_bits);
+  auto read = [&](const std::string& uri, int is_val) {
+    Reader reader(uri, param_.data_format, 0, 1, chunk_bytes);
+    while (reader.Next()) {
+      const auto& blk = reader.Value();
+      for (size_t r0 = 0; r0 < blk.size;) {
+        size_t r1 = r0 + 1;
+        while (r1 < blk.size && blk.offset[r1 + 1] - blk.offset[r0] <= kMaxNnz) ++r1;
+        if (!is_val) {
+          stats.Add(r1 - r0, blk.offset + r0, blk.index);   // bcd_learner.cc:107
+          chunk_rows_.push_back(r1 - r0);
+        }
+        DFH_CALL(dfh_bcd_add_chunk(obj_, is_val, r1 - r0, blk.offset + r0, blk.index, blk.value, blk.label + r0));
+        r0 = r1;
+      }
+    }
+  };
+  read(param_.data_in, 0);
+  stats.Get(fea_stats);
+  if (param_.data_val.size()) read(param_.data_val, 1);   // bcd_learner.cc:118-129
+}
+
+void BCDLearner::RunScheduler() {
+  // bcd_learner.cc:51-92, with the worker / server jobs as calls on the dfh_bcd object
+  LOG(INFO) << "loading data... ";
+  std::vector<real_t> load_rets;
+  PrepareData(&load_rets);
+  LOG(INFO) << "loaded " << load_rets.back() << " examples";
+
+  // partition feature group and build feature map
+  std::vector<std::pair<int, int>> feagrp;
+  const int nfeablk = static_cast<int>(load_rets.size()) - 2;
+  for (int i = 0; i < nfeablk; ++i) {
+    const int nblk = static_cast<int>(std::ceil(load_rets[i] / load_rets[nfeablk] * param_.block_ratio));
+    if (nblk > 0) feagrp.push_back(std::make_pair(i, nblk));
+  }
+  std::vector<bcd::Range> ranges;
+  bcd::PartitionFeature(param_.num_feature_group_bits, feagrp, &ranges);
+  LOG(INFO) << "partitioning feature into " << ranges.size() << " blocks";
+  std::vector<uint64_t> beg(ranges.size()), end(ranges.size());
+  for (size_t i = 0; i < ranges.size(); ++i) {
+    beg[i] = ranges[i].begin;
+    end[i] = ranges[i].end;
+  }
+  uint64_t nkeys = 0;
+  DFH_CALL(dfh_bcd_build(obj_, static_cast<float>(updater_param_.tail_feature_filter), static_cast<int>(ranges.size()), beg.data(),
+                         end.data(), updater_param_.l1, updater_param_.lr, &nkeys));
+
+  // iterate over data: the block order is std::random_shuffle on the process-wide rand() stream (bcd_learner.cc:79)
+  std::vector<int> feablks(ranges.size());
+  for (size_t i = 0; i < feablks.size(); ++i) feablks[i] = static_cast<int>(i);
+  for (int epoch = 0; epoch < param_.max_num_epochs; ++epoch) {
+    {
+      std::lock_guard<std::mutex> lk(*RefRand::GlobalLock());
+      RefRand::Global()->Shuffle(&feablks);
+    }
+    std::vector<real_t> progress(4, 0);
+    CHECK(feablks.size()) << "no feature block";
+    DFH_CALL(dfh_bcd_epoch(obj_, feablks.data(), static_cast<int>(feablks.size()), progress.data()));
+    for (const auto& cb : epoch_end_callback_) cb(epoch, progress);
+    const real_t cnt = progress[0];
+    LL << "epoch: " << epoch << ", objv: " << progress[1] / cnt << ", auc: " << progress[2] / cnt
+       << ", acc: " << progress[3] / cnt;
+  }
+  if (param_.model_out.size()) SaveModel();
+}
+
+// the final w as learner = sgd's model file without optimiser state (dfh_table_save, save_aux = 0)
+void BCDLearner::SaveModel() {
+  uint64_t nkeys = 0;
+  DFH_CALL(dfh_bcd_shape(obj_, &nkeys, nullptr, nullptr, nullptr));
+  std::vector<uint64_t> keys(std::max<uint64_t>(nkeys, 1));
+  std::vector<float> cnt(keys.size()), w(keys.size());
+  DFH_CALL(dfh_bcd_get_model(obj_, keys.data(), cnt.data(), w.data(), nullptr, nullptr));
+  std::vector<float> scal(4 * keys.size(), 0.f);
+  std::vector<int> has(keys.size(), 0);
+  for (size_t i = 0; i < nkeys; ++i) {
+    scal[4 * i] = cnt[i];   // {fea_cnt, w, sqrt_g, z}
+    scal[4 * i + 1] = w[i];
+  }
+  dfh_updater_param up;
+  dfh_updater_param_default(&up, 0);
+  dfh_table* t = nullptr;
+  DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
+  DFH_CALL(dfh_table_import(t, nkeys, keys.data(), scal.data(), has.data(), nullptr));
+  uint64_t saved = 0;
+  DFH_CALL(dfh_table_save(t, param_.model_out.c_str(), 0, &saved));
+  DFH_CALL(dfh_table_destroy(t));
+  LOG(INFO) << "model saved to " << param_.model_out;
+}
+
+}  // namespace difacto

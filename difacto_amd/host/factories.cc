@@ -3,6 +3,7 @@
  * (reference: src/loss/loss.cc:13-26, src/store/store.cc:8-15,
  * src/tracker/tracker.cc:8-15, src/learner.cc:15-35).
  */
+#include "./bcd_learner.h"
 #include "./device_store.h"
 #include "./hip_fm_loss.h"
 #include "./lbfgs_learner.h"
@@ -43,7 +44,8 @@ Tracker* Tracker::Create() { return new LocalTracker(); }
 Learner* Learner::Create(const std::string& type) {
   if (type == "sgd") return new SGDLearner();
   if (type == "lbfgs") return new LBFGSLearner();
-  LOG(FATAL) << "learner type " << type << " is not part of this build (sgd and lbfgs)";
+  if (type == "bcd") return new BCDLearner();
+  LOG(FATAL) << "learner type " << type << " is not part of this build (sgd, lbfgs and bcd)";
   return nullptr;
 }
 

@@ -547,6 +547,38 @@ int dfh_lbfgs_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, f
 /* Evaluate: validation AUC x n (NULL: skipped), nnz(w), r(w) */
 int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w);
 
+/* ------------------------------------------------ block coordinate descent (learner = bcd) */
+/* The learner's state, resident in HBM from load to finish: the localized training and validation chunks (one dfh_batch
+ * each) with their per-block layouts (a column-major slice for the gradient, a row-major slice for the prediction), the
+ * predictions of every chunk and the model (keys ascending, w, delta, delta w).  Logistic loss, diagonal Newton steps
+ * with l1 (src/bcd/).  One process, one GPU.  Data or state that does not fit in HBM fails with DFH_ERR_CAPACITY and the
+ * bytes needed. */
+typedef struct dfh_bcd dfh_bcd;
+int dfh_bcd_create(dfh_ctx* ctx, dfh_bcd** out);
+int dfh_bcd_destroy(dfh_bcd* o);
+/* a chunk of raw rows (Reader::Value()), localized on the device with Localizer(-1) (TileBuilder::Add) and kept */
+int dfh_bcd_add_chunk(dfh_bcd* o, int is_val, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,
+                      const float* label);
+/* BuildFeatureMap (bcd_learner.cc:118-169): merged training counts, keys with cnt > tail_feature_filter survive, w = 0,
+ * delta = 1; nblk key ranges [blk_begin, blk_end) (ReverseBytes keys, sorted, disjoint: PartitionFeature) cut the keys
+ * into blocks; every chunk's layouts are built on the device.  l1, lr: BCDUpdaterParam. */
+int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_t* blk_begin, const uint64_t* blk_end, float l1,
+                  float lr, uint64_t* nkeys);
+int dfh_bcd_shape(dfh_bcd* o, uint64_t* nkeys, int* nblk, int* ntrain_chunks, int* nval_chunks);
+/* block blk: its model positions [pos_begin, pos_end), its training entries and its touched rows (any pointer NULL) */
+int dfh_bcd_block_info(dfh_bcd* o, int blk, int* pos_begin, int* pos_end, uint64_t* nnz, uint64_t* rows);
+/* one epoch (IterateData, bcd_learner.cc:171-194): the blocks order[0 .. n-1] in turn, each gradient -> update -> the
+ * predictions of every chunk, queued back to back; progress[4] = {count, LogitObjv, AUC x n, Accuracy(.5)} summed over
+ * the training and validation chunks after the last block.  Synchronises once. */
+int dfh_bcd_epoch(dfh_bcd* o, const int* order, int n, float* progress);
+/* one block, synchronised: g, h (NULL: not returned) = the block's summed gradient and diagonal Hessian [pos_end -
+ * pos_begin] in fp64 before the update; progress as dfh_bcd_epoch (NULL: not computed) */
+int dfh_bcd_step(dfh_bcd* o, int blk, double* g, double* h, float* progress);
+/* the model (any pointer may be NULL): keys [nkeys], merged counts, w, delta, the last delta w */
+int dfh_bcd_get_model(dfh_bcd* o, uint64_t* keys, float* feacnt, float* w, float* delta, float* dw);
+/* the predictions of a chunk (pred NULL: only *nrows) */
+int dfh_bcd_get_pred(dfh_bcd* o, int is_val, int chunk, float* pred, size_t* nrows);
+
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
 int dfh_free(dfh_ctx* ctx, void* dptr);

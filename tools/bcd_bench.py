@@ -1,0 +1,121 @@
+"""learner = bcd on a Criteo-shaped synthetic (difacto_amd/synth.py), data, predictions and model resident in HBM.
+
+Prints one JSON line (and writes it to --out): ms per epoch (every block: gradient over the training chunks, update,
+prediction update; the progress after the last), the layout sizes and the bytes an epoch moves under this byte model:
+  column-major slices  s_gk + s_row (+ s_val) per training entry, plus the pred and label gathers (8 B per entry)
+  row-major slices     r_key (+ r_val) per entry and the dw gather (4 B per entry), 8 B of record and a pred read and
+                       write (8 B) per touched row
+  block state          g and h (16 B) and w, delta, dw read and written (24 B) per key
+With --stats FILE (rocprofv3 --kernel-trace --stats output of this tool's run): per-kernel times and the gradient pass's
+achieved TB/s (its bytes over k_bcd_grad + k_bcd_fixup time) against 5 TB/s.
+
+  python tools/bcd_bench.py [--rows 4000000] [--chunk-rows 1000000] [--block-ratio 1] [--epochs 3] [--out FILE]
+  rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/bcd_bench.py ...
+  python tools/bcd_bench.py --stats DIR/.../run_kernel_stats.csv --model FILE
+"""
+import argparse
+import csv
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def kernel_stats(path, model):
+    tot = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = row["Name"].split("(")[0].split("<")[0].split("::")[-1]
+            if name.startswith("k_bcd") or name.startswith("k_auc"):
+                tot[name] = tot.get(name, 0.0) + float(row["TotalDurationNs"])
+    out = dict(kernel_total_ms={k: round(v / 1e6, 3) for k, v in sorted(tot.items())})
+    if model:
+        m = json.load(open(model))
+        ep = m["epochs_timed"] + 1   # the warm-up epoch runs under the tracer too
+        g = (tot.get("k_bcd_grad", 0) + tot.get("k_bcd_fixup", 0)) / ep
+        p = tot.get("k_bcd_pred", 0) / ep
+        out.update(grad_ms_per_epoch=g / 1e6, pred_ms_per_epoch=p / 1e6,
+                   grad_TBps=m["bytes_grad"] / g / 1e3 if g else None, pred_TBps=m["bytes_pred"] / p / 1e3 if p else None,
+                   target_TBps=5.0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=4_000_000)
+    ap.add_argument("--chunk-rows", type=int, default=1_000_000)
+    ap.add_argument("--ids", type=int, default=33_000_000)
+    ap.add_argument("--block-ratio", type=float, default=1.0)
+    ap.add_argument("--tail-feature-filter", type=int, default=4)
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--out")
+    ap.add_argument("--stats")
+    ap.add_argument("--model")
+    args = ap.parse_args()
+    if args.stats:
+        r = kernel_stats(args.stats, args.model)
+        print(json.dumps(r))
+        if args.out:
+            open(args.out, "w").write(json.dumps(r) + "\n")
+        return
+    import bcd_ref as R
+    from difacto_amd import capi
+    from difacto_amd.synth import CriteoSynth
+    ctx = capi.Context(0)
+    res = dict(workload="Criteo-shaped synthetic: %d rows x 39 slots, %d ids, no values, chunks of %d rows, block_ratio %g, "
+               "tail_feature_filter %d" % (args.rows, args.ids, args.chunk_rows, args.block_ratio, args.tail_feature_filter))
+    obj = capi.Bcd(ctx)
+    gen = CriteoSynth(total_ids=args.ids, seed=7)
+    t0 = time.perf_counter()
+    nnz, sampled, entries = 0, 0, 0
+    for r0 in range(0, args.rows, args.chunk_rows):
+        b = gen.batch(min(args.chunk_rows, args.rows - r0))
+        n = len(b["label"])
+        obj.add_chunk(b["offset"], b["index"], None, b["label"])
+        nnz += len(b["index"])
+        s = len(range(0, n, 10))   # FeaGroupStats: every 10th row of a chunk, 39 entries each
+        sampled += s
+        entries += 39 * s
+    res["load_s"] = time.perf_counter() - t0
+    st = np.array([entries, sampled, args.rows], np.float32)
+    ranges = R.partition_feature(0, R.block_counts(st, args.block_ratio))
+    t0 = time.perf_counter()
+    nkeys = obj.build(ranges, tail_feature_filter=args.tail_feature_filter, l1=1.0, lr=0.9)
+    res["build_s"] = time.perf_counter() - t0
+    info = [obj.block_info(b) for b in range(len(ranges))]
+    touched = sum(i[3] for i in info)
+    tr_nnz = sum(i[2] for i in info)
+    res.update(nkeys=nkeys, nnz=nnz, nblk=len(ranges), block_nnz_max=max(i[2] for i in info), touched_rows=touched)
+    res["bytes_grad"] = tr_nnz * (4 + 4 + 8)
+    res["bytes_pred"] = tr_nnz * (4 + 4) + touched * (8 + 8)
+    res["bytes_state"] = nkeys * (16 + 24)
+    res["bytes_per_epoch"] = res["bytes_grad"] + res["bytes_pred"] + res["bytes_state"]
+    stream = R.RefRand()
+    order = list(range(len(ranges)))
+    stream.shuffle(order)
+    obj.epoch(order)   # warm
+    times, progs = [], []
+    for _ in range(args.epochs):
+        stream.shuffle(order)
+        t = time.perf_counter()
+        p = obj.epoch(order)
+        times.append(time.perf_counter() - t)
+        progs.append([float(x) for x in p])
+    res.update(epochs_timed=args.epochs, ms_per_epoch=[1e3 * t for t in times], ms_per_epoch_best=1e3 * min(times),
+               TBps_epoch=res["bytes_per_epoch"] / min(times) / 1e12, objv_per_row=[p[1] / p[0] for p in progs])
+    obj.close()
+    ctx.close()
+    print(json.dumps(res))
+    if args.out:
+        open(args.out, "w").write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()
