@@ -35,7 +35,7 @@ SYMBOLS = [
     "dfh_batch_create_many", "dfh_shard_multi_words", "dfh_shard_reserve", "dfh_comm_create_loopback", "dfh_comm_loopback_feed", "dfh_comm_loopback_wire", "dfh_comm_loopback_wire_time",
     "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
-    "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate",
+    "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate", "dfh_lbfgs_create_sharded",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred",
 ]
@@ -214,6 +214,7 @@ def lib():
     L.dfh_vec_combine.argtypes = [vp, u64, i32, vp, vp, f32, vp, vp, dp]
     L.dfh_vec_line_step.argtypes = [vp, u64, vp, vp, f32, vp, f32, f32, dp]
     L.dfh_lbfgs_create.argtypes = [vp, i32, i32, PP(vp)]
+    L.dfh_lbfgs_create_sharded.argtypes = [vp, vp, i32, i32, PP(vp)]
     L.dfh_lbfgs_destroy.argtypes = [vp]
     L.dfh_lbfgs_add_chunk.argtypes = [vp, i32, sz, vp, vp, vp, vp]
     L.dfh_lbfgs_init_model.argtypes = [vp, f32, i32, f32, f32, f32, PP(u64), PP(u64)]
@@ -739,10 +740,15 @@ def vec_line_step(ctx, n, w, p, x, vmask=None, l2=0.0, V_l2=0.0):
 class Lbfgs:
     """the full-batch L-BFGS state resident in HBM (dfh_lbfgs): data chunks, model, gradients, s / y history"""
 
-    def __init__(self, ctx, V_dim, m):
-        self.ctx, self.V_dim, self.m = ctx, V_dim, m
+    def __init__(self, ctx, V_dim, m, comm=None):
+        """comm (a Comm): the sharded object of dfh_lbfgs_create_sharded; every call is then collective and shape / model
+        calls see this rank's slice of the keys"""
+        self.ctx, self.V_dim, self.m, self.comm = ctx, V_dim, m, comm
         self.h = C.c_void_p()
-        _ck(lib().dfh_lbfgs_create(ctx.h, V_dim, m, C.byref(self.h)))
+        if comm is None:
+            _ck(lib().dfh_lbfgs_create(ctx.h, V_dim, m, C.byref(self.h)))
+        else:
+            _ck(lib().dfh_lbfgs_create_sharded(ctx.h, comm.h, V_dim, m, C.byref(self.h)))
 
     def add_chunk(self, offset, index, value, label, is_val=False):
         offset = np.ascontiguousarray(offset, np.uint64)

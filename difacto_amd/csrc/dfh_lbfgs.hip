@@ -379,6 +379,27 @@ __global__ void __launch_bounds__(THREADS) k_lb_gamma(float* __restrict__ g, uin
   }
 }
 
+// The sharded object's exchange around CalcGrad (dfh_lbfgs_create_sharded).  Both index lists are built once, in
+// init_model, and the data never changes.
+// Owner side, before the pull: the ragged rows of the pull list, requester after requester, out of the owned slice
+// of w: send[i] = w[src[i]].  The buffer is contiguous in peer order, the layout of the all-to-all-v's send side.
+__global__ void __launch_bounds__(THREADS) k_lb_pack(const float* __restrict__ w, const uint32_t* __restrict__ src, uint64_t cnt,
+                                                     float* __restrict__ send) {
+  for (uint64_t i = (uint64_t)blockIdx.x * THREADS + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * THREADS) send[i] = w[src[i]];
+}
+
+// Owner side, after the push: the gradient rows come back in the layout the pack wrote, so the contributions to owned
+// element p sit at recv[idx[rptr[p] .. rptr[p+1])], ascending, which is ascending source rank.  g[p] = 0 + each of them
+// in that order, written once: the same bits on every run and over every transport (no atomics).
+__global__ void __launch_bounds__(THREADS) k_lb_reduce(const float* __restrict__ recv, const uint32_t* __restrict__ rptr,
+                                                       const uint32_t* __restrict__ idx, uint64_t n, float* __restrict__ g) {
+  for (uint64_t p = (uint64_t)blockIdx.x * THREADS + threadIdx.x; p < n; p += (uint64_t)gridDim.x * THREADS) {
+    float s = 0.f;
+    for (uint32_t e = rptr[p], e1 = rptr[p + 1]; e < e1; ++e) s += recv[idx[e]];
+    g[p] = s;
+  }
+}
+
 // a chunk's loss (the forward's per-block partials, in slot order per thread, then a fixed tree) and AUC x n into
 // out[0..1]; the slots are cleared for the next chunk by the caller
 __global__ void __launch_bounds__(THREADS) k_lb_take_prog(const double* __restrict__ prog, double* __restrict__ out) {
@@ -495,6 +516,23 @@ struct dfh_lbfgs {
   double* d_part = nullptr;        // block partials
   double* d_res = nullptr;         // small results: [0, 2 x chunks) per-chunk {loss, AUC x n}, then reduction outputs
   size_t res_cap = 0;
+  // the model the chunks read and the gradient they write: d_w / d_pos / d_gnew, or on a sharded object the rank's
+  // local ragged model (every key of its chunks that survived, ascending) and its local gradient
+  float* d_mw = nullptr;
+  int64_t* d_mpos = nullptr;
+  float* d_mg = nullptr;
+  uint64_t nm = 0;
+  // ---- sharded (dfh_lbfgs_create_sharded): a worker for its own chunks, the owner of one slice of the ascending keys
+  dfh_comm* comm = nullptr;
+  void* sh_arena = nullptr;        // the buffers below, one allocation
+  float *d_lw = nullptr, *d_lg = nullptr;   // local ragged model (the pull's receive buffer) and gradient (the push's send buffer)
+  int64_t* d_lpos = nullptr;       // [local keys + 1]
+  float* d_xbuf = nullptr;         // [nx]: the pack's output (pull send) and the push's receive buffer, same layout
+  uint32_t* d_src = nullptr;       // [nx] owned element of every float of the pull list
+  uint32_t *d_rptr = nullptr, *d_ridx = nullptr;   // [n + 1], [nx]: the inverted list, ascending source rank per element
+  uint64_t nx = 0;
+  std::vector<size_t> own_b, loc_b;   // bytes per peer: owner side (pull send = push receive), worker side (the reverse)
+  bool pulled = false;             // d_lw holds the current w
 };
 
 namespace {
@@ -531,7 +569,7 @@ int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
   const lb::RowLanes rl{U, st, shift};
   const uint64_t waves = ((uint64_t)U + (64u >> shift) - 1) / (64u >> shift);
   const int gb = (int)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, 8192));
-  if (U) hipLaunchKernelGGL(lb::k_lb_gather, dim3(gb), dim3(lb::THREADS), 0, s, o->d_w, o->d_pos, ch.d_map, rl, o->d_rows);
+  if (U) hipLaunchKernelGGL(lb::k_lb_gather, dim3(gb), dim3(lb::THREADS), 0, s, o->d_mw, o->d_mpos, ch.d_map, rl, o->d_rows);
   DFH_HIP(hipGetLastError());
   int rc = dfh_batch_forward(ch.b, o->V_dim, o->d_rows);
   if (rc) return rc;
@@ -540,7 +578,7 @@ int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
   if (grad && U) {
     rc = dfh_batch_backward(ch.b, o->V_dim, o->d_rows, o->d_grows);
     if (rc) return rc;
-    hipLaunchKernelGGL(lb::k_lb_scatter, dim3(gb), dim3(lb::THREADS), 0, s, o->d_grows, o->d_pos, ch.d_map, rl, o->d_gnew);
+    hipLaunchKernelGGL(lb::k_lb_scatter, dim3(gb), dim3(lb::THREADS), 0, s, o->d_grows, o->d_mpos, ch.d_map, rl, o->d_mg);
   }
   hipLaunchKernelGGL(lb::k_lb_take_prog, dim3(1), dim3(lb::THREADS), 0, s, ch.b->d_prog, res);
   DFH_HIP(hipGetLastError());
@@ -549,15 +587,61 @@ int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
   return DFH_OK;
 }
 
+// the sums over ranks of a sharded object's fp64 partials, in rank order (the same bits on every rank); a no-op on a
+// plain object.  dfh_comm_allreduce_sum takes 64 values per call.
+int lb_allsum(dfh_lbfgs* o, double* v, size_t n) {
+  if (!o->comm) return DFH_OK;
+  for (size_t i = 0; i < n; i += 64) {
+    const int rc = dfh_comm_allreduce_sum(o->comm, v + i, (int)std::min<size_t>(64, n - i));
+    if (rc) return rc;
+  }
+  return DFH_OK;
+}
+
+// sharded: the owners' rows of w to the workers that use them.  The receive buffer is the worker's local ragged model.
+int lb_pull(dfh_lbfgs* o) {
+  hipStream_t s = o->ctx->stream;
+  if (o->nx) {
+    hipLaunchKernelGGL(lb::k_lb_pack, dim3(lb::blocks_for(o->nx, 1)), dim3(lb::THREADS), 0, s, o->d_w, o->d_src, o->nx, o->d_xbuf);
+    DFH_HIP(hipGetLastError());
+  }
+  const int rc = comm_alltoallv(o->comm, o->d_xbuf, o->own_b.data(), o->d_lw, o->loc_b.data(), nullptr, DFH_XCHG_ROWS);
+  if (rc) return rc;
+  o->pulled = true;
+  return DFH_OK;
+}
+
+// sharded: the local gradient back to the owners (it is ordered by owner already), then each owned element's
+// contributions added in ascending source rank into g_new
+int lb_push_reduce(dfh_lbfgs* o) {
+  hipStream_t s = o->ctx->stream;
+  const int rc = comm_alltoallv(o->comm, o->d_lg, o->loc_b.data(), o->d_xbuf, o->own_b.data(), nullptr, DFH_XCHG_GRADS);
+  if (rc) return rc;
+  if (o->n) {
+    hipLaunchKernelGGL(lb::k_lb_reduce, dim3(lb::blocks_for(o->n, 1)), dim3(lb::THREADS), 0, s, o->d_xbuf, o->d_rptr, o->d_ridx,
+                       (uint64_t)o->n, o->d_gnew);
+    DFH_HIP(hipGetLastError());
+  }
+  return DFH_OK;
+}
+
 // LBFGSLearner::CalcGrad (lbfgs_learner.cc:246-305) into g_new; loss and AUC x n summed over the chunks as the reference
-// sums them (each chunk's value as a float, in chunk order)
+// sums them (each chunk's value as a float, in chunk order), on a sharded object then over the ranks in fp64
 int lb_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n) {
   auto& tr = o->chunks[0];
   hipStream_t s = o->ctx->stream;
   int rc = DFH_OK;
-  DFH_HIP(hipMemsetAsync(o->d_gnew, 0, o->n * sizeof(float), s));
+  if (o->comm) {
+    rc = lb_pull(o);
+    if (rc) return rc;
+  }
+  if (o->nm) DFH_HIP(hipMemsetAsync(o->d_mg, 0, o->nm * sizeof(float), s));
   for (size_t i = 0; i < tr.size(); ++i) {
     rc = lb_chunk_pass(o, tr[i], true, o->d_res + 2 * i);
+    if (rc) return rc;
+  }
+  if (o->comm) {
+    rc = lb_push_reduce(o);
     if (rc) return rc;
   }
   if (gamma != 1.f) {
@@ -572,6 +656,13 @@ int lb_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n) {
     l += (float)r[2 * i];
     a += (float)r[2 * i + 1];
   }
+  if (o->comm) {
+    double t[2] = {l, a};
+    rc = lb_allsum(o, t, 2);
+    if (rc) return rc;
+    l = (float)t[0];
+    a = (float)t[1];
+  }
   if (loss) *loss = l;
   if (auc_n) *auc_n = a;
   return DFH_OK;
@@ -584,6 +675,9 @@ int lb_wstep(dfh_lbfgs* o, const float* p, float x, double out[3]) {
   if (rc) return rc;
   std::vector<double> r;
   rc = lb_fetch(o, res, 3, &r);
+  if (rc) return rc;
+  if (p && x != 0.f) o->pulled = false;
+  rc = lb_allsum(o, r.data(), 3);
   if (rc) return rc;
   for (int i = 0; i < 3; ++i) out[i] = r[i];
   return DFH_OK;
@@ -602,6 +696,7 @@ int lb_free(dfh_lbfgs* o) {
   if (o->d_grows) (void)hipFree(o->d_grows);
   if (o->d_part) (void)hipFree(o->d_part);
   if (o->d_res) (void)hipFree(o->d_res);
+  if (o->sh_arena) (void)hipFree(o->sh_arena);
   delete o;
   return DFH_OK;
 }
@@ -761,12 +856,169 @@ int dfh_lbfgs_add_chunk(dfh_lbfgs* o, int is_val, size_t nrows, const size_t* of
   return DFH_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// an all-to-all-v of host bytes over the communicator, staged through device buffers; synchronous (set-up only)
+int lb_xchg_host(dfh_lbfgs* o, const void* send, const std::vector<size_t>& sb, void* recv, const std::vector<size_t>& rb) {
+  size_t st = 0, rt = 0;
+  for (size_t x : sb) st += x;
+  for (size_t x : rb) rt += x;
+  hipStream_t s = o->ctx->stream;
+  char *d_s = nullptr, *d_r = nullptr;
+  DFH_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), std::max<size_t>(st, 16)));
+  if (hipMalloc(reinterpret_cast<void**>(&d_r), std::max<size_t>(rt, 16)) != hipSuccess) {
+    (void)hipFree(d_s);
+    set_error("dfh_lbfgs_init_model: no device memory for the set-up exchange");
+    return DFH_ERR_HIP;
+  }
+  int rc = DFH_OK;
+  if (st && hipMemcpyAsync(d_s, send, st, hipMemcpyHostToDevice, s) != hipSuccess) rc = DFH_ERR_HIP;
+  if (!rc) rc = comm_alltoallv(o->comm, d_s, sb.data(), d_r, rb.data());
+  if (!rc && rt && hipMemcpyAsync(recv, d_r, rt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = DFH_ERR_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = DFH_ERR_HIP;
+  (void)hipFree(d_s);
+  (void)hipFree(d_r);
+  if (rc == DFH_ERR_HIP) set_error("dfh_lbfgs_init_model: the set-up exchange failed");
+  return rc;
+}
+
+// what a worker asks a key's owner: the key, this rank's merged training count, whether its training chunks hold it
+// (a key of the validation chunks alone is asked for its row and never enters the model)
+struct LbReq {
+  uint64_t key;
+  float cnt;
+  uint32_t train;
+};
+
+// Set-up of a sharded object.  Split keys balanced on the ranks' training keys; every rank's requests to the owners;
+// the owner adds the counts over ranks (in rank order), filters on the global counts and builds its slice (keys,
+// cnts, lens); it answers every request with the key's lens, 0 when the key is not in the model.  Out: the worker's
+// local model (its surviving keys ascending, grouped by owner, and their lens), the pull list (src: the owned
+// element of every float the owner sends, requester after requester) and the bytes per peer of both sides.
+int lb_shard_model(dfh_lbfgs* o, float filter, int V_threshold, const std::vector<uint64_t>& tk, const std::vector<float>& tc,
+                   std::vector<uint64_t>* lkeys, std::vector<int>* llens, std::vector<uint32_t>* src) {
+  const int W = o->comm->world, k = o->V_dim;
+  std::vector<uint64_t> vk;
+  for (auto& ch : o->chunks[1]) vk.insert(vk.end(), ch.keys.begin(), ch.keys.end());
+  std::sort(vk.begin(), vk.end());
+  vk.erase(std::unique(vk.begin(), vk.end()), vk.end());
+  std::vector<LbReq> req;
+  req.reserve(tk.size() + vk.size());
+  for (size_t i = 0, j = 0; i < tk.size() || j < vk.size();) {
+    if (j < vk.size() && (i == tk.size() || vk[j] < tk[i])) {
+      req.push_back(LbReq{vk[j++], 0.f, 0u});
+    } else {
+      if (j < vk.size() && vk[j] == tk[i]) ++j;
+      req.push_back(LbReq{tk[i], tc[i], 1u});
+      ++i;
+    }
+  }
+  std::vector<uint64_t> splits(std::max(W - 1, 1), 0);
+  int rc = dfh_shard_balanced_splits(o->comm, tk.data(), tk.size(), splits.data());
+  if (rc) return rc;
+  // the owner of a key: the number of split keys at or below it
+  std::vector<int> owner(req.size());
+  std::vector<uint64_t> nreq(W, 0), nrecv(W, 0);
+  for (size_t i = 0; i < req.size(); ++i) {
+    owner[i] = (int)(std::upper_bound(splits.begin(), splits.begin() + (W - 1), req[i].key) - splits.begin());
+    ++nreq[owner[i]];
+  }
+  rc = lb_xchg_host(o, nreq.data(), std::vector<size_t>(W, 8), nrecv.data(), std::vector<size_t>(W, 8));
+  if (rc) return rc;
+  std::vector<size_t> sb(W), rb(W), seg(W + 1, 0);
+  for (int p = 0; p < W; ++p) {
+    sb[p] = nreq[p] * sizeof(LbReq);
+    rb[p] = nrecv[p] * sizeof(LbReq);
+    seg[p + 1] = seg[p] + nrecv[p];
+  }
+  std::vector<LbReq> got(seg[W]);
+  rc = lb_xchg_host(o, req.data(), sb, got.data(), rb);
+  if (rc) return rc;
+  // owner: every source's list is ascending and the sources lie in rank order; a stable sort by key keeps that order
+  std::vector<uint32_t> ord(got.size());
+  for (size_t i = 0; i < ord.size(); ++i) ord[i] = (uint32_t)i;
+  std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return got[a].key < got[b].key; });
+  for (size_t i = 0; i < ord.size();) {
+    size_t j = i;
+    float cnt = 0;
+    bool train = false;
+    for (; j < ord.size() && got[ord[j]].key == got[ord[i]].key; ++j) {
+      cnt += got[ord[j]].cnt;
+      train = train || got[ord[j]].train;
+    }
+    // RemoveTailFeatures on the global count (lbfgs_utils.h:100-116)
+    if (train && (!(filter > 0) || cnt > filter)) {
+      o->keys.push_back(got[ord[i]].key);
+      o->cnts.push_back(cnt);
+    }
+    i = j;
+  }
+  const size_t K = o->keys.size();
+  o->lens.assign(K, 1);
+  std::vector<uint64_t> pos(K + 1, 0);
+  for (size_t i = 0; i < K; ++i) {
+    if (k) o->lens[i] = 1 + (o->cnts[i] > V_threshold ? k : 0);
+    pos[i + 1] = pos[i] + o->lens[i];
+  }
+  // the answers, and the pull list in the requesters' order
+  std::vector<int32_t> reply(got.size(), 0), ans(req.size(), 0);
+  o->own_b.assign(W, 0);
+  for (int q = 0; q < W; ++q) {
+    size_t j = 0;
+    for (size_t e = seg[q]; e < seg[q + 1]; ++e) {
+      while (j < K && o->keys[j] < got[e].key) ++j;
+      if (j < K && o->keys[j] == got[e].key) {
+        reply[e] = o->lens[j];
+        for (int c = 0; c < o->lens[j]; ++c) src->push_back((uint32_t)(pos[j] + c));
+        o->own_b[q] += (size_t)o->lens[j] * sizeof(float);
+      }
+    }
+  }
+  if (pos[K] >= (1ull << 32) || src->size() >= (1ull << 32)) {
+    set_error("dfh_lbfgs_init_model: a shard of more than 2^32 - 1 floats or pull entries is not supported");
+    return DFH_ERR_CAPACITY;
+  }
+  for (int p = 0; p < W; ++p) {
+    sb[p] = nrecv[p] * sizeof(int32_t);
+    rb[p] = nreq[p] * sizeof(int32_t);
+  }
+  rc = lb_xchg_host(o, reply.data(), sb, ans.data(), rb);
+  if (rc) return rc;
+  // worker: its local model, the surviving keys in ascending order (grouped by owner: the owners' slices ascend)
+  o->loc_b.assign(W, 0);
+  for (size_t i = 0; i < req.size(); ++i) {
+    if (ans[i] <= 0) continue;
+    lkeys->push_back(req[i].key);
+    llens->push_back(ans[i]);
+    o->loc_b[owner[i]] += (size_t)ans[i] * sizeof(float);
+  }
+  return DFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfh_lbfgs_create_sharded(dfh_ctx* c, dfh_comm* comm, int V_dim, int m, dfh_lbfgs** out) {
+  DFH_ARG(c && comm && out && comm->ctx == c, "dfh_lbfgs_create_sharded: the context and the communicator must match");
+  DFH_ARG(!comm->loopback, "dfh_lbfgs_create_sharded: the loop-back transport is for dfh_shard_step measurements only");
+  const int rc = dfh_lbfgs_create(c, V_dim, m, out);
+  if (rc) return rc;
+  (*out)->comm = comm;
+  return DFH_OK;
+}
+
 int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshold, float V_init_scale, float l2, float V_l2,
                          uint64_t* nkeys, uint64_t* nparams) {
   DFH_ARG(o && !o->inited, "dfh_lbfgs_init_model: bad argument or called twice");
-  DFH_ARG(!o->chunks[0].empty(), "dfh_lbfgs_init_model: no training chunk");
+  DFH_ARG(o->comm || !o->chunks[0].empty(), "dfh_lbfgs_init_model: no training chunk");
   DFH_HIP(hipSetDevice(o->ctx->device));
+  const int k = o->V_dim;
   // merged feature counts (KVUnion of every chunk's counts in chunk order, tile_builder.h:171-176)
+  std::vector<uint64_t> tk;
+  std::vector<float> tc;
   {
     size_t tot = 0;
     for (auto& ch : o->chunks[0]) tot += ch.U;
@@ -781,36 +1033,64 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
       size_t j = i;
       float cnt = 0;
       for (; j < kc.size() && kc[j].first == kc[i].first; ++j) cnt += kc[j].second;
-      // RemoveTailFeatures (lbfgs_utils.h:100-116): a key survives with cnt > filter
-      if (!(tail_feature_filter > 0) || cnt > tail_feature_filter) {
-        o->keys.push_back(kc[i].first);
-        o->cnts.push_back(cnt);
-      }
+      tk.push_back(kc[i].first);
+      tc.push_back(cnt);
       i = j;
     }
   }
-  const size_t K = o->keys.size();
-  const int k = o->V_dim;
-  o->lens.assign(K, 1);
-  std::vector<int64_t> pos(K + 1, 0);
-  for (size_t i = 0; i < K; ++i) {
-    if (k) o->lens[i] = 1 + (o->cnts[i] > V_threshold ? k : 0);   // InitWeight, lbfgs_updater.h:47-52
-    pos[i + 1] = pos[i] + o->lens[i];
+  std::vector<uint64_t> lkeys;   // sharded: the worker's local model
+  std::vector<int> llens;
+  std::vector<uint32_t> src;
+  if (o->comm) {
+    const int rc = lb_shard_model(o, tail_feature_filter, V_threshold, tk, tc, &lkeys, &llens, &src);
+    if (rc) return rc;
+  } else {
+    for (size_t i = 0; i < tk.size(); ++i) {
+      // RemoveTailFeatures (lbfgs_utils.h:100-116): a key survives with cnt > filter
+      if (!(tail_feature_filter > 0) || tc[i] > tail_feature_filter) {
+        o->keys.push_back(tk[i]);
+        o->cnts.push_back(tc[i]);
+      }
+    }
+    o->lens.assign(o->keys.size(), 1);
+    if (k)
+      for (size_t i = 0; i < o->keys.size(); ++i) o->lens[i] = 1 + (o->cnts[i] > V_threshold ? k : 0);   // InitWeight, lbfgs_updater.h:47-52
   }
+  const size_t K = o->keys.size();
+  std::vector<int64_t> pos(K + 1, 0);
+  for (size_t i = 0; i < K; ++i) pos[i + 1] = pos[i] + o->lens[i];
   o->n = (uint64_t)pos[K];
   o->l2 = l2;
   o->V_l2 = V_l2;
   const uint64_t n = o->n;
+  // the rand_r chain runs over the keys of every shard in order: this shard starts behind the draws of shards 0 .. r-1
+  uint64_t skip = 0;
+  if (o->comm && k) {
+    const int W = o->comm->world;
+    const uint64_t mine = n - K;
+    std::vector<uint64_t> draws(W, 0);
+    const int rc = dfh_comm_allgather(o->comm, &mine, sizeof(mine), draws.data());
+    if (rc) return rc;
+    for (int q = 0; q < o->comm->rank; ++q) skip += draws[q];
+  }
   // every model-sized vector in one allocation: w, g_new, g, m s slots, m y slots (each padded to 64 floats), pos, V mask
   const size_t vec = ((n + 63) / 64) * 64 * sizeof(float);
   const size_t mask_words = k ? (n + 31) / 32 + 1 : 0;
   const size_t arena = (size_t)(3 + 2 * o->m) * vec + ((K + 1) * sizeof(int64_t) + 255) / 256 * 256 + mask_words * 4 + 256;
   const size_t rows = std::max<size_t>(o->max_U, 1) * o->stride * sizeof(float);
   const size_t part = lb::part_bytes(lb::NA * lb::NB);
+  // sharded: local model and gradient, local pos, the exchange buffer, the pull list and the inverted list
+  uint64_t nl = 0;
+  for (int l : llens) nl += (uint64_t)l;
+  const uint64_t nx = src.size();
+  auto pad = [](size_t b) { return (std::max<size_t>(b, 1) + 255) / 256 * 256; };
+  const size_t sh_arena = o->comm ? 2 * pad(nl * sizeof(float)) + pad((lkeys.size() + 1) * sizeof(int64_t)) +
+                                        3 * pad(nx * sizeof(uint32_t)) + pad((n + 1) * sizeof(uint32_t))
+                                  : 0;
   size_t free_b = 0, total_b = 0;
   DFH_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (arena + 2 * rows + part > free_b) {
-    set_error(lb_bytes_msg("the model and the optimiser state", arena + 2 * rows + part, free_b));
+  if (arena + 2 * rows + part + sh_arena > free_b) {
+    set_error(lb_bytes_msg("the model and the optimiser state", arena + 2 * rows + part + sh_arena, free_b));
     return DFH_ERR_CAPACITY;
   }
   DFH_HIP(hipMalloc(&o->arena, arena));
@@ -839,6 +1119,7 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   std::vector<uint32_t> mask(mask_words, 0u);
   if (k) {
     unsigned seed = 0;
+    for (uint64_t d = 0; d < skip; ++d) (void)rand_r(&seed);
     const float scale = V_init_scale * 2;
     for (size_t i = 0; i < K; ++i) {
       for (int j = 1; j < o->lens[i]; ++j) {
@@ -852,14 +1133,57 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   if (n) DFH_HIP(hipMemcpyAsync(o->d_w, w.data(), n * sizeof(float), hipMemcpyHostToDevice, s));
   DFH_HIP(hipMemcpyAsync(o->d_pos, pos.data(), (K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   if (k) DFH_HIP(hipMemcpyAsync(o->d_vmask, mask.data(), mask_words * 4, hipMemcpyHostToDevice, s));
-  // each chunk's key -> model key map (TileBuilder::BuildColmap, tile_builder.h:59-76: -1 = not in the model)
+  o->d_mw = o->d_w;
+  o->d_mpos = o->d_pos;
+  o->d_mg = o->d_gnew;
+  o->nm = n;
+  std::vector<int64_t> lpos;
+  std::vector<uint32_t> rptr, ridx;
+  if (o->comm) {
+    DFH_HIP(hipMalloc(&o->sh_arena, sh_arena));
+    p = static_cast<char*>(o->sh_arena);
+    auto take_p = [&](size_t bytes) {
+      char* r = p;
+      p += pad(bytes);
+      return r;
+    };
+    o->d_lw = reinterpret_cast<float*>(take_p(nl * sizeof(float)));
+    o->d_lg = reinterpret_cast<float*>(take_p(nl * sizeof(float)));
+    o->d_lpos = reinterpret_cast<int64_t*>(take_p((lkeys.size() + 1) * sizeof(int64_t)));
+    o->d_xbuf = reinterpret_cast<float*>(take_p(nx * sizeof(float)));
+    o->d_src = reinterpret_cast<uint32_t*>(take_p(nx * sizeof(uint32_t)));
+    o->d_ridx = reinterpret_cast<uint32_t*>(take_p(nx * sizeof(uint32_t)));
+    o->d_rptr = reinterpret_cast<uint32_t*>(take_p((n + 1) * sizeof(uint32_t)));
+    o->nx = nx;
+    lpos.assign(lkeys.size() + 1, 0);
+    for (size_t i = 0; i < lkeys.size(); ++i) lpos[i + 1] = lpos[i] + llens[i];
+    // the inverted list: every owned element's entries of the pull list in ascending order (= ascending source rank)
+    rptr.assign(n + 1, 0);
+    ridx.resize(nx);
+    for (uint32_t e : src) ++rptr[e + 1];
+    for (uint64_t i = 0; i < n; ++i) rptr[i + 1] += rptr[i];
+    std::vector<uint32_t> cur(rptr.begin(), rptr.end() - 1);
+    for (uint64_t i = 0; i < nx; ++i) ridx[cur[src[i]]++] = (uint32_t)i;
+    DFH_HIP(hipMemcpyAsync(o->d_lpos, lpos.data(), lpos.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (nx) DFH_HIP(hipMemcpyAsync(o->d_src, src.data(), nx * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (nx) DFH_HIP(hipMemcpyAsync(o->d_ridx, ridx.data(), nx * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    DFH_HIP(hipMemcpyAsync(o->d_rptr, rptr.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    o->d_mw = o->d_lw;
+    o->d_mpos = o->d_lpos;
+    o->d_mg = o->d_lg;
+    o->nm = nl;
+  }
+  // each chunk's key -> model key map (TileBuilder::BuildColmap, tile_builder.h:59-76: -1 = not in the model); on a
+  // sharded object into the local model
+  const std::vector<uint64_t>& mkeys = o->comm ? lkeys : o->keys;
+  const size_t MK = mkeys.size();
   for (auto& cs : o->chunks)
     for (auto& ch : cs) {
       std::vector<int32_t> map(std::max<size_t>(ch.U, 1), -1);
       size_t j = 0;
       for (size_t u = 0; u < ch.U; ++u) {
-        while (j < K && o->keys[j] < ch.keys[u]) ++j;
-        if (j < K && o->keys[j] == ch.keys[u]) map[u] = (int32_t)j;
+        while (j < MK && mkeys[j] < ch.keys[u]) ++j;
+        if (j < MK && mkeys[j] == ch.keys[u]) map[u] = (int32_t)j;
       }
       DFH_HIP(hipMalloc(&ch.d_map, map.size() * sizeof(int32_t)));
       DFH_HIP(hipMemcpyAsync(ch.d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -895,8 +1219,9 @@ int dfh_lbfgs_get_model(dfh_lbfgs* o, uint64_t* keys, int* lens, float* feacnt, 
 }
 
 int dfh_lbfgs_set_weights(dfh_lbfgs* o, const float* w) {
-  DFH_ARG(o && o->inited && w, "dfh_lbfgs_set_weights: bad argument");
+  DFH_ARG(o && o->inited && (w || !o->n), "dfh_lbfgs_set_weights: bad argument");
   DFH_ARG(!o->have_g, "dfh_lbfgs_set_weights: training has started");
+  o->pulled = false;
   if (!o->n) return DFH_OK;
   DFH_HIP(hipSetDevice(o->ctx->device));
   DFH_HIP(hipMemcpyAsync(o->d_w, w, o->n * sizeof(float), hipMemcpyHostToDevice, o->ctx->stream));
@@ -954,6 +1279,8 @@ int dfh_lbfgs_prepare_direction(dfh_lbfgs* o, float* incr_B, int* mcur) {
   std::vector<double> h;
   rc = lb_fetch(o, lb_tail(o), rs, &h);
   if (rc) return rc;
+  rc = lb_allsum(o, h.data(), rs);
+  if (rc) return rc;
   // Twoloop::CalcIncreB's layout (lbfgs_twoloop.h:25-37)
   const int nb = ia.nb;
   for (int i = 0; i < k; ++i) {
@@ -1006,6 +1333,8 @@ int dfh_lbfgs_calc_direction(dfh_lbfgs* o, const float* d, float* p_g) {
   std::vector<double> h;
   rc = lb_fetch(o, lb_tail(o), 1, &h);
   if (rc) return rc;
+  rc = lb_allsum(o, h.data(), 1);
+  if (rc) return rc;
   *p_g = (float)h[0];
   o->alpha = 0;
   return DFH_OK;
@@ -1030,12 +1359,13 @@ int dfh_lbfgs_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, f
   ia.a[0] = o->d_gnew;
   ia.alias[0] = -1;
   ia.b[0] = p;
-  const size_t rs = lb::inner_res_size(1);
   double* res = lb_tail(o);
   rc = lb::launch_inner(o->ctx->stream, ia, nullptr, nullptr, nullptr, nullptr, o->d_part, res);
   if (rc) return rc;
   std::vector<double> h;
-  rc = lb_fetch(o, res, rs, &h);
+  rc = lb_fetch(o, res, 1, &h);
+  if (rc) return rc;
+  rc = lb_allsum(o, h.data(), 1);
   if (rc) return rc;
   // the worker's then the server's share of the job's status (lbfgs_learner.cc:147-150, 232-243; lbfgs_updater.h:125-133)
   *objv = loss + (float)r[0];
@@ -1053,6 +1383,10 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
   if (r_w) *r_w = (float)r[0];
   if (val_auc_n) {
     auto& va = o->chunks[1];
+    if (o->comm && !o->pulled) {   // the validation chunks read the local model: w has moved since the last pull
+      rc = lb_pull(o);
+      if (rc) return rc;
+    }
     for (size_t i = 0; i < va.size(); ++i) {
       rc = lb_chunk_pass(o, va[i], false, o->d_res + 2 * i);
       if (rc) return rc;
@@ -1062,6 +1396,12 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
     if (rc) return rc;
     float a = 0;
     for (size_t i = 0; i < va.size(); ++i) a += (float)h[2 * i + 1];
+    if (o->comm) {
+      double t = a;
+      rc = lb_allsum(o, &t, 1);
+      if (rc) return rc;
+      a = (float)t;
+    }
     *val_auc_n = a;
   }
   return DFH_OK;

@@ -8,7 +8,9 @@
 #include <memory>
 #include <thread>
 #include "./batch_reader.h"
+#include "./comm_setup.h"
 #include "./device_context.h"
+#include "./model_parts.h"
 
 namespace difacto {
 
@@ -17,6 +19,7 @@ DMLC_REGISTER_PARAMETER(LBFGSUpdaterParam);
 
 LBFGSLearner::~LBFGSLearner() {
   if (obj_) dfh_lbfgs_destroy(obj_);
+  if (comm_) dfh_comm_destroy(comm_);
 }
 
 KWArgs LBFGSLearner::Init(const KWArgs& kwargs) {
@@ -25,7 +28,12 @@ KWArgs LBFGSLearner::Init(const KWArgs& kwargs) {
         << "learner = lbfgs has no prediction task: train with model_out=<file>, then score with "
            "task=predict learner=sgd model_in=<file> V_dim=<V_dim> pred_out=<file>";
   const char* nw = getenv("DMLC_NUM_WORKER");
-  CHECK(!IsDistributed() && !(nw && atoi(nw) > 1))
+  const char* role = getenv("DMLC_ROLE");
+  // one process per GPU only with the whole environment of a rank; a scheduler or server role is refused as the
+  // sharded store of learner = sgd refuses it
+  if (role && std::string(role) != "worker") ReadRankEnv();
+  const bool sharded = role && nw && getenv("DIFACTO_RANK") && getenv("DIFACTO_RENDEZVOUS");
+  CHECK(sharded || (!IsDistributed() && !(nw && atoi(nw) > 1)))
       << "learner = lbfgs runs in one process on one GPU: a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is not supported";
   // lbfgs_learner.cc:369-393
   auto remain = Learner::Init(kwargs);
@@ -34,7 +42,17 @@ KWArgs LBFGSLearner::Init(const KWArgs& kwargs) {
   remain = updater_.Init(remain);
   CHECK(param_.loss == "fm" || param_.loss == "logit") << "unknown loss type: " << param_.loss << " (this build provides fm and logit)";
   const int k = param_.loss == "logit" ? 0 : updater_.param().V_dim;
-  DFH_CALL(dfh_lbfgs_create(DeviceContext::Get(), k, updater_.param().m, &obj_));
+  if (sharded) {
+    const RankEnv env = ReadRankEnv();   // before the device context: the rank's device
+    rank_ = env.rank;
+    world_ = env.world;
+    comm_ = ConnectRanks(rank_, world_, &files_, 120.0);
+    LOG(INFO) << "lbfgs: rank " << rank_ << " of " << world_ << " connected (" << (files_ ? "file transport" : "RCCL")
+              << "): a worker for part " << rank_ << " of the data and the server of one key range";
+    DFH_CALL(dfh_lbfgs_create_sharded(DeviceContext::Get(), comm_, k, updater_.param().m, &obj_));
+  } else {
+    DFH_CALL(dfh_lbfgs_create(DeviceContext::Get(), k, updater_.param().m, &obj_));
+  }
   return remain;
 }
 
@@ -43,9 +61,9 @@ void LBFGSLearner::PrepareData(std::vector<real_t>* rets) {
   // is cut by rows
   const size_t chunk_bytes = std::max<size_t>(64, static_cast<size_t>(param_.data_chunk_size * 1024 * 1024));
   const size_t kMaxNnz = size_t(1) << 31;
-  rets->assign(6, 0);
-  auto read = [&](const std::string& uri, int is_val, real_t* out) {
-    Reader reader(uri, param_.data_format, 0, 1, chunk_bytes);
+  double cnt[6] = {0, 0, 0, 0, 0, 0};
+  auto read = [&](const std::string& uri, int is_val, double* out) {
+    Reader reader(uri, param_.data_format, rank_, world_, chunk_bytes);   // part rank_ of world_
     size_t nrows = 0, nnz = 0, nchunks = 0;
     while (reader.Next()) {
       const auto& blk = reader.Value();
@@ -63,8 +81,13 @@ void LBFGSLearner::PrepareData(std::vector<real_t>* rets) {
     out[1] = nchunks;
     out[2] = nnz;
   };
-  read(param_.data_in, 0, rets->data());
-  if (param_.data_val.size()) read(param_.data_val, 1, rets->data() + 3);
+  read(param_.data_in, 0, cnt);
+  if (param_.data_val.size()) read(param_.data_val, 1, cnt + 3);
+  if (comm_) {
+    LOG(INFO) << "rank " << rank_ << ": " << cnt[0] << " training examples in " << cnt[1] << " chunks";
+    DFH_CALL(dfh_comm_allreduce_sum(comm_, cnt, 6));   // the counts the log shows are global
+  }
+  rets->assign(cnt, cnt + 6);
 }
 
 void LBFGSLearner::InitServer(std::vector<real_t>* rets) {
@@ -84,7 +107,12 @@ void LBFGSLearner::InitServer(std::vector<real_t>* rets) {
   }
   float nnz = 0, r = 0;
   DFH_CALL(dfh_lbfgs_evaluate(obj_, nullptr, &nnz, &r));
-  rets->assign({r, static_cast<real_t>(n)});
+  double total = static_cast<double>(n);   // this rank's slice; the log shows the model's size
+  if (comm_) {
+    LOG(INFO) << "rank " << rank_ << " owns " << nkeys << " keys, " << n << " parameters";
+    DFH_CALL(dfh_comm_allreduce_sum(comm_, &total, 1));
+  }
+  rets->assign({r, static_cast<real_t>(total)});
 }
 
 float LBFGSLearner::Direction() {
@@ -205,13 +233,15 @@ void LBFGSLearner::SaveModel() {
   }
   dfh_updater_param up;
   dfh_updater_param_default(&up, k);
-  dfh_table* t = nullptr;
-  DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
-  DFH_CALL(dfh_table_import(t, nkeys, keys.data(), scal.data(), has.data(), V.data()));
-  uint64_t saved = 0;
-  DFH_CALL(dfh_table_save(t, param_.model_out.c_str(), 0, &saved));
-  DFH_CALL(dfh_table_destroy(t));
-  LOG(INFO) << "model saved to " << param_.model_out;
+  // a sharded run: this rank's key range into <model_out>.part-<rank>, committed with the manifest (model_parts.h)
+  SaveModelParts(comm_, rank_, world_, param_.model_out, [&](const std::string& tmp) {
+    dfh_table* t = nullptr;
+    DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
+    if (nkeys) DFH_CALL(dfh_table_import(t, nkeys, keys.data(), scal.data(), has.data(), V.data()));
+    uint64_t saved = 0;
+    DFH_CALL(dfh_table_save(t, tmp.c_str(), 0, &saved));
+    DFH_CALL(dfh_table_destroy(t));
+  });
 }
 
 }  // namespace difacto

@@ -4,20 +4,26 @@
  *
  * The scheduler loop (RunScheduler: direction, Wolfe line search, stop criteria, epoch-end callbacks) follows
  * lbfgs_learner.cc:14-126 line by line.  The jobs it issues there to workers and servers are calls on one dfh_lbfgs
- * object here: one process, one GPU.  The (2m+1)^2 B-matrix algebra of the two-loop recursion stays on the host
+ * object here.  One process on one GPU, or one process per GPU (DMLC_ROLE=worker, DMLC_NUM_WORKER, DIFACTO_RANK and
+ * DIFACTO_RENDEZVOUS all set; example/run_local_gpus.sh): then every process is a worker for part <rank> of <world> of
+ * the data and the server of one key range of the model (dfh_lbfgs_create_sharded), and every scalar the scheduler
+ * decides on is a sum over the ranks, so all ranks print the same lines and stop at the same epoch.  The (2m+1)^2 B-matrix algebra of the two-loop recursion stays on the host
  * (lbfgs_mini::Twoloop), the vectors never leave the device.
  *
  * Differences from the reference:
  *   - no tile store on disk (data_cache is accepted and unused) and no thread pool (num_threads is accepted and unused)
  *   - model_out is written (the reference declares it and never writes it): the final weights in the format of
  *     learner = sgd's model_out, without optimiser state, so that task = predict learner = sgd model_in = ... scores them
- *   - a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) and task = predict are refused with a message
+ *   - model_out of a sharded run is <model_out>.part-<rank> plus the <model_out>.parts manifest, as learner = sgd writes it
+ *   - task = predict, and a multi-process environment that is not complete (see above), are refused with a message
  */
 #ifndef DIFACTO_HOST_LBFGS_LEARNER_H_
 #define DIFACTO_HOST_LBFGS_LEARNER_H_
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
+#include "./comm_setup.h"
 #include "./lbfgs_mini.h"
 #include "./lbfgs_param.h"
 #include "difacto/learner.h"
@@ -84,6 +90,10 @@ class LBFGSLearner : public Learner {
   LBFGSUpdater updater_;
   int nthreads_ = 1;
   dfh_lbfgs* obj_ = nullptr;
+  // the sharded mode: this process is rank rank_ of world_; comm_ is NULL in one process
+  int rank_ = 0, world_ = 1;
+  dfh_comm* comm_ = nullptr;
+  std::unique_ptr<FileExchange> files_;
   lbfgs_mini::Twoloop twoloop_;
   std::vector<std::function<void(int epoch, const lbfgs::Progress& prog)>> epoch_end_callback_;
 };

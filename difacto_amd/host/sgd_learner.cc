@@ -15,6 +15,7 @@
 #include "./hip_fm_loss.h"
 #include "./host_localizer.h"
 #include "./libsvm_reader.h"
+#include "./model_parts.h"
 #include "./sharded_store.h"
 #include "data/row_block.h"
 
@@ -774,49 +775,14 @@ void SGDLearner::IterateDataLiteral(const sgd::Job& job, sgd::Progress* progress
   }
 }
 
-// Updater::Save / Load.  A sharded run writes one part per rank (<model_out>.part-<rank>) plus a manifest
-// (<model_out>.parts: the number of parts, written by rank 0, which also removes the parts a run with more ranks left
-// behind under the same name) and reads exactly the parts the manifest names, keeping the keys of its own range: a
-// model can be re-loaded under any number of ranks, and stale parts of an earlier save are never imported.
+// Updater::Save / Load.  A sharded run writes one part per rank plus a manifest and reads exactly the parts the manifest
+// names, keeping the keys of its own range (model_parts.h).
 void SGDLearner::SaveModel() {
   auto* ss = dynamic_cast<ShardedDeviceStore*>(store_);
-  const std::string path = ss ? param_.model_out + ".part-" + std::to_string(store_->Rank()) : param_.model_out;
-  // written under a temporary name and renamed when complete: a reader never sees half a file, and a rank that dies
-  // mid-save leaves the previous part in place
-  const std::string tmp = path + ".tmp";
-  {
+  SaveModelParts(ss ? ss->comm() : nullptr, store_->Rank(), store_->NumWorkers(), param_.model_out, [&](const std::string& tmp) {
     std::unique_ptr<dmlc::Stream> fo(dmlc::Stream::Create(tmp.c_str(), "w"));
     GetUpdater()->Save(true, fo.get());
-  }
-  if (ss) {
-    // the manifest is the commit point of a sharded save: it may only name parts that are complete.  Every rank has closed
-    // its part when this all-reduce returns (a rank that failed never arrives: no new manifest); the parts are then
-    // renamed into place and rank 0 writes the manifest after a second round.
-    double ok[1] = {1.0};
-    DFH_CALL(dfh_comm_allreduce_sum(ss->comm(), ok, 1));
-    CHECK_EQ(static_cast<int>(ok[0]), store_->NumWorkers()) << "a rank did not finish its model part";
-  }
-  CHECK_EQ(rename(tmp.c_str(), path.c_str()), 0) << "cannot move " << tmp << " to " << path;
-  LOG(INFO) << "model saved to " << path;
-  if (ss) {
-    double done[1] = {1.0};
-    DFH_CALL(dfh_comm_allreduce_sum(ss->comm(), done, 1));   // every part is in place
-  }
-  if (ss && store_->Rank() == 0) {
-    const int world = store_->NumWorkers();
-    for (int n = world;; ++n) {  // parts of an earlier save with more ranks
-      const std::string stale = param_.model_out + ".part-" + std::to_string(n);
-      if (access(stale.c_str(), F_OK) != 0) break;
-      CHECK_EQ(unlink(stale.c_str()), 0) << "cannot remove the stale model part " << stale;
-      LOG(INFO) << "removed the stale model part " << stale;
-    }
-    const std::string mf = param_.model_out + ".parts";
-    FILE* f = fopen((mf + ".tmp").c_str(), "w");
-    CHECK(f) << "cannot write " << mf;
-    fprintf(f, "%d\n", world);
-    CHECK_EQ(fclose(f), 0);
-    CHECK_EQ(rename((mf + ".tmp").c_str(), mf.c_str()), 0);
-  }
+  });
 }
 
 void SGDLearner::LoadModel() {
@@ -829,7 +795,7 @@ void SGDLearner::LoadModel() {
     return;
   }
   uint64_t lo = 0, hi = 0, total = 0;
-  DFH_CALL(dfh_shard_owned_range(ss->shard(), nullptr, &lo, &hi));
+  DFH_CALL(dfh_shard_owned_range(ss->shard(), ss->splits(), &lo, &hi));   // the range the shard serves
   // how many parts: the manifest of the save; a model saved before manifests existed: every part up to the first gap
   int want = -1;
   const std::string mf = param_.model_in + ".parts";

@@ -28,74 +28,17 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include "./comm_setup.h"
 #include "./device_store.h"
 
 namespace difacto {
 
-/*! \brief test transport: an all-to-all-v through files in a shared directory */
-class FileExchange {
- public:
-  FileExchange(const std::string& dir, int rank, int world) : dir_(dir), rank_(rank), world_(world) {}
-  static int Call(void* user, const void* send, const size_t* sb, void* recv, const size_t* rb) {
-    return static_cast<FileExchange*>(user)->Run(static_cast<const char*>(send), sb, static_cast<char*>(recv), rb);
-  }
-
- private:
-  std::string Name(uint64_t seq, int src, int dst) const {
-    return dir_ + "/ex" + std::to_string(seq) + "." + std::to_string(src) + "." + std::to_string(dst);
-  }
-  int Run(const char* send, const size_t* sb, char* recv, const size_t* rb) {
-    const uint64_t seq = seq_++;
-    size_t off = 0;
-    for (int d = 0; d < world_; ++d) {
-      const std::string fin = Name(seq, rank_, d), tmp = fin + ".tmp";
-      FILE* f = fopen(tmp.c_str(), "wb");
-      if (!f) return 1;
-      if (sb[d] && fwrite(send + off, 1, sb[d], f) != sb[d]) return 1;
-      fclose(f);
-      if (rename(tmp.c_str(), fin.c_str()) != 0) return 1;
-      off += sb[d];
-    }
-    off = 0;
-    for (int s = 0; s < world_; ++s) {
-      const std::string fin = Name(seq, s, rank_);
-      FILE* f = nullptr;
-      for (int tries = 0; tries < 600000 && !(f = fopen(fin.c_str(), "rb")); ++tries)
-        std::this_thread::sleep_for(std::chrono::microseconds(100));
-      if (!f) return 1;
-      if (rb[s] && fread(recv + off, 1, rb[s], f) != rb[s]) return 1;
-      fclose(f);
-      unlink(fin.c_str());
-      off += rb[s];
-    }
-    return 0;
-  }
-  std::string dir_;
-  int rank_, world_;
-  uint64_t seq_ = 0;
-};
-
 class ShardedDeviceStore : public Store {
  public:
   ShardedDeviceStore() {
-    const char* w = getenv("DMLC_NUM_WORKER");
-    const char* r = getenv("DIFACTO_RANK");
-    // In the reference's launch a scheduler and servers run beside the workers and park in tracker_->Wait().  Here
-    // the workers own the model shards and schedule themselves: any other role joining would race the workers for
-    // rank 0.  It is refused, not parked: a launcher that starts one is misconfigured for this build.
-    const char* role = getenv("DMLC_ROLE");
-    CHECK(!role || std::string(role) == "worker")
-        << "DMLC_ROLE=" << role << ": this build runs workers only (each worker owns a key range of the model on its GPU and "
-        << "runs the scheduler loop itself); start DMLC_NUM_WORKER worker processes, no scheduler, no servers";
-    world_ = w ? atoi(w) : 1;
-    CHECK(r || world_ <= 1) << "DMLC_NUM_WORKER=" << world_ << " needs DIFACTO_RANK (0.." << world_ - 1
-                            << ") in every worker's environment: without it every process would come up as rank 0";
-    rank_ = r ? atoi(r) : 0;
-    CHECK(world_ >= 1 && world_ <= 32 && rank_ >= 0 && rank_ < world_)
-        << "DMLC_NUM_WORKER (1..32) / DIFACTO_RANK (0..DMLC_NUM_WORKER-1) are not consistent";
-    // one GPU per rank, unless the launcher already narrowed the visible devices to this rank's
-    if (!getenv("DIFACTO_DEVICE") && !getenv("HIP_VISIBLE_DEVICES") && !getenv("ROCR_VISIBLE_DEVICES"))
-      setenv("DIFACTO_DEVICE", std::to_string(rank_).c_str(), 0);
+    const RankEnv env = ReadRankEnv();
+    world_ = env.world;
+    rank_ = env.rank;
   }
   virtual ~ShardedDeviceStore() {
     if (shard_) dfh_shard_destroy(shard_);
@@ -107,34 +50,7 @@ class ShardedDeviceStore : public Store {
     auto* up = CHECK_NOTNULL(dynamic_cast<DeviceSGDUpdater*>(CHECK_NOTNULL(updater_.get())));
     CHECK(up->device_param().V_init == "hash" || up->param().V_dim == 0)
         << "the sharded store needs V_init=hash: the rand_r chain of the reference depends on the global order of allocations";
-    const char* rv = getenv("DIFACTO_RENDEZVOUS");
-    const char* kind = getenv("DIFACTO_COMM");
-    CHECK(rv || world_ == 1) << "DIFACTO_RENDEZVOUS must name the rendezvous file (rccl) or directory (file transport)";
-    dfh_ctx* ctx = DeviceContext::Get();
-    if (kind && std::string(kind) == "file") {
-      files_.reset(new FileExchange(rv ? rv : "/tmp", rank_, world_));
-      DFH_CALL(dfh_comm_create_callback(ctx, rank_, world_, &FileExchange::Call, files_.get(), &comm_));
-    } else {
-      char id[DFH_COMM_ID_BYTES];
-      if (rank_ == 0) {
-        DFH_CALL(dfh_comm_unique_id(id));
-        if (world_ > 1) {
-          const std::string tmp = std::string(rv) + ".tmp";
-          FILE* f = CHECK_NOTNULL(fopen(tmp.c_str(), "wb"));
-          CHECK_EQ(fwrite(id, 1, sizeof(id), f), sizeof(id));
-          fclose(f);
-          CHECK_EQ(rename(tmp.c_str(), rv), 0);
-        }
-      } else {
-        FILE* f = nullptr;
-        for (int tries = 0; tries < 120000 && !(f = fopen(rv, "rb")); ++tries)
-          std::this_thread::sleep_for(std::chrono::milliseconds(1));
-        CHECK(f) << "rank 0 never wrote the rendezvous file " << rv;
-        CHECK_EQ(fread(id, 1, sizeof(id), f), sizeof(id));
-        fclose(f);
-      }
-      DFH_CALL(dfh_comm_create_rccl(ctx, rank_, world_, id, &comm_));
-    }
+    comm_ = ConnectRanks(rank_, world_, &files_);
     LOG(INFO) << "sharded store: rank " << rank_ << " of " << world_ << " connected ("
               << (files_ ? "file transport" : "RCCL") << ")";
     return kwargs;
@@ -158,6 +74,7 @@ class ShardedDeviceStore : public Store {
     DFH_CALL(dfh_shard_create(up->table(), comm_, balanced ? splits.data() : nullptr, &shard_));
     if (dp.shard_exchange == "overlap") DFH_CALL(dfh_shard_set_exchange(shard_, 1));
     if (reserve_keys_) DFH_CALL(dfh_shard_reserve(shard_, reserve_keys_, 2 * reserve_keys_));  // no re-allocation inside a step
+    if (balanced) splits_ = splits;
     uint64_t lo = 0, hi = 0;
     DFH_CALL(dfh_shard_owned_range(shard_, balanced ? splits.data() : nullptr, &lo, &hi));
     LOG(INFO) << "sharded store: rank " << rank_ << " owns the reversed keys [" << lo << ", " << (hi ? std::to_string(hi) : "2^64")
@@ -201,6 +118,8 @@ class ShardedDeviceStore : public Store {
    *  when the shard is created; 0: they grow when a step first meets a size */
   void set_reserve_keys(size_t n) { reserve_keys_ = n; }
   dfh_comm* comm() { return comm_; }
+  /*! \brief the split keys the shard was created with, NULL for the uniform ranges (what dfh_shard_owned_range takes) */
+  const uint64_t* splits() const { return splits_.empty() ? nullptr : splits_.data(); }
 
  private:
   int rank_ = 0, world_ = 1;
@@ -208,6 +127,7 @@ class ShardedDeviceStore : public Store {
   dfh_comm* comm_ = nullptr;
   dfh_shard* shard_ = nullptr;
   size_t reserve_keys_ = 0;
+  std::vector<uint64_t> splits_;
   std::unique_ptr<FileExchange> files_;
 };
 

@@ -522,6 +522,22 @@ int dfh_vec_line_step(dfh_ctx* ctx, uint64_t n, float* w, const float* p, float 
  * DFH_ERR_CAPACITY and the bytes needed. */
 typedef struct dfh_lbfgs dfh_lbfgs;
 int dfh_lbfgs_create(dfh_ctx* ctx, int V_dim, int m, dfh_lbfgs** out);
+/* The same learner over the ranks of a communicator (RCCL or host callback; not the loop-back transport): each rank is a
+ * worker for its own chunks (1/N of the rows) and the owner of one slice of the ascending keys (1/N of the model and
+ * of the optimiser state), what the reference's RunScheduler does with its worker and server groups
+ * (src/lbfgs/lbfgs_learner.cc:14-163).  On such an object EVERY dfh_lbfgs_* call below is COLLECTIVE: every rank makes
+ * the same calls in the same order (a rank without rows adds no chunk and still takes part).  What they return —
+ * loss, AUC x n, incr_B, <p, g>, objv, nnz(w), r(w) — are sums over the ranks (each rank's fp64 partials added in rank
+ * order): every rank gets the same bits, and with one rank the bits of dfh_lbfgs_create's object.
+ *   init_model  split keys balanced on the ranks' training keys; the owner adds the counts over ranks and filters
+ *               (tail_feature_filter, V_threshold) on the global counts; V comes from the one rand_r(seed = 0) chain in
+ *               global key order, so the union of the shards is the model one process builds from the same rows.
+ *   calc_grad   the owners' rows go to the workers that use them (k_lb_pack + all-to-all-v), the chunks run on the
+ *               local copy, the local gradients go back and each owned element adds its contributions in ascending
+ *               source rank (k_lb_reduce): no float atomics, the same bits over every run and transport.
+ *   the others  run on the rank's own slice; only their fp64 partials cross the wire.
+ * shape, get_model and set_weights see the rank's own slice (keys ascending).  DFH_ERR_CAPACITY applies per rank. */
+int dfh_lbfgs_create_sharded(dfh_ctx* ctx, dfh_comm* comm, int V_dim, int m, dfh_lbfgs** out);
 int dfh_lbfgs_destroy(dfh_lbfgs* o);
 /* a chunk of raw rows (Reader::Value()), localized on the device with Localizer(-1) (TileBuilder::Add) and kept */
 int dfh_lbfgs_add_chunk(dfh_lbfgs* o, int is_val, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,
