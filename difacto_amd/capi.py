@@ -37,7 +37,7 @@ SYMBOLS = [
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
     "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate", "dfh_lbfgs_create_sharded",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
-    "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred",
+    "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -124,6 +124,7 @@ def lib():
     L.dfh_batch_create.argtypes = [vp, sz, sz, PP(vp)]
     L.dfh_batch_destroy.argtypes = [vp]
     L.dfh_batch_create_many.argtypes = [vp, i32, sz, sz, PP(vp)]
+    L.dfh_batch_split_entries.argtypes = [vp, vp]
     L.dfh_batch_load_host.argtypes = [vp, sz, vp, vp, vp, vp]
     L.dfh_batch_load_device.argtypes = [vp, sz, sz, vp, vp, vp, vp]
     L.dfh_batch_attach_device.argtypes = [vp, sz, sz, vp, vp, vp, vp]
@@ -645,6 +646,12 @@ class Batch:
         out = np.zeros(nrows, np.float32)
         _ck(lib().dfh_batch_get_pred(self.h, _p(out)))
         return out
+
+    def split_entries(self):
+        """entries the last training step put on the split list (parts of the keys with more than 4 096 occurrences)"""
+        n = C.c_uint32(0)
+        _ck(lib().dfh_batch_split_entries(self.h, C.byref(n)))
+        return int(n.value)
 
     def forward(self, V_dim, d_rows):
         _ck(lib().dfh_batch_forward(self.h, V_dim, _dp(d_rows)))

@@ -192,6 +192,10 @@ struct dfh_batch {
   uint32_t* d_split_ticket = nullptr;
   float* d_split_part = nullptr;
   size_t split_cap = 0;
+  // the list's two counters, d_U + 2 + {0, 1} (SplitOut): split_sel = the one the next listing step appends to (zero by then),
+  // split_last = the one the last listing step filled; split_listing: a launch of the running step has taken the list
+  int split_sel = 0, split_last = 0;
+  bool split_listing = false;
   uint32_t seg_nb = 0;                              // list buckets of the current localized view
   uint2* d_uw = nullptr;           // {table row, w} per unique key, written by the step's k_lookup
   uint32_t *d_urow = nullptr, *d_need = nullptr, *d_rank = nullptr, *d_total = nullptr;
@@ -281,6 +285,11 @@ int main_begin(dfh_batch* b) {
 }
 int main_end(dfh_batch* b) {
   dfh_ctx* c = b->ctx;
+  if (b->split_listing) {  // this step's launches filled one counter of the split list and zeroed the other: the next step's
+    b->split_listing = false;
+    b->split_last = b->split_sel;
+    b->split_sel ^= 1;
+  }
   if (c->pipeline) {
     DFH_HIP(hipEventRecord(b->ev_free, c->stream));
     b->free_pending = true;
@@ -292,6 +301,17 @@ int sync_all(dfh_ctx* c) {
   for (hipStream_t p : c->extra) DFH_HIP(hipStreamSynchronize(p));
   DFH_HIP(hipStreamSynchronize(c->stream));
   return DFH_OK;
+}
+// the list of the very hot keys' parts for the update's split role (SplitOut, dfh_kernels.hip): handed to the launches of a
+// TRAINING step that see the minibatch's keys with their segments; u_base = rank of the first key such a launch sees
+inline bool split_listed(const dfh_ctx* c, const dfh_batch* b, int is_train) { return b && is_train && c->upd_kernel && c->upd_split; }
+// (every launch that takes it appends to the batch object's current counter and zeroes the other one; the step's main_end then
+// swaps the two — the owner of SplitOut's invariant.  Called after main_begin: behind the batch object's previous update.)
+inline uint32_t* split_counter(const dfh_batch* b) { return b->d_U + 2 + b->split_sel; }
+inline SplitOut split_out(const dfh_ctx* c, dfh_batch* b, int is_train, uint32_t u_base) {
+  if (!split_listed(c, b, is_train)) return SplitOut{nullptr, nullptr, 0u, 0u};
+  b->split_listing = true;
+  return SplitOut{b->d_split_ent, split_counter(b), u_base, (uint32_t)b->split_cap};
 }
 }  // namespace
 
@@ -357,6 +377,10 @@ int check_table_err(dfh_table* t) {
   }
   if (e & 8u) {
     set_error("key index: a claimed slot never received its row id (find_or_insert gave up waiting)");
+    return DFH_ERR_STATE;
+  }
+  if (e & 16u) {
+    set_error("split list: a very hot key's parts did not fit (lookup_split; the list was not empty when the step began)");
     return DFH_ERR_STATE;
   }
   return DFH_OK;
@@ -554,7 +578,7 @@ BatchView batch_view(const dfh_batch* b) {
   v.seg.few = b->d_few;
   v.seg.few_ent = b->d_few_ent;
   v.seg.split_ent = b->d_split_ent;
-  v.seg.split_n = b->d_U + 2;   // the batch's device scalar block: [0] U, [1] REFRAND total, [2] entries of the split list
+  v.seg.split_n = split_counter(b);   // the batch's device scalar block: [0] U, [1] REFRAND total, [2], [3] entries of the split list (SplitOut)
   return v;
 }
 
@@ -715,7 +739,7 @@ UpdArgs upd_args(dfh_batch* b, const TableView& tv, int k, int kp, uint32_t* nee
   a.seg.few = b->d_few;
   a.seg.few_ent = b->d_few_ent;
   a.seg.split_ent = b->d_split_ent;
-  a.seg.split_n = b->d_U + 2;
+  a.seg.split_n = split_counter(b);   // (inside a step: the counter its listing launches filled; otherwise an empty one)
   a.split_part = b->d_split_part;
   a.split_ticket = b->d_split_ticket;
   a.nb_split = 0;
@@ -772,7 +796,7 @@ int launch_update_fused(dfh_batch* b, const TableView& tv, int k, int kp, uint32
   // round 4 by shifting the role 1 or 4 blocks: no difference, 86.0 against 85.9 M examples/sec — kept because it is free.)
   a.nb_few += (8u - (a.nb_hot + a.nb_mid + a.nb_few) % 8u) % 8u;
   // the parts of keys with more than HOT_SPLIT_MIN occurrences: taken by the hot role's blocks before their own lists
-  a.nb_split = (c->upd_split && nnz > HOT_SPLIT_MIN) ? 1u : 0u;
+  a.nb_split = (c->upd_split && nnz > HOT_SPLIT_MIN) ? (uint32_t)b->split_cap : 0u;
   const size_t nb_single = std::max<size_t>(1, std::min<size_t>((b->nrows + UPD_NW - 1) / UPD_NW, (size_t)c->upd_single_blocks));
   hipEvent_t ea = nullptr, eb = nullptr;  // timing rides on the dispatch, like the forward's
   if ((c->timing >> DFH_K_BACKWARD) & 1u) {
@@ -3465,7 +3489,7 @@ int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt) {
     // (the lookup's first block also adds up the AUC slots this batch object's previous step left behind)
     const int gl = grid_for_threads(Nb, c);
     // the pass that sees every unique key's segment lists the parts of the very hot ones for the update's split role
-    const SplitOut so = (is_train && c->upd_kernel && c->upd_split) ? SplitOut{b->d_split_ent, b->d_U + 2, 0u} : SplitOut{nullptr, nullptr, 0u};
+    const SplitOut so = split_out(c, b, is_train, 0u);
     RiderSet rs;  // single-queue step: the stages of later minibatches' Localizer that belong into this launch
     collect_riders(c, 0, true, ((uint32_t)gl + 7u) / 8u, &rs);
     if (rs.n)
@@ -3521,6 +3545,20 @@ int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt) {
     DFH_HIP(hipGetLastError());
   }
   return main_end(b);
+}
+
+int dfh_batch_split_entries(dfh_batch* b, uint32_t* n) {
+  DFH_ARG(b && n, "dfh_batch_split_entries: NULL argument");
+  dfh_ctx* c = b->ctx;
+  DFH_HIP(hipSetDevice(c->device));
+  if (b->pend_stage < RID_STAGES) {  // (single-queue step: Localizer stages still noted are queued first; they zero the counter)
+    int rc = flush_pending(b);
+    if (rc) return rc;
+  }
+  if (b->ready_pending) DFH_HIP(hipStreamWaitEvent(c->stream, b->ev_ready, 0));
+  DFH_HIP(hipMemcpyAsync(n, b->d_U + 2 + b->split_last, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  DFH_HIP(hipStreamSynchronize(c->stream));
+  return DFH_OK;
 }
 
 int dfh_batch_forward(dfh_batch* b, int V_dim, const float* d_rows) {

@@ -78,7 +78,7 @@ struct SegLists {
   // ALSO listed part by part — {u, beg_p, end_p, p << 16 | nparts}, the parts of a key consecutive — so that k_update_fused can
   // give every part a block of its own (upd_split_role); it stays in the hot list for the consumers that take whole segments
   const SegEnt* split_ent;
-  const uint32_t* split_n;  // entries in split_ent (device scalar: reset by the Localizer's count pass, filled by k_lookup_step)
+  const uint32_t* split_n;  // entries in split_ent (device scalar: emptied by every training step before its listing launches fill it: SplitOut)
 };
 #ifndef DFH_HOT_SPLIT
 #define DFH_HOT_SPLIT 1024

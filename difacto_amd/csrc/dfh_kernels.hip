@@ -510,15 +510,33 @@ __global__ void __launch_bounds__(256) k_auc_finalize(AucFin f) { auc_finalize_b
 // is the kernel descriptor's next free VGPR in granules of 8.  Emit did not fit in the 32 registers five 96-register waves of
 // k_update_fused leave free on a SIMD at either size; since the register fit of the preparation kernels it is allocated 32 —
 // tests/test_prep_registers.py.)
+// INVARIANT (one owner): the list is empty when a training step's first listing launch starts.  The STEP keeps it.  A batch
+// object has TWO counters (d_U + 2, d_U + 3; both zero at creation): the listing launches of a step append to one (`n`) and
+// leave the OTHER at zero (split_other: one store by the launch's first thread), and the step that listed then swaps them
+// (split_out / main_end, dfh_api.hip) — so the next step, whenever it comes and whether or not a localize came between, starts
+// from a counter that the previous step's launches zeroed, and this step's update reads the one just filled.  The reset
+// costs no launch of its own (a 4-byte memset node per step was measured at -3 % on the default benchmark line).  A step may
+// make two listing launches, the own keys' lookup and the others' row words (sharded store): both append to the same
+// counter and zero the same other one.  A batch object can be stepped any number of times per localize (later epochs,
+// dfh_batch_load_localized_host): when only the Localizer emptied the list every very hot key was listed once more per
+// step and updated once per copy.  The Localizer's count pass and k_seg_lists_reset still zero d_U + 2; no step relies on it.
 struct SplitOut {
   SegEnt* ent;        // NULL: no list (the update's hot role takes every key whole)
-  uint32_t* n;        // entries so far (zeroed by the Localizer's count pass)
+  uint32_t* n;        // entries so far (zero when the step begins: see above); the OTHER counter is its neighbour, split_other(n)
   uint32_t u_base;    // rank of the first key this launch sees (the sharded store looks up its own keys only)
-};
-__device__ __forceinline__ void lookup_split(const SplitOut& so, uint32_t u, uint32_t beg, uint32_t end) {
+  uint32_t cap;       // entries the list can hold (dfh_batch::split_cap: enough for any minibatch the batch object can hold)
+};   // (24 bytes, as before the capacity was added: the step's lookup is short of scalar registers)
+// d_U + 2 <-> d_U + 3 (d_U is 256-byte aligned: the two counters differ in address bit 2)
+__device__ __forceinline__ uint32_t* split_other(uint32_t* n) { return reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(n) ^ 4u); }
+// err: the table's error word — bit 16 = a key's parts did not fit (dfh_table_check)
+__device__ __forceinline__ void lookup_split(const SplitOut& so, uint32_t* err, uint32_t u, uint32_t beg, uint32_t end) {
   if (!(DFH_HOT_SPLIT_BUILD & 1) || !so.ent || end - beg <= HOT_SPLIT_MIN) return;
   const uint32_t nparts = (end - beg + HOT_SPLIT - 1u) / HOT_SPLIT;
   const uint32_t base = atomicAdd(so.n, nparts);
+  if (base + nparts > so.cap) {   // cannot happen with an emptied list (split_cap); nothing is written, the counter stays beyond
+    atomicOr(err, 16u);           // cap, and the update, which sees that, leaves the whole list alone (upd_split_role)
+    return;
+  }
   for (uint32_t p = 0; p < nparts; ++p)
     so.ent[base + p] = make_uint4(u + so.u_base, beg + p * HOT_SPLIT, min(beg + (p + 1u) * HOT_SPLIT, end), (p << 16) | nparts);
 }
@@ -528,9 +546,10 @@ __device__ __forceinline__ void lookup_body(const TableView& t, const uint64_t* 
                          uint32_t n_static, uint32_t* __restrict__ urow, const float* __restrict__ cnt,
                          const uint32_t* __restrict__ col_ptr, int push_cnt, uint32_t* __restrict__ need_init,
                          int rows_known, uint2* __restrict__ uw, AucFin fin, const uint32_t bid, const uint32_t nblk,
-                         const SplitOut so = SplitOut{nullptr, nullptr, 0u}) {
+                         const SplitOut so = SplitOut{nullptr, nullptr, 0u, 0u}) {
   // a step's lookup also closes the AUC its batch object's previous step left pending (dfh_sgd_step; fin.n == 0: none)
   if (fin.n && bid == 0) auc_finalize_block(fin);
+  if (SPLIT && so.n && bid == 0 && threadIdx.x == 0) *split_other(so.n) = 0u;   // the NEXT step's split list starts empty (SplitOut)
   uint32_t n = d_n ? *d_n : n_static;
   __shared__ uint32_t ins_sh[8];
   // (block-uniform trip count: the insert below is a block-wide call)
@@ -546,7 +565,7 @@ __device__ __forceinline__ void lookup_body(const TableView& t, const uint64_t* 
     else r = active ? find_or_insert(t, key) : 0u;
     if (!active) continue;
     if (urow && !rows_known) urow[u] = r;
-    if (SPLIT && col_ptr) lookup_split(so, u, col_ptr[u], col_ptr[u + 1]);
+    if (SPLIT && col_ptr) lookup_split(so, t.err, u, col_ptr[u], col_ptr[u + 1]);
     float w = 0.f;
     bool hasv = false;
     if (push_cnt) {
@@ -616,21 +635,23 @@ struct UwRemote {
   uint2* uw;                 // the whole minibatch's array (the lookup's `uw` starts at the rank's own keys)
   const uint32_t* col_ptr;   // likewise
   SplitOut so;               // the others' keys can be very hot too (u_base 0: ranks are the minibatch's)
+  uint32_t* err;             // the table's error word (lookup_split)
 };
 __device__ __forceinline__ void uw_remote_body(const UwRemote& m) {
   const uint32_t U = *m.d_U;
+  if (m.so.n && blockIdx.x == 0 && threadIdx.x == 0) *split_other(m.so.n) = 0u;   // (as lookup_body: SplitOut)
   for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < U; u += gridDim.x * blockDim.x) {
     if (u - m.lo < m.hi - m.lo) continue;
     // (bit 30: the key occurs once in the minibatch — the singles role of the mixed update launch takes it)
     const uint32_t single = (m.col_ptr && m.col_ptr[u + 1] - m.col_ptr[u] == 1u) ? kSingleRow : 0u;
-    if (m.col_ptr) lookup_split(m.so, u, m.col_ptr[u], m.col_ptr[u + 1]);
+    if (m.col_ptr) lookup_split(m.so, m.err, u, m.col_ptr[u], m.col_ptr[u + 1]);
     const float2 wh = *reinterpret_cast<const float2*>(m.rows + (size_t)u * m.stride);   // [w, has_V (0 / 1 as float), ...]
     m.uw[u] = make_uint2(u | kRemoteRow | single | (wh.y != 0.f ? kHasV : 0u), __float_as_uint(wh.x));
   }
 }
 __global__ void k_uw_remote(const float* __restrict__ rows, size_t stride, const uint32_t* __restrict__ d_U, uint32_t lo,
-                            uint32_t hi, uint2* __restrict__ uw, const uint32_t* __restrict__ col_ptr, SplitOut so) {
-  uw_remote_body(UwRemote{rows, stride, d_U, lo, hi, uw, col_ptr, so});
+                            uint32_t hi, uint2* __restrict__ uw, const uint32_t* __restrict__ col_ptr, SplitOut so, uint32_t* err) {
+  uw_remote_body(UwRemote{rows, stride, d_U, lo, hi, uw, col_ptr, so, err});
 }
 // the own keys' lookup and the others' row words in ONE launch (overlapped exchange: the rows of the other owners arrived
 // during the previous step; one launch boundary less on the main stream of the sharded step)
@@ -1481,7 +1502,7 @@ __global__ void k_seg_lists_reset(uint2* mid0, uint2* hot0, uint2* few0, uint32_
     *mid0 = make_uint2(0u, 0u);
     *hot0 = make_uint2(0u, 0u);
     *few0 = make_uint2(0u, 0u);
-    *split_n = 0u;   // (these paths list whole segments only: no part lists)
+    *split_n = 0u;   // (an empty split list until the first training step; every step empties it itself: SplitOut)
   }
 }
 

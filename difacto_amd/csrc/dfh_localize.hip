@@ -117,7 +117,7 @@ struct LocView {
   uint64_t* last_key;
   uint32_t* nheads;       // [P] runs of equal keys inside the bucket
   uint32_t* lh;           // [P] local index of the bucket's last run head (0: one run only)
-  uint32_t* split_n;      // entries of the split list (SegLists::split_ent): zeroed by the count pass, filled by the step's k_lookup
+  uint32_t* split_n;      // entries of the split list (SegLists::split_ent): left empty by the count pass; every training step empties it again before its lookup fills it (SplitOut)
 };
 
 // long-segment lists for k_backward_all, one slot range per list bucket (dfh_internal.h: SegLists)
@@ -319,7 +319,7 @@ __device__ __forceinline__ void loc_count_block(const LocView& v, const uint32_t
     sp[b] = b < P - 1 ? v.spl_pos[b] : ~0u;
   }
   const uint32_t base = bid * LOC_TILE;
-  if (bid == 0 && threadIdx.x == 0 && v.split_n) *v.split_n = 0u;   // (the step's k_lookup appends to the list)
+  if (bid == 0 && threadIdx.x == 0 && v.split_n) *v.split_n = 0u;   // (empty until a training step; the STEP owns emptying it: SplitOut)
   uint64_t key[PER];
   if (GATHER) {
     // the rows that cover this tile: their offsets and where they start in their row buffer, in LDS

@@ -100,7 +100,9 @@ struct UpdArgs {
   // split_part[entry][UPD_SPLIT_STRIDE], a ticket per key in split_ticket[first entry] (zero between launches)
   float* split_part;
   uint32_t* split_ticket;
-  uint32_t nb_split;        // 1: the hot role's blocks take the split list's parts first; 0: keys of any length go through the hot role whole
+  // > 0: the hot role's blocks take the split list's parts first, and the value is the number of entries the list can hold (a
+  // counter beyond it means lookup_split refused a key: error word bit 16); 0: keys of any length go through the hot role whole
+  uint32_t nb_split;
 };
 constexpr int UPD_SPLIT_STRIDE = 4 + 256;   // gw, xxp, -, - | gv[kp <= 256]
 
@@ -412,7 +414,7 @@ __device__ __forceinline__ void upd_hot_role(const UpdArgs& a, uint32_t blk, uin
 // tiles per wave at C3 size, ~3 dependent round trips each — a launch as long as that chain whatever else it holds.  Here
 // every part has a block; a part's sums go to split_part[entry] (stores, then a device-scope RELEASE: the L2's dirty lines are
 // written back — no invalidate), a ticket per key counts the parts that have arrived, and the block that brings the LAST part
-// adds the partials up IN PART ORDER (reads that bypass the L2: agent-scope atomic loads) — deterministic, whichever block
+// adds the partials up IN PART ORDER (behind a device-scope ACQUIRE; reads that bypass the L2: agent-scope atomic loads) — deterministic, whichever block
 // comes last — fetches the row and applies the update.  Nobody waits for anybody.
 template <int L, bool EXACT, int DB, bool HAS_VAL, bool MIXED>
 __device__ __forceinline__ void upd_split_role(const UpdArgs& a, uint32_t blk, uint32_t nblk, float& pen, char* smem) {
@@ -422,7 +424,8 @@ __device__ __forceinline__ void upd_split_role(const UpdArgs& a, uint32_t blk, u
   const int kp = EXACT ? 4 * L : a.kp, k = a.k;
   const bool sub_ok = EXACT ? true : (sub * 4 < kp);
   const int w = threadIdx.x >> 6;
-  const uint32_t n = *a.seg.split_n;
+  uint32_t n = *a.seg.split_n;   // this step's entries: the step emptied the list before its first listing launch (SplitOut)
+  if (n > a.nb_split) n = 0u;   // lookup_split refused a key and left holes below the counter: nothing of the list is used
   for (uint32_t j = blk; j < n; j += nblk) {
     const SegEnt e = a.seg.split_ent[j];
     const uint32_t u = e.x, beg = e.y, end = e.z, p = e.w >> 16, nparts = e.w & 0xFFFFu;
@@ -458,6 +461,8 @@ __device__ __forceinline__ void upd_split_role(const UpdArgs& a, uint32_t blk, u
       if (sub == 0) t = atomicAdd(a.split_ticket + first, 1u);
       t = __shfl(t, 0, 64);   // (lane 0 is sub 0 of group 0)
       if (t == nparts - 1u) {   // the last part of its key to arrive: add the parts up in part order, apply
+        // ACQUIRE, pairing with the release above through the ticket: the other parts' sums happen-before the loads below
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         gw = 0.f; xxp = 0.f;
         g4 = make_float4(0.f, 0.f, 0.f, 0.f);
         for (uint32_t q = 0; q < nparts; ++q) {

@@ -292,6 +292,11 @@ int dfh_batch_shape(dfh_batch* b, size_t* nrows, size_t* nnz, size_t* U); /* syn
 int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt);
 int dfh_batch_progress(dfh_batch* b, dfh_progress* out, int reset); /* synchronises */
 int dfh_batch_get_pred(dfh_batch* b, float* pred);                  /* synchronises */
+/* entries of the batch's split list: the parts (of 1 024 occurrences) of the keys with more than 4 096 occurrences that the
+ * last TRAINING step (dfh_sgd_step, dfh_shard_step) of this batch object listed for its update; 0 before the first.  Every
+ * training step starts from an empty list, so the value does not depend on how often the batch was stepped since it was
+ * localized.  Read-only; synchronises. */
+int dfh_batch_split_entries(dfh_batch* b, uint32_t* n);
 
 /* -------------------------------------------- sharded (multi-GPU) building blocks */
 /* Rows cross the wire in a fixed-stride layout of dfh_row_stride(V_dim) floats:

@@ -450,36 +450,71 @@ def _check_step_state(so, exp1, keys, kw, V_dim, gtol_w, gtol_V, what):
 
 
 def _run_fused_vs_oracle(capi, ctx, oracle, V_dim, mode, batches, epochs, kw, device_localize=True, capacity=1 << 16,
-                         table=None, count_push_every_step=False):
+                         table=None, count_push_every_step=False, relocalize=True, upd_split=True, batch_nnz=None,
+                         validate_between=False, record_as=None, out=None):
     """dfh_sgd_step against the oracle's worker loop, STEP BY STEP FROM IDENTICAL STATE (round 5; VERDICT r4: the fixed
     rtol 5e-5 on logits / 2e-4 on the final weights of rounds 1-4 let a defect of 4 x rtol through): before every step the
     oracle store takes the device's state of the step's keys, then both sides run the step and are compared with the
     tolerance north_star states — logits at rtol 1e-5 + the summation floor, every field of every touched SGDEntry at
-    the gradient tolerance times the field's sensitivity (_check_step_state)."""
+    the gradient tolerance times the field's sensitivity (_check_step_state).
+
+    After EVERY step the batch object's split list must hold exactly the parts of this minibatch's very hot keys
+    (split_testlib.split_entries_expected over the oracle's localized counts; 0 with the ctx option upd_split off) — however
+    often the object has been stepped since it was localized.
+
+    relocalize=False: one batch object per minibatch out of ONE allocation (dfh_batch_create_many), each localized once,
+    then stepped in every epoch.  The run is bounded so that even a list that grew with every step would stay inside its
+    buffers: epochs x entries per step <= split_cap, asserted before the first step.
+    validate_between: a validation step (is_train = 0) on the same batch object after every training step — the model
+    must not move, and the list must still be the training step's.
+    out (a dict): receives preds (every step's logits) and model (the final pull of all keys)."""
     from oracle import bindings as ob, tolerance as T
+    from split_testlib import split_cap, split_entries_expected
     om = ob.INIT_HASH if mode == "hash" else ob.INIT_REFRAND
     dm = capi.INIT_HASH if mode == "hash" else capi.INIT_REFRAND
     so = oracle.store_create(init_mode=om, V_dim=V_dim, **kw)
     tb = table if table is not None else capi.Table(ctx, capacity, V_dim=V_dim, init_mode=dm, **kw)
     max_rows = max(len(b["label"]) for b in batches)
     max_nnz = max(int(b["offset"][-1]) for b in batches)
-    bt = capi.Batch(ctx, max_rows, max(max_nnz, 1))
+    cap_nnz = max(max_nnz, 1) if batch_nnz is None else batch_nnz
+    assert cap_nnz >= max_nnz
     locs = [oracle.localize(b["offset"], b["index"]) for b in batches]
     designs = [T.design(l["offset"], l["index"], b["value"], l["U"]) for b, l in zip(batches, locs)]
+    listed = [split_entries_expected(l["feacnt"]) if upd_split else 0 for l in locs]
+
+    def load(bt_, b, loc, with_cnt):
+        if device_localize:
+            bt_.load_host(b["offset"], b["index"], b["value"], b["label"])
+            bt_.localize()
+        else:
+            bt_.load_localized_host(loc["offset"], loc["index"], b["value"], b["label"], loc["feaids"],
+                                    loc["feacnt"] if with_cnt else None)
+
+    if relocalize:
+        bt = capi.Batch(ctx, max_rows, cap_nnz)
+        bts = [bt] * len(batches)
+    else:
+        # (steps of one batch object) x (entries a step lists) stays inside the list even if no step emptied it
+        assert epochs * (2 if validate_between else 1) * max(listed + [0]) <= split_cap(cap_nnz), (epochs, listed, split_cap(cap_nnz))
+        bts = capi.create_batches(ctx, len(batches), max_rows, cap_nnz)
+        for bt_, b, loc in zip(bts, batches, locs):
+            load(bt_, b, loc, True)
+            assert bt_.split_entries() == 0   # nothing is listed before a training step
     worst_pred = worst_state = 0.0
     for epoch in range(epochs):
         push_cnt = epoch == 0 or count_push_every_step
-        for b, loc, D in zip(batches, locs, designs):
+        for bt, b, loc, D, nlist in zip(bts, batches, locs, designs, listed):
             if not (epoch == 0 and b is batches[0] and table is None):
                 _resync_oracle(so, _export_index(tb), loc["feaids"])
-            if device_localize:
-                bt.load_host(b["offset"], b["index"], b["value"], b["label"])
-                bt.localize()
-            else:
-                bt.load_localized_host(loc["offset"], loc["index"], b["value"], b["label"], loc["feaids"],
-                                       loc["feacnt"] if push_cnt else None)
+            if relocalize:
+                load(bt, b, loc, push_cnt)
             bt.sgd_step(tb, is_train=True, push_cnt=push_cnt)
             pg = bt.pred()
+            got_list = bt.split_entries()
+            assert got_list == nlist, "epoch %d: the split list holds %d entries after the step, the minibatch has %d parts" % (
+                epoch, got_list, nlist)
+            if out is not None:
+                out.setdefault("preds", []).append(pg.copy())
             prog_g = bt.progress(reset=True)
             if push_cnt:  # the step's own count push precedes its pull (sgd_learner.cc:214-217)
                 so.push(loc["feaids"], ob.FEA_COUNT, loc["feacnt"])
@@ -513,17 +548,36 @@ def _run_fused_vs_oracle(capi, ctx, oracle, V_dim, mode, batches, epochs, kw, de
             nterms = loc["U"] * (1 + V_dim)
             assert prog_g.penalty == pytest.approx(prog_o.penalty, rel=max(1e-4, min(0.05, 0.5 * nterms * 2.0 ** -24)), abs=1e-6)
             assert prog_g.nrows == prog_o.nrows
+            if validate_between:
+                before = _export_index(tb)
+                bt.sgd_step(tb, is_train=False)
+                pv2 = bt.pred()
+                after = _export_index(tb)
+                assert all(np.array_equal(x, y) for x, y in zip(before, after) if x is not None), "a validation step moved the model"
+                assert bt.split_entries() == nlist
+                bt.progress(reset=True)
+                # its logits: FMLoss::Predict on the weights the training step left on the device (V_dim > 0 cases only)
+                vals_d, lens_d = tb.pull(loc["feaids"])
+                wp_, vp_ = oracle.get_pos(lens_d)
+                want = oracle.fm_predict(V_dim, loc["offset"], loc["index"], b["value"], vals_d, wp_, vp_)
+                w64b, V64b, _ = T.dense_rows(vals_d, lens_d, V_dim)
+                _, floor_v = T.predict_bound(D, w64b, V64b)
+                T.check(pv2, want, floor_v, "logits of the validation step, epoch %d" % epoch)
     # final model state, key by key: one step apart from identical state, so the last step's tolerance class
     allkeys = np.unique(np.concatenate([l["feaids"] for l in locs]))
     vg, lg = tb.pull(allkeys)
     vo, lo = so.pull(allkeys)
     assert np.array_equal(lg, lo)
     n_with_v = int(np.sum(lo > 1)) if V_dim else 0
-    _record_parity("fused_stepwise/k%d/%s/%d_batches_x_%d" % (V_dim, mode, len(batches), epochs),
+    _record_parity(record_as or "fused_stepwise/k%d/%s/%d_batches_x_%d" % (V_dim, mode, len(batches), epochs),
                    dict(worst_logit_err_over_tol=worst_pred, worst_state_err_over_tol=worst_state, steps=epochs * len(batches)))
+    if out is not None:
+        out["model"] = (vg, lg)
+        out["worst"] = (worst_pred, worst_state)
     if table is None:
         tb.close()
-    bt.close()
+    for bt_ in ([bt] if relocalize else bts):
+        bt_.close()
     return n_with_v
 
 
@@ -761,6 +815,285 @@ def test_fused_step_keys_in_every_row(capi, ctx, oracle, V_dim, binary):
     for a, b in zip(finals[0][0], finals[1][0]):
         assert np.array_equal(a, b)
     assert np.array_equal(finals[0][1][0], finals[1][1][0]) and np.array_equal(finals[0][1][1], finals[1][1][1])
+
+
+# ---- the update's split role (upd_split_role) wherever dfh_sgd_step can reach it
+HOT_KW = dict(l1=0.01, l2=0.0, lr=0.05, V_lr=0.02, V_l2=0.01, V_threshold=0, V_init_scale=0.1, seed=4)
+
+
+def _every_row_batches(rng, binary, n=2, nrows=6000):
+    """the generator of test_fused_step_keys_in_every_row: key 7 in every row, key 11 in 75 % of the rows"""
+    from split_testlib import hot_batch
+    return [hot_batch(rng, nrows, [(7, 1.1), (11, 0.75)], n_other=(2, 7), binary=binary) for _ in range(n)]
+
+
+@pytest.mark.parametrize("V_dim,binary,device_localize,cnt_every_step", [(8, False, True, True), (64, True, True, False),
+                                                                       (8, False, False, False), (64, True, False, True)])
+def test_split_keys_restepped_without_relocalize(capi, ctx, oracle, V_dim, binary, device_localize, cnt_every_step):
+    """a batch object that is localized ONCE and stepped in every epoch (later epochs of a worker loop that keeps its
+    minibatches on the device, every dfh_batch_load_localized_host user): each training step must start from an empty split
+    list.  Until the step emptied the list itself, every step after the first listed the very hot keys once more and
+    updated them once per copy (a race on the row: it could come out right by accident, which is why the LIST LENGTH is
+    asserted after every step, not just the numbers).  Two batch objects out of one allocation, three epochs each
+    (3 x 11 entries <= split_cap 96), device- and host-localized, with the count push in every step for half the cases
+    (kCountLater through the split apply).  Step by step against the oracle, and logits and model BIT FOR BIT those of a
+    run that localizes before every step: the role is deterministic by construction (part order, wave order)."""
+    rng = np.random.default_rng(33)
+    batches = _every_row_batches(rng, binary)
+    nnz_cap = max(int(b["offset"][-1]) for b in batches) + 4096
+    name = "split_restep/k%d/%s/%s" % (V_dim, "device" if device_localize else "host", "cnt" if cnt_every_step else "cnt0")
+    a, b = {}, {}
+    _run_fused_vs_oracle(capi, ctx, oracle, V_dim, "hash", batches, 3, HOT_KW, capacity=1 << 17, device_localize=device_localize,
+                         count_push_every_step=cnt_every_step, relocalize=False, batch_nnz=nnz_cap, record_as=name, out=a)
+    _run_fused_vs_oracle(capi, ctx, oracle, V_dim, "hash", batches, 3, HOT_KW, capacity=1 << 17, device_localize=device_localize,
+                         count_push_every_step=cnt_every_step, relocalize=True, batch_nnz=nnz_cap, record_as=name + "/relocalized", out=b)
+    assert len(a["preds"]) == len(b["preds"]) == 6
+    for x, y in zip(a["preds"], b["preds"]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a["model"][0], b["model"][0]) and np.array_equal(a["model"][1], b["model"][1])
+
+
+def test_split_list_worst_legal_shape(capi, ctx, oracle):
+    """as many segments of exactly 4 097 occurrences as a small batch object can hold and nothing else: the shape that lists
+    the most entries per pair (5 per 4 097; tests/test_split_list.py shows on the host that split_cap covers any partition).
+    The list holds exactly the host's count, the table's error word stays clean (lookup_split's clamp did not fire), and
+    the step matches the oracle"""
+    from split_testlib import split_cap, split_entries_expected
+    nrows, nkeys = 4097, 4
+    off = (np.arange(nrows + 1) * nkeys).astype(np.uint64)
+    idx = np.tile(np.array([3, 5, 9, 17], np.uint64), nrows)
+    rng = np.random.default_rng(4)
+    val = (rng.normal(size=len(idx)) * 0.3).astype(np.float32)
+    lab = np.where(rng.random(nrows) < 0.3, 1.0, -1.0).astype(np.float32)
+    b = dict(offset=off, index=idx, value=val, label=lab)
+    assert split_entries_expected([4097] * nkeys) == 20 <= split_cap(nrows * nkeys) == 48
+    tb = capi.Table(ctx, 1 << 10, V_dim=8, init_mode=capi.INIT_HASH, **HOT_KW)
+    _run_fused_vs_oracle(capi, ctx, oracle, 8, "hash", [b], 2, HOT_KW, table=tb, batch_nnz=nrows * nkeys,
+                         record_as="split_worst_shape/k8")   # (asserts the list length after both steps)
+    tb.check()
+    tb.close()
+
+
+def _boundary_batch(rng, binary=False):
+    """8 192 rows whose keys have segments of exactly 8 192 (8 parts), 5 120 (5 full parts), 4 097 (5 parts, the last of ONE
+    occurrence), 4 096 (stays whole in the hot role), 9 (mid role) occurrences, beside 1-2 ids a row from a space so large that most occur once"""
+    from split_testlib import hot_batch
+    return hot_batch(rng, 8192, [(21, 8192), (22, 5120), (23, 4097), (24, 4096), (25, 9)], n_other=(1, 3), id_lo=1000, id_hi=1 << 40,
+                     binary=binary)
+
+
+@pytest.mark.parametrize("upd_split", [1, 0])
+def test_split_boundaries_of_the_cut(capi, oracle, upd_split):
+    """segment lengths on both sides of every boundary of the cut in ONE minibatch, on a batch object that is stepped three
+    times with a validation step after each training step (the model must not move, the next training step must still be
+    right).  The same tolerance with the split role (18 entries a step) and with the ctx option upd_split = 0 (no entries:
+    the hot role walks the segments whole)"""
+    from split_testlib import split_entries_expected
+    rng = np.random.default_rng(12)
+    b = _boundary_batch(rng)
+    loc = oracle.localize(b["offset"], b["index"])
+    cnt = np.sort(loc["feacnt"])[::-1]
+    assert list(cnt[:5]) == [8192, 5120, 4097, 4096, 9] and cnt[5] <= 2 and split_entries_expected(loc["feacnt"]) == 18
+    c = capi.Context(0)
+    try:
+        c.set_option("upd_split", upd_split)
+        _run_fused_vs_oracle(capi, c, oracle, 8, "hash", [b], 3, HOT_KW, capacity=1 << 16, relocalize=False, upd_split=bool(upd_split),
+                             validate_between=True, count_push_every_step=True, batch_nnz=int(b["offset"][-1]) + 60000,
+                             record_as="split_boundaries/k8/upd_split%d" % upd_split)
+    finally:
+        c.close()
+
+
+INST_KW = dict(HOT_KW, V_threshold=6, l1=0.001)
+
+
+def _instantiation_batch(V_dim, binary):
+    """4 300 rows: key 7 in every row (split: five parts), key 11 in 90 % (hot role), 1-4 more ids a row out of 1 900, so that
+    the ordinary keys occur ~5 times a step.  With V_threshold = 6 and the count pushed in every step no key has its V in
+    step 0 (w is still 0 at the count push), and in step 1 the two hot keys and most of the others gain it: has_V of the
+    split key flips between two steps.
+    (Why the ordinary keys get their V too: with V on the two hot keys ONLY and binary features, the key's V gradient is a
+    sum of 4 300 terms that take ~250 distinct values.  The reference adds them serially in fp32 and its roundings are
+    then biased, not a random walk: ITS gradient is 2.2-2.8 x the floor of oracle/tolerance.py away from the fp64 value
+    (measured on the CPU, V_dim 128 and 256, binary), and the device, which adds in tiles, was found 1.5 x outside against
+    it.  With V on the ordinary keys the terms differ from row to row and the reference stays within 0.6 x the floor over all
+    twelve cases, 0.22 x on the two hot keys.)"""
+    from split_testlib import hot_batch
+    rng = np.random.default_rng(700 + V_dim + int(binary))
+    return hot_batch(rng, 4300, [(7, 4300), (11, 0.9)], n_other=(1, 5), id_lo=100, id_hi=2000, binary=binary)
+
+
+@pytest.mark.parametrize("V_dim", [0, 5, 8, 100, 128, 256])
+@pytest.mark.parametrize("binary", [False, True])
+def test_split_role_every_instantiation(capi, ctx, oracle, V_dim, binary):
+    """every k_update_fused instantiation the dispatch can pick, with a split key in the minibatch: V_dim 0 (no V: the lanes
+    beyond the header idle), 5 (kp 8, not EXACT), 8, 100 (not EXACT), 128, 256 (a full UPD_SPLIT_STRIDE row, the widest shared
+    tile); binary and valued (HAS_VAL); REFRAND init for V_dim 5 valued and 128 binary (need_init through the split apply);
+    V_threshold > 0, so that the split key gains its V during the run (_instantiation_batch)"""
+    batches = [_instantiation_batch(V_dim, binary)]
+    mode = "refrand" if (V_dim, binary) in ((5, False), (128, True)) else "hash"
+    out = {}
+    n_with_v = _run_fused_vs_oracle(capi, ctx, oracle, V_dim, mode, batches, 3, INST_KW, capacity=1 << 16, count_push_every_step=True,
+                                    record_as="split_instantiations/k%d/%s/%s" % (V_dim, "binary" if binary else "valued", mode), out=out)
+    assert (n_with_v > 500) if V_dim else (n_with_v == 0)
+    if V_dim:   # the split key is among them (it has a V block in the final pull), and had none when step 0 ran
+        loc = oracle.localize(batches[0]["offset"], batches[0]["index"])
+        u = int(np.argmax(loc["feacnt"]))
+        assert loc["feacnt"][u] == 4300 and out["model"][1][np.searchsorted(np.unique(loc["feaids"]), loc["feaids"][u])] == 1 + V_dim
+
+
+def _contended_batch(rng):
+    """5 000 rows, 12 ids in 84-100 % of them (every one beyond 4 096 occurrences: ~56 list entries) and 4 in 40-70 %"""
+    from split_testlib import hot_batch
+    hot = [(30 + i, float(f)) for i, f in enumerate(np.linspace(0.84, 1.01, 12))] + [(50 + i, f) for i, f in enumerate((0.4, 0.5, 0.6, 0.7))]
+    return hot_batch(rng, 5000, hot, n_other=(1, 4), id_lo=1000, id_hi=30000, binary=False)
+
+
+def test_split_role_deterministic_under_contention(capi, oracle):
+    """many split keys at once: with upd_hot_blocks = 8 each block takes ~7 parts in turn (the j += nblk iterations, the
+    barrier that keeps a part's shared sums until they are consumed), with the default every part has a block of its own and
+    which block brings a key's last part is a race.  Three runs of each are bit-identical to one another AND across the two
+    settings (the combine adds in part order, whoever comes last); tickets that did not return to zero or partials read
+    before they were written would show here.  One of the runs is also checked against the oracle step by step"""
+    from split_testlib import split_cap, split_entries_expected
+    rng = np.random.default_rng(71)
+    batches = [_contended_batch(rng) for _ in range(2)]
+    locs = [oracle.localize(b["offset"], b["index"]) for b in batches]
+    nlist = [split_entries_expected(l["feacnt"]) for l in locs]
+    nnz_cap = max(int(b["offset"][-1]) for b in batches) + 24000   # (room for three steps' entries even if no step emptied the list)
+    assert min(nlist) >= 40 and int(np.sum(locs[0]["feacnt"] > 4096)) == 12
+    assert 3 * max(nlist) <= split_cap(nnz_cap)
+    keys = np.unique(np.concatenate([l["feaids"] for l in locs]))
+    runs = []
+    for hot_blocks in (8, 8, 8, 512, 512, 512):
+        c = capi.Context(0)
+        c.set_option("upd_hot_blocks", hot_blocks)
+        tb = capi.Table(c, 1 << 16, V_dim=16, init_mode=capi.INIT_HASH, **HOT_KW)
+        bts = capi.create_batches(c, 2, 5000, nnz_cap)
+        for bt, b in zip(bts, batches):
+            bt.load_host(b["offset"], b["index"], b["value"], b["label"])
+            bt.localize()
+        preds = []
+        for ep in range(3):
+            for bt, n in zip(bts, nlist):
+                bt.sgd_step(tb, is_train=True, push_cnt=(ep == 0))
+                preds.append(bt.pred())
+                assert bt.split_entries() == n
+        tb.check()
+        runs.append((preds, tb.pull(keys)))
+        for o in bts + [tb]:
+            o.close()
+        c.close()
+    for preds, model in runs[1:]:
+        for x, y in zip(preds, runs[0][0]):
+            assert np.array_equal(x, y)
+        assert np.array_equal(model[0], runs[0][1][0]) and np.array_equal(model[1], runs[0][1][1])
+    c = capi.Context(0)
+    try:
+        c.set_option("upd_hot_blocks", 8)
+        _run_fused_vs_oracle(capi, c, oracle, 16, "hash", batches, 2, HOT_KW, capacity=1 << 16, relocalize=False, batch_nnz=nnz_cap,
+                             record_as="split_contention/k16/hot_blocks8")
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("nrows", [4300, 40000])   # below and beyond AUC_PAIRS_MAX_N = 32 768
+def test_split_keys_with_auc_riding_in_the_update(capi, oracle, nrows):
+    """compute_auc with split keys in the minibatch: below the pair-counting size the AUC blocks ride in front of the split
+    role's blocks in the update launch, above it the AUC is a launch of its own.  AUC against the oracle as
+    test_fused_step_auc does, the list length after every step, and the model bit for bit that of a run without the AUC"""
+    from split_testlib import hot_batch, split_entries_expected
+    rng = np.random.default_rng(90 + nrows)
+    b = hot_batch(rng, nrows, [(7, 1.1), (11, 0.5)], n_other=(1, 4), id_hi=30000, binary=False)
+    loc = oracle.localize(b["offset"], b["index"])
+    nlist = split_entries_expected(loc["feacnt"])
+    assert nlist >= 5
+    models = []
+    for auc in (1, 0):
+        c = capi.Context(0)
+        tb = capi.Table(c, 1 << 16, V_dim=8, init_mode=capi.INIT_HASH, **HOT_KW)
+        bt = capi.Batch(c, nrows, int(b["offset"][-1]))
+        bt.set_option("compute_auc", auc)
+        bt.load_host(b["offset"], b["index"], b["value"], b["label"])
+        bt.localize()
+        checked = 0
+        for step in range(3):
+            bt.sgd_step(tb, is_train=True, push_cnt=(step == 0))
+            assert bt.split_entries() == nlist
+            pred = bt.pred()
+            prog = bt.progress(reset=True)
+            if not auc:
+                continue
+            # the definition (bin_class_metric.h:35-56) in exact arithmetic, ties by index; the oracle where no logits tie
+            lab = (b["label"] > 0)[np.lexsort((np.arange(nrows), pred))]
+            area, tp = float(np.sum(np.cumsum(lab)[~lab])), float(lab.sum())
+            a = area / (tp * (nrows - tp))
+            assert prog.auc == pytest.approx((1 - a if a < 0.5 else a) * nrows, rel=3e-7)
+            if len(np.unique(pred)) == len(pred):
+                assert prog.auc == pytest.approx(oracle.auc_times_n(b["label"], pred), rel=1e-5)
+                checked += 1
+        # (40 000 fp32 logits: some coincide, the exact check above covers those steps)
+        assert checked >= 2 or not auc or nrows > 10000
+        tb.check()
+        models.append(tb.pull(loc["feaids"]))
+        for o in (bt, tb):
+            o.close()
+        c.close()
+    assert np.array_equal(models[0][0], models[1][0]) and np.array_equal(models[0][1], models[1][1])
+
+
+@pytest.mark.parametrize("streams,prep_lookup", [(1, True), (2, False), (2, "fused")])
+def test_split_keys_pipelined_prep_matches_serial(capi, oracle, streams, prep_lookup):
+    """the preparation pipeline (dfh_ctx_set_pipeline) with split keys: the Localizer, and with prep_lookup the key probe, of
+    the next minibatch run on a preparation stream while this one steps, so the step's own k_lookup_step runs with
+    rows_known and still has to list the parts.  Logits of every step and the model bit for bit the serial run's"""
+    from split_testlib import hot_batch, split_entries_expected
+    rng = np.random.default_rng(314)
+    batches = [hot_batch(rng, 4300, [(7, 1.1), (11, 0.97)], n_other=(1, 5), id_hi=30000, binary=(i == 1)) for i in range(3)]
+    locs = [oracle.localize(b["offset"], b["index"]) for b in batches]
+    nlist = [split_entries_expected(l["feacnt"]) for l in locs]
+    assert min(nlist) >= 10
+    keys = np.unique(np.concatenate([l["feaids"] for l in locs]))
+    max_nnz = max(int(b["offset"][-1]) for b in batches)
+    nsteps = 7
+
+    def run(pipelined):
+        c = capi.Context(0)
+        if pipelined:
+            c.set_pipeline(streams)
+        tb = capi.Table(c, 1 << 17, V_dim=8, init_mode=capi.INIT_HASH, **HOT_KW)
+        bts = [capi.Batch(c, 4300, max_nnz) for _ in range(2)]
+
+        def prep(i):
+            b, bt = batches[i % 3], bts[i % 2]
+            bt.load_host(b["offset"], b["index"], b["value"], b["label"])
+            if pipelined and prep_lookup == "fused":
+                bt.localize(table=tb)
+            else:
+                bt.localize()
+                if pipelined and prep_lookup:
+                    bt.lookup(tb)
+
+        preds = []
+        prep(0)
+        for i in range(nsteps):
+            if i + 1 < nsteps:
+                prep(i + 1)
+            bt = bts[i % 2]
+            bt.sgd_step(tb, is_train=True, push_cnt=(i < 3))
+            preds.append(bt.pred())
+            assert bt.split_entries() == nlist[i % 3]
+        tb.check()
+        model = tb.pull(keys)
+        for o in bts + [tb]:
+            o.close()
+        c.close()
+        return preds, model
+
+    ref, got = run(False), run(True)
+    for x, y in zip(got[0], ref[0]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(got[1][0], ref[1][0]) and np.array_equal(got[1][1], ref[1][1])
 
 
 SGD_BASIC = [69.314718, 69.314718, 67.151912, 61.414778, 56.244989, 53.218700, 51.248737, 49.846688,

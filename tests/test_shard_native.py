@@ -28,7 +28,20 @@ ROWS = 300
 PUSH_CNT_STEPS = 2
 
 
+SHAPE = "mixed"     # "hot": minibatches of HOT_ROWS rows with two keys beyond 4 096 occurrences (the update's split role)
+HOT_ROWS = 4500
+HOT_IDS = (7, 8)    # ReverseBytes puts an id's low nibble on top: key 0x70.. is rank 0's under the uniform split of 2, 0x80.. rank 1's
+RESTEP = False      # hot shape: the LAST minibatch of every rank is stepped twice without a localize in between
+EXACT_GRADS = False  # emulate / emulate_overlap: push the fp64 value of every gradient (rounded once) instead of FMLoss::CalcGrad's
+
+
+def rows():
+    return HOT_ROWS if SHAPE == "hot" else ROWS
+
+
 def nsteps(rank):
+    if SHAPE == "hot":
+        return 3 - (rank % 2) + (1 if RESTEP else 0)  # ranks 0, 2: three minibatches; ranks 1, 3: two (+ the last one again)
     return 5 - (rank % 2) * 2  # ranks 0, 2: five minibatches; ranks 1, 3: three
 
 
@@ -45,9 +58,33 @@ DENSE_IDS = False   # the overlapped-exchange cases: every step draws from the s
 
 def make_batches(rank):
     from conftest import random_batch
+    if SHAPE == "hot":
+        # a fresh minibatch every step: HOT_IDS[0] in every row, HOT_IDS[1] in 95 % of the rows, 1-2 more ids a row
+        from split_testlib import hot_batch
+        rng = np.random.default_rng(1900 + rank)
+        bs = [hot_batch(rng, HOT_ROWS, [(HOT_IDS[0], 1.1), (HOT_IDS[1], 0.95)], n_other=(1, 3), id_lo=1000, id_hi=60000,
+                        binary=(i % 2 == 0)) for i in range(nsteps(rank) - (1 if RESTEP else 0))]
+        return bs + bs[-1:] if RESTEP else bs
     rng = np.random.default_rng(900 + rank)
     return [random_batch(rng, ROWS, 2 ** 64 - 1 if (i % 2 and not DENSE_IDS) else 3000, 30, binary=(i % 2 == 0))
             for i in range(nsteps(rank))]
+
+
+def calc_grad(oracle, V_dim, loc, b, vals, lens, p, wp, vp):
+    """FMLoss::CalcGrad of the oracle (fp32, serial sums), or with EXACT_GRADS the same gradient evaluated in fp64
+    (oracle/tolerance.py) and rounded once: the two emulations differ by the reference's OWN summation rounding, carried
+    through every later step"""
+    if not EXACT_GRADS:
+        return oracle.fm_calcgrad(V_dim, loc["offset"], loc["index"], b["value"], b["label"], vals, p, wp, vp)
+    from oracle import tolerance as T
+    w64, V64, has = T.dense_rows(vals, lens, V_dim)
+    gw, gV, _, _ = T.calcgrad_bound(T.design(loc["offset"], loc["index"], b["value"], loc["U"]), b["label"], p, w64, V64, has)
+    out = np.zeros(int(np.sum(lens)), np.float32)
+    begs = np.cumsum(lens) - lens
+    out[begs] = gw
+    for u in np.flatnonzero(has):
+        out[begs[u] + 1:begs[u] + 1 + V_dim] = gV[u]
+    return out
 
 
 def subset_push(store, kind, keys, grads, lens, mask):
@@ -87,7 +124,7 @@ def emulate(oracle, batches, V_dim, hyper, splits, rec=None):
             p = oracle.fm_predict(V_dim, loc["offset"], loc["index"], b["value"], vals, wp, vp)
             preds[r].append(p)
             loss[r] += oracle.loss_evaluate(b["label"], p)
-            grads[r] = oracle.fm_calcgrad(V_dim, loc["offset"], loc["index"], b["value"], b["label"], vals, p, wp, vp)
+            grads[r] = calc_grad(oracle, V_dim, loc, b, vals, lens, p, wp, vp)
         owner = {r: sharded.owner_of(locs[r]["feaids"], splits) for r in act}
         if rec is not None:
             rec.append(dict(locs=locs, pulled=pulled, grads=grads))
@@ -162,7 +199,7 @@ def emulate_overlap(oracle, batches, V_dim, hyper, splits, rec=None):
             p = oracle.fm_predict(V_dim, l["offset"], l["index"], b["value"], vals, wp, vp)
             preds[r].append(p)
             loss[r] += oracle.loss_evaluate(b["label"], p)
-            grads[r] = oracle.fm_calcgrad(V_dim, l["offset"], l["index"], b["value"], b["label"], vals, p, wp, vp)
+            grads[r] = calc_grad(oracle, V_dim, l, b, vals, lens, p, wp, vp)
             lens_of[r] = lens
             if rec is not None:
                 if len(rec) <= i:
@@ -177,9 +214,10 @@ def emulate_overlap(oracle, batches, V_dim, hyper, splits, rec=None):
     return store, preds, loss
 
 
-def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
-    global DENSE_IDS
+def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync", shape="mixed", mixed_update=1, restep=False):
+    global DENSE_IDS, SHAPE, RESTEP
     DENSE_IDS = mode == "overlap"
+    SHAPE, RESTEP = shape, restep
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -188,6 +226,7 @@ def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
     from difacto_amd import capi, sharded
     from difacto_amd.synth import reverse_bytes_np
     ctx = capi.Context(0)
+    ctx.set_option("shard_mixed_update", mixed_update)
 
     def exchange(send, sb, recv, rb):  # bytes in, bytes out: gloo all_to_all_v on the host
         out = torch.empty(sum(rb), dtype=torch.uint8)
@@ -213,10 +252,17 @@ def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
         sh.set_exchange("overlap")   # two minibatches in flight: needs the next one announced (prefetch)
         sh.set_timing(True)
     if balanced:   # exchange buffers up front (dfh_shard_reserve: no re-allocation inside a step); the other cases let them grow
-        sh.reserve(ROWS * 30, 2 * ROWS * 30 * world)
+        sh.reserve(rows() * 30, 2 * rows() * 30 * world)
     batches = make_batches(rank)
     max_nnz = max(int(b["offset"][-1]) for b in batches)
-    bts = [capi.Batch(ctx, ROWS, max_nnz) for _ in range(2)]
+    bts = [capi.Batch(ctx, rows(), max_nnz) for _ in range(2)]
+    want_split = None
+    if shape == "hot":   # entries a training step must leave on the split list: the parts of BOTH hot keys, own and remote
+        from oracle import bindings as ob_
+        from split_testlib import split_cap, split_entries_expected
+        o_ = ob_.Oracle()
+        want_split = [split_entries_expected(o_.localize(b["offset"], b["index"])["feacnt"]) for b in batches]
+        assert min(want_split) == 10 and 2 * max(want_split) <= split_cap(max_nnz)
     bt = bts[0]
     if prefetch:
         ctx.set_pipeline(1)   # the next minibatch is localized on the preparation stream while this one steps
@@ -224,6 +270,8 @@ def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
     def prepare(j):
         if j >= len(batches):
             return None
+        if restep and j == len(batches) - 1:   # the same localized batch object once more (sync, no prefetch: it is bts[(j - 1) % 2])
+            return bts[(j - 1) % 2]
         b = batches[j]
         bts[j % 2].load_host(b["offset"], b["index"], b["value"], b["label"])
         bts[j % 2].localize()
@@ -241,6 +289,8 @@ def _worker(rank, world, port, out_dir, balanced, prefetch, mode="sync"):
             break
         if cur is not None:
             preds.append(cur.pred().copy())
+            if want_split is not None:
+                assert cur.split_entries() == want_split[i], (rank, i, cur.split_entries(), want_split[i])
         i += 1
         cur = nxt if prefetch else prepare(i)
     assert i == max(nsteps(r) for r in range(world))
@@ -323,10 +373,100 @@ def test_shard_step_ranks_share_one_gpu(tmp_path, oracle, WORLD, balanced, prefe
 
 
 @pytest.mark.gpu
-def test_shard_step_world1_over_rccl_matches_fused():
+# (no more than six processes on the GPU at once: the widest case runs 4 ranks beside the test process)
+@pytest.mark.parametrize("WORLD,balanced,prefetch,exchange,mixed_update,restep", [
+    (2, False, False, "sync", 1, False),      # k_lookup_step (u_base = own_lo) + k_uw_remote, k_update_fused<MIXED>
+    (2, False, True, "overlap", 1, False),    # k_lookup_uw_remote from the second step on
+    (4, True, False, "sync", 1, False),
+    (2, False, False, "sync", 0, False),      # two launches: the own keys' one must skip the others' entries, tickets stay zero
+    (2, False, False, "sync", 1, True),       # the same localized batch object stepped twice
+])
+def test_shard_step_hot_keys_split_role(tmp_path, oracle, WORLD, balanced, prefetch, exchange, mixed_update, restep):
+    """the sharded step with keys beyond 4 096 occurrences (data shape `hot`: 4 500 rows per rank and step, HOT_IDS[0] in every
+    row, HOT_IDS[1] in 95 %, a fresh minibatch every step, 3 steps on even ranks and 2 on odd): both launches that see a
+    step's keys append to ONE split list — the own keys' lookup with u_base = own_lo, the others' row words with u_base = 0 —
+    which the step empties first.  Every rank asserts after every step that its list holds exactly the parts of both hot
+    keys (a list that is not emptied, or emptied between the two launches, shows there), and the table's error word is clean.
+
+    Numbers: against the one-store emulation, as the other cases of this file.  Their fixed tolerances (rtol 1e-5 / 2e-5,
+    atol 1e-6) were chosen for 300-row sums; for this shape the REFERENCE ALONE was measured on the CPU first (world 2,
+    sync, uniform): its fp32 logits are within 0.02 x (rtol 1e-5 + atol 1e-6) of fp64, but its pushed gradients of the hot
+    keys — serial fp32 sums of ~4 500 terms that cancel to a tenth of their magnitude — are up to 26 x that away from the
+    fp64 value, and a hot key's model entries after ONE update from identical state up to 2.2 x (rtol 2e-5 + atol 1e-6).
+    The reference's own rounding does not fit the fixed tolerance, so this shape adds the reference's own error to it,
+    carried through all steps: the emulation is run a second time with every gradient evaluated in fp64 and rounded once
+    (EXACT_GRADS), and a quantity may differ from the fp32 emulation by the fixed tolerance plus TWICE the largest
+    difference between the two emulations over its group (a step's logits of one rank; one key's entries) — once for the
+    reference's rounding, once for the device's, whose tiled sums of the same terms round no worse than serial ones.  The
+    existing shapes keep the fixed tolerances."""
+    global DENSE_IDS, SHAPE, RESTEP, EXACT_GRADS
+    from difacto_amd import sharded
+    from difacto_amd.synth import reverse_bytes_np
+    port = 29500 + (os.getpid() % 60) + WORLD + (10 if prefetch else 0) + (20 if restep else 0) + (30 if not mixed_update else 0)
+    try:
+        SHAPE, RESTEP, DENSE_IDS = "hot", restep, exchange == "overlap"
+        batches = [make_batches(r) for r in range(WORLD)]
+        if balanced:
+            splits = sharded.balanced_splits(reverse_bytes_np(np.concatenate([b["index"] for r in range(WORLD) for b in batches[r]])), WORLD)
+        else:
+            splits = sharded.uniform_splits(WORLD)
+        # the configuration really has a split key that is its rank's OWN and one that is REMOTE to its rank
+        own_split = remote_split = False
+        for r in range(WORLD):
+            for b in batches[r]:
+                loc = oracle.localize(b["offset"], b["index"])
+                hot = loc["feaids"][loc["feacnt"] > 4096]
+                assert len(hot) == 2
+                owner = sharded.owner_of(hot, splits)
+                own_split |= bool(np.any(owner == r)) and r > 0   # (a rank whose own_lo > 0 lists an own split key)
+                remote_split |= bool(np.any(owner != r))
+        assert own_split and remote_split
+        if WORLD == 2 and not balanced:
+            assert list(sharded.owner_of(reverse_bytes_np(np.array(HOT_IDS, np.uint64)), splits)) == [0, 1]
+        mp.spawn(_worker, args=(WORLD, port, str(tmp_path), balanced, prefetch, exchange, "hot", mixed_update, restep), nprocs=WORLD, join=True)
+        emu = emulate_overlap if exchange == "overlap" else emulate
+        store, preds, loss = emu(oracle, batches, V_DIM, HYPER, splits)
+        EXACT_GRADS = True
+        store64, preds64, _ = emu(oracle, batches, V_DIM, HYPER, splits)
+        EXACT_GRADS = False
+        total = 0
+        for r in range(WORLD):
+            got = np.load(os.path.join(tmp_path, "rank%d.npz" % r))
+            gp = got["preds"].reshape(nsteps(r), HOT_ROWS)
+            for i in range(nsteps(r)):
+                own_err = 2 * float(np.abs(preds[r][i].astype(np.float64) - preds64[r][i]).max())
+                tol = 1e-5 * np.abs(preds[r][i]) + 1e-6 + own_err
+                err = np.abs(gp[i].astype(np.float64) - preds[r][i])
+                assert np.all(err <= tol), "rank %d step %d logits: worst err / tol %.3g (the reference's own error part %.3g)" % (
+                    r, i, (err / tol).max(), own_err)
+            assert float(got["loss"]) == pytest.approx(loss[r], rel=1e-5)
+            assert float(got["nrows"]) == HOT_ROWS * nsteps(r)
+            vals, lens = store.pull(got["keys"])
+            vals64, lens64 = store64.pull(got["keys"])
+            assert np.array_equal(got["lens"], lens) and np.array_equal(lens64, lens)
+            ends = np.cumsum(lens)
+            own_err = 2 * np.maximum.reduceat(np.abs(vals.astype(np.float64) - vals64), ends - lens)
+            tol = 2e-5 * np.abs(vals) + 1e-6 + np.repeat(own_err, lens)
+            err = np.abs(got["vals"].astype(np.float64) - vals)
+            assert np.all(err <= tol), "rank %d owned model: worst err / tol %.3g at entry %d" % (r, (err / tol).max(), int((err / tol).argmax()))
+            assert np.any(lens > 1)
+            total += int(got["nkeys"])
+        assert total == store.size()
+    finally:
+        SHAPE, RESTEP, DENSE_IDS, EXACT_GRADS = "mixed", False, False, False
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["mixed", "hot"])
+def test_shard_step_world1_over_rccl_matches_fused(shape):
     """one rank over the real transport (RCCL loaded at run time): every key is the rank's own, so the step
     is the fused step (k_lookup -> k_forward<MIXED> on the table -> k_backward_all with the in-place
-    update) and must give what dfh_sgd_step gives"""
+    update) and must give what dfh_sgd_step gives.
+    shape `hot`: minibatches with two keys beyond 4 096 occurrences (u_base = 0, the lookup clamps to *d_U): with one rank
+    dfh_shard_step makes the launches of dfh_sgd_step with the same arguments but the key range (all keys either way) — the
+    same k_lookup_step with the same count-push mode, the same forward, the same k_update_fused on the same lists, no AUC
+    on either side — so logits and model must be BIT-identical, and the split list as long.  (The `mixed` shape keeps the
+    tolerances it had.)"""
     from conftest import random_batch
     from difacto_amd import capi
     ctx = capi.Context(0)
@@ -337,12 +477,18 @@ def test_shard_step_world1_over_rccl_matches_fused():
     assert info.startswith("rccl ") and "librccl" in info and int(info.split()[1]) > 20000, info
     kw = dict(l1=0.02, l2=0.01, lr=0.3, V_lr=0.05, V_l2=0.02, V_threshold=0, V_init_scale=0.2, seed=2)
     rng = np.random.default_rng(77)
-    batches = [random_batch(rng, 200, 4000, 25, binary=(i == 1)) for i in range(3)]
+    if shape == "hot":
+        from split_testlib import hot_batch
+        batches = [hot_batch(rng, HOT_ROWS, [(HOT_IDS[0], 1.1), (HOT_IDS[1], 0.95)], n_other=(1, 4), id_lo=1000, id_hi=30000,
+                             binary=(i == 1)) for i in range(3)]
+    else:
+        batches = [random_batch(rng, 200, 4000, 25, binary=(i == 1)) for i in range(3)]
+    nrows = max(len(b["label"]) for b in batches)
     ta = capi.Table(ctx, 1 << 15, V_dim=16, **kw)
     tb = capi.Table(ctx, 1 << 15, V_dim=16, **kw)
     sh = capi.Shard(tb, comm)
     max_nnz = max(int(b["offset"][-1]) for b in batches)
-    ba, bb = capi.Batch(ctx, 200, max_nnz), capi.Batch(ctx, 200, max_nnz)
+    ba, bb = capi.Batch(ctx, nrows, max_nnz), capi.Batch(ctx, nrows, max_nnz)
     for epoch in range(2):
         for b in batches:
             for bt in (ba, bb):
@@ -351,6 +497,9 @@ def test_shard_step_world1_over_rccl_matches_fused():
             ba.sgd_step(ta, is_train=True, push_cnt=(epoch == 0))
             assert sh.step(bb, is_train=True, push_cnt=(epoch == 0))
             np.testing.assert_allclose(bb.pred(), ba.pred(), rtol=1e-5, atol=1e-6)
+            if shape == "hot":
+                assert np.array_equal(bb.pred(), ba.pred())
+                assert bb.split_entries() == ba.split_entries() == 10
             pa, pb = ba.progress(), bb.progress()
             assert pb.loss == pytest.approx(pa.loss, rel=1e-6) and pb.penalty == pytest.approx(pa.penalty, rel=1e-5)
     assert not sh.step(None)  # nobody has data: the epoch is over
@@ -359,6 +508,8 @@ def test_shard_step_world1_over_rccl_matches_fused():
     assert np.array_equal(ea["keys"][oa], eb["keys"][ob_]) and np.array_equal(ea["has_V"][oa], eb["has_V"][ob_])
     np.testing.assert_allclose(eb["scal"][ob_], ea["scal"][oa], rtol=2e-5, atol=1e-6)
     np.testing.assert_allclose(eb["V"][ob_], ea["V"][oa], rtol=2e-5, atol=1e-6)
+    if shape == "hot":
+        assert np.array_equal(eb["scal"][ob_], ea["scal"][oa]) and np.array_equal(eb["V"][ob_], ea["V"][oa])
     assert comm.allreduce_sum([1.5, 2.0]).tolist() == [1.5, 2.0]
     sent, recv, groups = comm.stats()
     assert sent == 0 and recv == 0 and groups > 0   # one rank: nothing leaves it, the exchanges still ran

@@ -48,7 +48,7 @@ POLICIES = [
 ]
 
 
-def run_stream(capi, batches, kw, V_dim, max_rows, single, opts, ahead, nsteps, is_train_of, inspect_every=0):
+def run_stream(capi, batches, kw, V_dim, max_rows, single, opts, ahead, nsteps, is_train_of, inspect_every=0, want_split=None):
     ctx = capi.Context(0)
     if single:
         ctx.set_option("single_queue", 1)
@@ -78,6 +78,8 @@ def run_stream(capi, batches, kw, V_dim, max_rows, single, opts, ahead, nsteps, 
             locs.append(bt.get_localized())      # a consumer other than the step: the stages still noted are queued first
         bt.sgd_step(tb, is_train=is_train_of(i), push_cnt=(i < len(batches)))
         preds.append(bt.pred())
+        if want_split is not None and is_train_of(i):   # entries of the split list the training step left (k_lookup_riders carries it)
+            assert bt.split_entries() == want_split[i % len(batches)], "step %d" % i
     prog = [b_.progress(reset=True) for b_ in bts]
     tot = (sum(p.loss for p in prog), sum(p.auc for p in prog), sum(p.penalty for p in prog), sum(p.nrows for p in prog))
     keys = np.unique(np.concatenate([capi.reverse_bytes_np(b["index"]) if hasattr(capi, "reverse_bytes_np") else
@@ -123,6 +125,28 @@ def test_single_queue_bit_identical_to_serial(capi, opts, ahead):
     train = lambda i: i % 7 != 6   # a validation step now and then: its launches carry riders too (or the stages run alone)
     ref = run_stream(capi, batches, kw, 8, 1500, False, {}, 1, nsteps, train)
     got = run_stream(capi, batches, kw, 8, 1500, True, opts, ahead, nsteps, train)
+    _same(got[0], ref[0], "pred")
+    _sums(got[2], ref[2])
+    _same(list(got[3]), list(ref[3]), "model")
+
+
+@pytest.mark.parametrize("opts,ahead", [POLICIES[0], POLICIES[3], POLICIES[6]])
+def test_single_queue_with_split_keys(capi, oracle, opts, ahead):
+    """minibatches of 4 300 rows with a key in EVERY row and one in 97 % of them (segments beyond 4 096 occurrences): in the
+    single-queue step k_lookup_riders lists their parts and the riders share the update launch with the split role's
+    blocks.  Every training step leaves exactly the minibatch's parts on the list; logits, progress sums and the model bit
+    for bit the serial step's"""
+    from split_testlib import hot_batch, split_entries_expected
+    rng = np.random.default_rng(19)
+    batches = [hot_batch(rng, 4300, [(7, 1.1), (11, 0.97)], n_other=(2, 6), id_hi=60000, binary=(i % 2 == 0), labels01=True)
+               for i in range(4)]
+    want = [split_entries_expected(oracle.localize(b["offset"], b["index"])["feacnt"]) for b in batches]
+    assert min(want) == 10
+    kw = dict(l1=0.01, l2=0.0, lr=0.05, V_lr=0.02, V_l2=0.01, V_threshold=0, V_init_scale=0.1, seed=4)
+    nsteps = 13
+    train = lambda i: i % 6 != 5
+    ref = run_stream(capi, batches, kw, 8, 4300, False, {}, 1, nsteps, train, want_split=want)
+    got = run_stream(capi, batches, kw, 8, 4300, True, opts, ahead, nsteps, train, want_split=want)
     _same(got[0], ref[0], "pred")
     _sums(got[2], ref[2])
     _same(list(got[3]), list(ref[3]), "model")
