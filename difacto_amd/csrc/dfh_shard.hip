@@ -21,6 +21,10 @@
 // A key's pushes are applied owner first, then the other sources in ascending rank order — one legal
 // execution of the reference's asynchronous Push protocol, the same on every run.  With one rank
 // nothing is exchanged and nothing waits for the host: the step is dfh_sgd_step.
+// Every stage is one function of the minibatch's Flight (flight_L, flight_K, flight_R, flight_RW, flight_F, flight_G,
+// flight_P); the two exchange modes are two schedules over them: shard_step_sync (every stage on the context's stream, one
+// minibatch at a time in exchange slot 0) and shard_step_overlap (K, RW, G on a collectives' stream, two minibatches in
+// flight in alternating slots, events between the stages).
 // Zero staleness: every minibatch reads the model all earlier ones have updated.  No all-reduce:
 // the traffic is key-routed rows, an all-to-all that uses every xGMI link of a GPU at once.
 //
@@ -36,6 +40,7 @@
 
 #include <chrono>
 #include <deque>
+#include <optional>
 #include <thread>
 
 namespace dfh {
@@ -212,8 +217,8 @@ struct dfh_shard {
   int64_t* d_bounds = nullptr;          // [world+1]
   int64_t* d_cnt = nullptr;             // [2][2*world]: what I send every peer / what every peer sends me
   int64_t* h_cnt = nullptr;             // pinned copy
-  // Two sets of exchange buffers: the sync step uses set 0; the overlapped step (two minibatches in flight)
-  // alternates, one set per minibatch under way.
+  // Two sets of exchange buffers (slots): the sync schedule uses set 0 and so do the literal host calls; the overlap
+  // schedule (two minibatches in flight) alternates, one set per minibatch under way.  Sized by slot_bufs alone.
   // owner side, sized to the keys received in a step
   uint64_t* r_keys[2] = {nullptr, nullptr};
   float* r_cnt[2] = {nullptr, nullptr};
@@ -225,6 +230,7 @@ struct dfh_shard {
   size_t w_cap[2] = {0, 0};
   float* w_grads[2] = {nullptr, nullptr};
   size_t g_cap[2] = {0, 0};
+  std::vector<size_t> xsb, xrb, xso;    // bytes per peer of the exchange being queued (flight_bytes)
   uint64_t steps = 0;
   // counts of the FOLLOWING step, exchanged inside the current one (dfh_shard_prefetch_counts)
   dfh_batch* next_b = nullptr;
@@ -241,7 +247,7 @@ struct dfh_shard {
   // r_keys[q] / r_cnt[q] waits for it (P reads r_keys / r_rowid / r_rows on the main stream; K writes on the collectives')
   hipEvent_t ev_p[2] = {nullptr, nullptr};
   bool p_pending[2] = {false, false};
-  struct Flight {                     // one minibatch on its way through the stages
+  struct Flight {                     // one minibatch on its way through the stages (flight_L ... flight_P)
     dfh_batch* b = nullptr;           // NULL: this rank has no minibatch in that step (it still serves its shard)
     bool described = false;           // the counts exchange is through: the sizes below are valid
     bool pulled = false;              // K, R, RW are queued: the other owners' rows are on their way to w_rows[slot]
@@ -253,7 +259,9 @@ struct dfh_shard {
     int slot = 0;
     bool listed = false;              // R left the key lists of the per-key owner side: P runs over them
   } fl[2];
-  int cur = 0;                        // fl[cur]: the minibatch the next step trains; fl[cur ^ 1]: the one after
+  // overlap: fl[cur] is the minibatch the next step trains, fl[cur ^ 1] the one after.  The sync schedule describes its one
+  // minibatch in fl[0] and never marks it pulled.
+  int cur = 0;
   // ---- per-stage timing (dfh_shard_set_timing): counts, L, K, R, RW, F, G, P
   bool timing = false;
   struct Span { int id; hipEvent_t a, b; };
@@ -835,6 +843,8 @@ int dfh_shard_owned_range(dfh_shard* s, const uint64_t* splits, uint64_t* key_lo
 }  // extern "C"
 
 namespace {
+using Flight = dfh_shard::Flight;
+
 // queue, on the main stream: owner ranges of b's keys -> {keys for every owner, "I have a minibatch"} ->
 // every peer -> pinned host memory
 int queue_counts(dfh_shard* s, dfh_batch* b, hipStream_t on = nullptr) {
@@ -885,8 +895,23 @@ struct StageScope {
   }
 };
 
+// ---- The stages of a step (the table in the header of this file), each written once as a function of the minibatch's
+// Flight.  dfh_shard_step is one of two SCHEDULES over them, shard_step_sync and shard_step_overlap: a schedule decides
+// whether a stage runs, on which stream an exchange (K, RW, G) is queued — L, R, F and P launch the table's and the batch's
+// kernels, which run on the context's stream — and which events order the stages.  The events are the overlap schedule's:
+// a stage waits for the ones it is handed inside its timing bracket, before its work, and records `done` behind it; the
+// sync schedule hands none.
+inline int wait_on(hipStream_t st, hipEvent_t e) {
+  if (e) DFH_HIP(hipStreamWaitEvent(st, e, 0));
+  return DFH_OK;
+}
+inline int record_on(hipStream_t st, hipEvent_t e) {
+  if (e) DFH_HIP(hipEventRecord(e, st));
+  return DFH_OK;
+}
+
 // sizes of a minibatch's exchange from the counts that have arrived in h_cnt
-void flight_sizes(dfh_shard* s, dfh_shard::Flight& f, dfh_batch* b, int slot) {
+void flight_sizes(dfh_shard* s, Flight& f, dfh_batch* b, int slot) {
   const int W = s->c->world, me = s->c->rank;
   f.b = b;
   f.have = b != nullptr && b->nnz > 0;
@@ -895,19 +920,27 @@ void flight_sizes(dfh_shard* s, dfh_shard::Flight& f, dfh_batch* b, int slot) {
   f.seg.assign(W + 1, 0);
   f.off.assign(W + 1, 0);
   f.active = 0;
-  for (int p = 0; p < W; ++p) {
-    f.send[p] = (size_t)s->h_cnt[2 * p];
-    f.recv[p] = (size_t)s->h_cnt[2 * W + 2 * p];
-    f.active += s->h_cnt[2 * W + 2 * p + 1] != 0 ? 1 : 0;
-    f.off[p + 1] = f.off[p] + f.send[p];  // owner p's keys are ranks [off[p], off[p+1]) of the minibatch's key list
-  }
-  f.own_lo = (uint32_t)f.off[me];
-  f.own_hi = (uint32_t)f.off[me + 1];
-  f.send[me] = f.recv[me] = 0;  // the rank's own keys are not exchanged
   f.nrecv = 0;
-  for (int p = 0; p < W; ++p) {
-    f.nrecv += f.recv[p];
-    f.seg[p + 1] = f.seg[p] + f.recv[p];
+  if (W == 1) {
+    // one rank: there are no counts.  Every key is its own, and how many there are stays on the device (b->d_U): the
+    // own range is open-ended (the kernels clamp to *d_U) and U is not known here
+    f.active = b != nullptr ? 1 : 0;
+    f.own_lo = 0;
+    f.own_hi = 0xFFFFFFFFu;
+  } else {
+    for (int p = 0; p < W; ++p) {
+      f.send[p] = (size_t)s->h_cnt[2 * p];
+      f.recv[p] = (size_t)s->h_cnt[2 * W + 2 * p];
+      f.active += s->h_cnt[2 * W + 2 * p + 1] != 0 ? 1 : 0;
+      f.off[p + 1] = f.off[p] + f.send[p];  // owner p's keys are ranks [off[p], off[p+1]) of the minibatch's key list
+    }
+    f.own_lo = (uint32_t)f.off[me];
+    f.own_hi = (uint32_t)f.off[me + 1];
+    f.send[me] = f.recv[me] = 0;  // the rank's own keys are not exchanged
+    for (int p = 0; p < W; ++p) {
+      f.nrecv += f.recv[p];
+      f.seg[p + 1] = f.seg[p] + f.recv[p];
+    }
   }
   f.U = f.off[W];
   f.any_own = f.have && f.own_hi > f.own_lo;
@@ -917,34 +950,54 @@ void flight_sizes(dfh_shard* s, dfh_shard::Flight& f, dfh_batch* b, int slot) {
   f.slot = slot;
 }
 
-// the exchange buffers of a flight's slot (growing one waits for everything queued: rare)
-int flight_bufs(dfh_shard* s, const dfh_shard::Flight& f, size_t stride) {
-  const int q = f.slot;
-  int rc;
+// The one place a slot's exchange buffers are sized: the owner side for r_need received keys, the worker side for the
+// pulled rows of w_need keys and the gradient rows of g_need keys (0: not needed).  slack: the growth policy of a step,
+// 1.5x + 1024 (dfh_shard_reserve asks for exact sizes).  Growing waits for everything queued on every stream: rare.
+int slot_bufs(dfh_shard* s, int q, size_t r_need, size_t w_need, size_t g_need, bool slack) {
+  if (r_need <= s->r_cap[q] && w_need <= s->w_cap[q] && g_need <= s->g_cap[q]) return DFH_OK;
   hipStream_t st = s->t->ctx->stream;
-  if (f.nrecv > s->r_cap[q] || (f.any_remote && (f.U > s->w_cap[q] || f.U > s->g_cap[q]))) {
-    if (s->cs) DFH_HIP(hipStreamSynchronize(s->cs));
-    rc = sync_all(s->t->ctx);
-    if (rc) return rc;
-  }
-  if (f.nrecv > s->r_cap[q]) {
-    const size_t cap = f.nrecv + f.nrecv / 2 + 1024;
+  const size_t stride = dfh_row_stride(s->t->v.k);
+  int rc = sync_all(s->t->ctx);  // (the collectives' stream is one of the context's extra streams)
+  if (rc) return rc;
+  auto cap_for = [slack](size_t n) { return slack ? n + n / 2 + 1024 : n; };
+  if (r_need > s->r_cap[q]) {
+    const size_t cap = cap_for(r_need);
     if ((rc = grow(&s->r_keys[q], cap, st)) || (rc = grow(&s->r_cnt[q], cap, st)) || (rc = grow(&s->r_rowid[q], multi_words(cap, s->c->world), st)) ||
         (rc = grow(&s->r_rows[q], cap * stride, st)))
       return rc;
     s->r_cap[q] = cap;
   }
-  if (f.any_remote && f.U > s->w_cap[q]) {
-    const size_t cap = f.U + f.U / 2 + 1024;
+  if (w_need > s->w_cap[q]) {
+    const size_t cap = cap_for(w_need);
     if ((rc = grow(&s->w_rows[q], cap * stride, st))) return rc;
     s->w_cap[q] = cap;
   }
-  if (f.any_remote && f.U > s->g_cap[q]) {
-    const size_t cap = f.U + f.U / 2 + 1024;
+  if (g_need > s->g_cap[q]) {
+    const size_t cap = cap_for(g_need);
     if ((rc = grow(&s->w_grads[q], cap * stride, st))) return rc;
     s->g_cap[q] = cap;
   }
   return DFH_OK;
+}
+
+// the exchange buffers of a flight's slot
+int flight_bufs(dfh_shard* s, const Flight& f) {
+  const size_t w = f.any_remote ? f.U : 0;
+  return slot_bufs(s, f.slot, f.nrecv, w, w, true);
+}
+
+// bytes per peer of one exchange of f at `unit` bytes per key, into the shard's lists (comm_exchange has read them when it
+// returns)
+void flight_bytes(dfh_shard* s, const Flight& f, size_t unit) {
+  const int W = s->c->world;
+  s->xsb.resize(W);
+  s->xrb.resize(W);
+  s->xso.resize(W);
+  for (int p = 0; p < W; ++p) {
+    s->xsb[p] = f.send[p] * unit;
+    s->xrb[p] = f.recv[p] * unit;
+    s->xso[p] = f.off[p] * unit;  // worker-side buffers are indexed by the key's rank u: owner p's slice starts at off[p]
+  }
 }
 
 // ctx option "owner_per_key" (DFH_OWNER_PER_KEY=1 sets its default; measurement): the owner side per DISTINCT key in two launches (dfh_shard_count_pull_multi,
@@ -953,91 +1006,398 @@ int flight_bufs(dfh_shard* s, const dfh_shard::Flight& f, size_t stride) {
 // (profiles/r06o_owner_side_per_key.txt) — the default stays per entry.
 bool owner_per_entry(const dfh_table* t) { return !t->ctx->owner_per_key; }
 
-void flight_bytes(const dfh_shard::Flight& f, int W, size_t unit, std::vector<size_t>& sb, std::vector<size_t>& rb, std::vector<size_t>& so) {
-  sb.resize(W);
-  rb.resize(W);
-  so.resize(W);
-  for (int p = 0; p < W; ++p) {
-    sb[p] = f.send[p] * unit;
-    rb[p] = f.recv[p] * unit;
-    so[p] = f.off[p] * unit;  // worker-side buffers are indexed by the key's rank u: owner p's slice starts at off[p]
+// L: this rank's own keys: rows + Push(kFeaCount) on its own table, {row, w} per key for the forward.  rows_in: the rows
+// of the other owners are already on their way (the overlap schedule, every step but an epoch's first) — the launch waits
+// for them and writes the row words of the others' keys too (k_lookup_uw_remote: one launch boundary less on the main
+// stream; F is then told uw_done)
+int flight_L(dfh_shard* s, Flight& f, int is_train, int push_cnt, hipEvent_t rows_in = nullptr) {
+  if (!f.any_own) return DFH_OK;
+  dfh_table* t = s->t;
+  dfh_ctx* ctx = t->ctx;
+  dfh_batch* b = f.b;
+  hipStream_t st = ctx->stream;
+  const bool one = s->c->world == 1;           // the number of keys is on the device: rows and threads for nnz of them
+  const uint32_t n_own = f.own_hi - f.own_lo;  // meaningless with one rank (the kernel clamps to *d_U)
+  const size_t n = one ? (size_t)b->nnz : (size_t)n_own;
+  if (int rcr = table_reserve(t, n)) return rcr;
+  StageScope ts(s, DFH_SHARD_STAGE_L, st);
+  const bool counts = push_cnt != 0;
+  const float* cntp = (counts && b->has_cnt) ? b->d_feacnt + f.own_lo : (const float*)nullptr;
+  const int mode = counts ? ((is_train && ctx->upd_kernel) ? 2 : 1) : 0;
+  if (rows_in) {
+    DFH_HIP(hipStreamWaitEvent(st, rows_in, 0));  // the rows of the other owners have arrived
+    const size_t stride = dfh_row_stride(t->v.k);
+    const UwRemote m{s->w_rows[f.slot], stride, b->d_U, f.own_lo, f.own_hi, b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err};
+    hipLaunchKernelGGL(k_lookup_uw_remote, dim3(grid_for_threads(f.U, ctx)), dim3(256), 0, st, t->v, b->d_feaids + f.own_lo, n_own,
+                       b->d_urow + f.own_lo, cntp, b->d_col_ptr + f.own_lo, mode, b->d_uw + f.own_lo, auc_pending(b), m,
+                       split_out(ctx, b, is_train, f.own_lo));
+  } else {
+    hipLaunchKernelGGL(k_lookup_step, dim3(grid_for_threads(n, ctx)), dim3(256), 0, st, t->v, b->d_feaids + f.own_lo,
+                       one ? b->d_U : (const uint32_t*)nullptr, one ? 0u : n_own, b->d_urow + f.own_lo, cntp, b->d_col_ptr + f.own_lo, mode,
+                       (uint32_t*)nullptr, 0, b->d_uw + f.own_lo, auc_pending(b), split_out(ctx, b, is_train, f.own_lo));
   }
+  b->auc_pending_n = 0;  // (the lookup's first block added up the AUC slots this batch object's previous step left)
+  DFH_HIP(hipGetLastError());
+  return DFH_OK;
 }
 
-// K on the collectives' stream: the keys other ranks own (+ their epoch-0 counts) to their owners
-int flight_K(dfh_shard* s, dfh_shard::Flight& f, int push_cnt) {
+// K: the keys other ranks own (+ their epoch-0 counts) to their owners.  Two message groups, one send and one receive per
+// peer each — the pattern every RCCL release serves (several sends to one peer inside a group are not).
+// ready: the minibatch's Localizer (preparation stream); freed: the previous user of this slot's receive buffers has applied
+// (or released) what it received
+int flight_K(dfh_shard* s, Flight& f, int push_cnt, hipStream_t st, hipEvent_t ready = nullptr, hipEvent_t freed = nullptr,
+             hipEvent_t done = nullptr) {
   dfh_comm* c = s->c;
-  const int W = c->world;
   dfh_batch* b = f.b;
-  StageScope ts(s, DFH_SHARD_STAGE_K, s->cs);
-  if (b && b->ready_pending) DFH_HIP(hipStreamWaitEvent(s->cs, b->ev_ready, 0));  // its Localizer (preparation stream)
-  if (s->p_pending[f.slot]) {  // the previous user of this slot's receive buffers has applied (or released) what it received
-    DFH_HIP(hipStreamWaitEvent(s->cs, s->ev_p[f.slot], 0));
-    s->p_pending[f.slot] = false;
-  }
-  std::vector<size_t> sb, rb, so;
-  flight_bytes(f, W, sizeof(uint64_t), sb, rb, so);
-  XPart xk{f.have ? b->d_feaids : nullptr, sb.data(), so.data(), s->r_keys[f.slot], rb.data(), nullptr};
-  int rc = comm_exchange(c, &xk, 1, s->cs, DFH_XCHG_KEYS);
+  int rc;
+  StageScope ts(s, DFH_SHARD_STAGE_K, st);
+  if ((rc = wait_on(st, ready)) || (rc = wait_on(st, freed))) return rc;
+  flight_bytes(s, f, sizeof(uint64_t));
+  XPart xk{f.have ? b->d_feaids : nullptr, s->xsb.data(), s->xso.data(), s->r_keys[f.slot], s->xrb.data(), nullptr};
+  rc = comm_exchange(c, &xk, 1, st, DFH_XCHG_KEYS);
   if (rc) return rc;
   if (push_cnt) {
     if (f.have && !b->has_cnt) {
-      hipLaunchKernelGGL(k_loc_counts, dim3(grid_for_threads(b->nnz, c->ctx)), dim3(256), 0, s->cs, b->d_col_ptr, b->d_U, b->d_feacnt);
+      hipLaunchKernelGGL(k_loc_counts, dim3(grid_for_threads(b->nnz, c->ctx)), dim3(256), 0, st, b->d_col_ptr, b->d_U, b->d_feacnt);
       DFH_HIP(hipGetLastError());
       b->has_cnt = true;
     }
-    flight_bytes(f, W, sizeof(float), sb, rb, so);
-    XPart xc{f.have ? b->d_feacnt : nullptr, sb.data(), so.data(), s->r_cnt[f.slot], rb.data(), nullptr};
-    rc = comm_exchange(c, &xc, 1, s->cs, DFH_XCHG_CNT);
+    flight_bytes(s, f, sizeof(float));
+    XPart xc{f.have ? b->d_feacnt : nullptr, s->xsb.data(), s->xso.data(), s->r_cnt[f.slot], s->xrb.data(), nullptr};
+    rc = comm_exchange(c, &xc, 1, st, DFH_XCHG_CNT);
     if (rc) return rc;
   }
-  DFH_HIP(hipEventRecord(s->ev_k[f.slot], s->cs));
-  return DFH_OK;
+  return record_on(st, done);
 }
 
-// R on the main stream (owners resolve the received keys once, count-push, pull), RW on the collectives' stream
-int flight_R_RW(dfh_shard* s, dfh_shard::Flight& f, int push_cnt) {
-  dfh_comm* c = s->c;
+// R: owners resolve the received keys once, count-push, pull (every source reads the same model version); per received
+// entry or per distinct key (owner_per_entry) — P follows the choice through f.listed
+int flight_R(dfh_shard* s, Flight& f, int push_cnt, hipEvent_t keys_in = nullptr, hipEvent_t done = nullptr) {
   dfh_table* t = s->t;
-  const int W = c->world, q = f.slot;
+  const int W = s->c->world, q = f.slot;
   hipStream_t st = t->ctx->stream;
-  const size_t stride = dfh_row_stride(t->v.k);
   int rc;
-  {
-    StageScope ts(s, DFH_SHARD_STAGE_R, st);
-    DFH_HIP(hipStreamWaitEvent(st, s->ev_k[q], 0));
-    if (f.nrecv) {
-      rc = dfh_shard_resolve_multi(t, s->r_keys[q], f.seg.data(), W, q, s->r_rowid[q]);
-      if (rc) return rc;
-      f.listed = !owner_per_entry(t);
-      if (!f.listed) {
-        if (push_cnt) {
-          rc = dfh_shard_push_count_multi(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, s->r_cnt[q]);
-          if (rc) return rc;
-        }
-        rc = dfh_shard_pull_resolved(t, s->r_rowid[q], f.nrecv, s->r_rows[q]);
-      } else {
-        rc = dfh_shard_count_pull_multi(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, push_cnt ? s->r_cnt[q] : nullptr, s->r_rows[q]);
+  StageScope ts(s, DFH_SHARD_STAGE_R, st);
+  if ((rc = wait_on(st, keys_in))) return rc;
+  if (f.nrecv) {
+    rc = dfh_shard_resolve_multi(t, s->r_keys[q], f.seg.data(), W, q, s->r_rowid[q]);
+    if (rc) return rc;
+    f.listed = !owner_per_entry(t);
+    if (!f.listed) {
+      if (push_cnt) {
+        rc = dfh_shard_push_count_multi(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, s->r_cnt[q]);
+        if (rc) return rc;
       }
+      rc = dfh_shard_pull_resolved(t, s->r_rowid[q], f.nrecv, s->r_rows[q]);
+    } else {
+      rc = dfh_shard_count_pull_multi(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, push_cnt ? s->r_cnt[q] : nullptr, s->r_rows[q]);
+    }
+    if (rc) return rc;
+  }
+  return record_on(st, done);
+}
+
+// RW: rows back to the workers, each owner's slice to its place among the minibatch's keys
+int flight_RW(dfh_shard* s, Flight& f, hipStream_t st, hipEvent_t rows_out = nullptr, hipEvent_t done = nullptr) {
+  const int q = f.slot;
+  int rc;
+  StageScope ts(s, DFH_SHARD_STAGE_RW, st);
+  if ((rc = wait_on(st, rows_out))) return rc;
+  flight_bytes(s, f, dfh_row_stride(s->t->v.k) * sizeof(float));
+  XPart x{s->r_rows[q], s->xrb.data(), nullptr, s->w_rows[q], s->xsb.data(), s->xso.data()};
+  rc = comm_exchange(s->c, &x, 1, st, DFH_XCHG_ROWS);
+  if (rc) return rc;
+  return record_on(st, done);
+}
+
+// F: the worker's math: own keys on the table, the others on the pulled rows.  uw_done: L wrote the others' row words
+// (and waited for their rows); rows_in: the event to wait for otherwise.  grads_done: recorded between the gradient rows of
+// the others' keys and the own keys' in-place update, so that G may start while that runs — the stage is then timed in two
+// brackets around it
+int flight_F(dfh_shard* s, Flight& f, int is_train, int push_cnt, bool uw_done = false, hipEvent_t rows_in = nullptr,
+             hipEvent_t grads_done = nullptr) {
+  dfh_table* t = s->t;
+  dfh_ctx* ctx = t->ctx;
+  dfh_batch* b = f.b;
+  hipStream_t st = ctx->stream;
+  const int q = f.slot, k = t->v.k, kp = t->v.kp;
+  const size_t stride = dfh_row_stride(k);
+  const KeyRange own{f.own_lo, f.own_hi, 0u}, others{f.own_lo, f.own_hi, 1u}, others_pen{f.own_lo, f.own_hi, 3u};
+  // round 5: with keys of other ranks in the minibatch ONE launch of k_update_fused<MIXED> serves all keys — gradient rows for
+  // the others' keys, the in-place update for the own ones (ctx option shard_mixed_update = 0: the two launches of round 4)
+  const bool mixed = b && is_train && f.any_remote && ctx->upd_kernel != 0 && ctx->shard_mixed_update != 0;
+  // BinClassMetric::AUC of the minibatch: rides in the own keys' update launch of a training step (k_update_fused has idle
+  // VALUs), a launch of its own otherwise
+  bool auc_rides = b && b->compute_auc && is_train && (f.any_own || mixed) && ctx->auc_in_update != 0 && ctx->upd_kernel != 0;
+  const int pgrid = f.have ? std::min(grid_for_waves(b->nnz, ctx), PROG_SLOTS) : 1;
+  int rc;
+  std::optional<StageScope> ts;
+  if (b) {
+    ts.emplace(s, DFH_SHARD_STAGE_F, st);
+    rc = ensure_xv(b, kp);
+    if (rc) return rc;
+    if ((rc = wait_on(st, rows_in))) return rc;  // the rows of the other owners have arrived
+    if (f.any_remote && !uw_done) {
+      hipLaunchKernelGGL(k_uw_remote, dim3(grid_for_threads(f.U, ctx)), dim3(256), 0, st, s->w_rows[q], stride, b->d_U, f.own_lo, f.own_hi,
+                         b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err);
+      DFH_HIP(hipGetLastError());
+    }
+    // one rank: no MixSrc at all, the forward that reads the table only
+    MixSrc mix{f.any_remote ? s->w_rows[q] + 4 : nullptr, stride};
+    rc = launch_forward(b, table_src(t, b->d_urow), k, kp, b->d_uw, s->c->world > 1 ? &mix : nullptr);
+    if (rc) return rc;
+    if (b->compute_auc && !auc_rides) {
+      rc = launch_auc(b);
       if (rc) return rc;
     }
-    DFH_HIP(hipEventRecord(s->ev_r[q], st));
+    if (f.any_remote && !is_train) {  // EvaluatePenalty over the pulled weights (sgd_learner.cc:249-273)
+      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, batch_view(b), packed_src(s->w_rows[q], k), t->v, k, kp, others);
+      DFH_HIP(hipGetLastError());
+    }
+    if (mixed) {  // gradient rows of the others' keys AND the own keys' in-place update, one launch
+      const bool with_auc = auc_rides && b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
+      rc = launch_update_fused(b, t->v, k, kp, b->d_need, b->d_uw, kAllKeys, push_cnt != 0, with_auc, s->w_rows[q], s->w_grads[q], stride);
+      if (rc) return rc;
+      if (auc_rides && !with_auc) {  // the minibatch is beyond the pair-counting size
+        rc = launch_auc(b);
+        if (rc) return rc;
+      }
+    } else if (is_train && f.any_remote) {  // the gradient-row launch reads every pulled row anyway: it adds up their penalty too
+      rc = launch_backward<false>(b, packed_src(s->w_rows[q], k), t->v, s->w_grads[q], stride, k, kp, nullptr, others_pen);
+      if (rc) return rc;
+    }
   }
-  {
-    StageScope ts(s, DFH_SHARD_STAGE_RW, s->cs);
-    DFH_HIP(hipStreamWaitEvent(s->cs, s->ev_r[q], 0));
-    std::vector<size_t> sb, rb, so;
-    flight_bytes(f, W, stride * sizeof(float), sb, rb, so);
-    XPart x{s->r_rows[q], rb.data(), nullptr, s->w_rows[q], sb.data(), so.data()};
-    rc = comm_exchange(c, &x, 1, s->cs, DFH_XCHG_ROWS);
-    if (rc) return rc;
-    DFH_HIP(hipEventRecord(s->ev_rw[q], s->cs));
+  if (grads_done) {
+    ts.reset();
+    if (is_train) DFH_HIP(hipEventRecord(grads_done, st));  // the gradient rows are complete: G may start ...
+    if (b && !mixed) ts.emplace(s, DFH_SHARD_STAGE_F, st);  // ... while the own keys are updated in place
   }
-  f.pulled = true;
+  if (b && !mixed) {
+    if (is_train && f.any_own) {  // the fused in-place update accumulates the own keys' penalty itself
+      const bool auc_wanted = auc_rides;
+      rc = launch_backward<true>(b, table_src(t, b->d_urow), t->v, nullptr, 0, k, kp, b->d_need, own, b->d_uw,
+                                 push_cnt != 0 && ctx->upd_kernel != 0, &auc_rides);
+      if (rc) return rc;
+      if (auc_wanted && !auc_rides) {  // the minibatch is beyond the pair-counting size
+        rc = launch_auc(b);
+        if (rc) return rc;
+      }
+    } else if (f.any_own) {
+      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, batch_view(b), table_src(t, b->d_urow), t->v, k, kp, own);
+      DFH_HIP(hipGetLastError());
+    }
+  }
   return DFH_OK;
 }
 
-int shard_step_overlap(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int* any_active);
+// G: gradient rows to the owners (into the buffer their rows came from)
+int flight_G(dfh_shard* s, Flight& f, hipStream_t st, hipEvent_t grads_in = nullptr, hipEvent_t done = nullptr) {
+  const int q = f.slot;
+  int rc;
+  StageScope ts(s, DFH_SHARD_STAGE_G, st);
+  if ((rc = wait_on(st, grads_in))) return rc;
+  flight_bytes(s, f, dfh_row_stride(s->t->v.k) * sizeof(float));
+  XPart x{s->w_grads[q], s->xsb.data(), s->xso.data(), s->r_rows[q], s->xrb.data(), nullptr};
+  rc = comm_exchange(s->c, &x, 1, st, DFH_XCHG_GRADS);
+  if (rc) return rc;
+  return record_on(st, done);
+}
+
+// P: the other sources' gradients, applied source rank after source rank over what R left (f.listed); a step that does not
+// train releases the rows R resolved
+int flight_P(dfh_shard* s, Flight& f, int is_train, hipEvent_t grads_in = nullptr) {
+  dfh_table* t = s->t;
+  const int W = s->c->world, q = f.slot;
+  if (!is_train) return f.nrecv ? dfh_shard_release(t, s->r_rowid[q], f.nrecv, q) : DFH_OK;
+  hipStream_t st = t->ctx->stream;
+  int rc;
+  StageScope ts(s, DFH_SHARD_STAGE_P, st);
+  if ((rc = wait_on(st, grads_in))) return rc;
+  if (f.nrecv) {
+    rc = !f.listed ? dfh_shard_push_grad_multi(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, s->r_rows[q])
+                   : dfh_shard_push_grad_listed(t, s->r_rowid[q], s->r_keys[q], f.seg.data(), W, q, s->r_rows[q]);
+    if (rc) return rc;
+  }
+  return DFH_OK;
+}
+
+// ---- the sync schedule: one minibatch at a time, described in fl[0], exchange slot 0; every stage on the context's
+// stream, ordered by it alone.  One rank: nothing is counted, nothing exchanged, nothing waits for the host.
+int shard_step_sync(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int* any_active) {
+  dfh_ctx* ctx = s->t->ctx;
+  if (s->timing) ++s->stage_steps;
+  DFH_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int W = s->c->world;
+  int rc;
+  if (b) {
+    rc = main_begin(b);
+    if (rc) return rc;
+  }
+  // ---- counts: {keys for every owner, "I have a minibatch"} -> every peer, then to the host (the step's one host wait)
+  if (W > 1) {
+    if (s->counts_ready && s->counts_for == b) {
+      // exchanged inside the previous step: long arrived
+      DFH_HIP(hipEventSynchronize(s->cnt_ev));
+    } else {
+      DFH_ARG(!s->counts_ready, "dfh_shard_step: the batch differs from the one announced to dfh_shard_prefetch_counts");
+      {
+        StageScope ts(s, DFH_SHARD_STAGE_COUNTS, st);
+        rc = queue_counts(s, b);
+        if (rc) return rc;
+      }
+      DFH_HIP(hipStreamSynchronize(st));
+    }
+    s->counts_ready = false;
+  }
+  Flight& f = s->fl[0];
+  flight_sizes(s, f, b, 0);
+  if (any_active) *any_active = f.active != 0 ? 1 : 0;
+  ++s->steps;
+  if (b) b->nrows_seen += (float)b->nrows;
+  if (f.active == 0) {
+    s->next_armed = false;  // the epoch is over: nothing follows
+    return b ? main_end(b) : DFH_OK;
+  }
+  if ((rc = flight_bufs(s, f))) return rc;
+  if ((rc = flight_L(s, f, is_train, push_cnt))) return rc;
+  if (W > 1 && (rc = flight_K(s, f, push_cnt, st))) return rc;
+  if (f.nrecv && (rc = flight_R(s, f, push_cnt))) return rc;
+  if (W > 1 && (rc = flight_RW(s, f, st))) return rc;
+  if ((rc = flight_F(s, f, is_train, push_cnt))) return rc;
+  // ---- the counts of the FOLLOWING step (dfh_shard_prefetch_counts): on their way to the host while this
+  // step's gradients travel and are applied, so that the next call finds them there
+  if (s->next_armed) {
+    s->next_armed = false;
+    dfh_batch* nb = s->next_b;
+    if (nb) {
+      rc = main_begin(nb);  // its Localizer (preparation stream) has to be through
+      if (rc) return rc;
+    }
+    rc = queue_counts(s, nb);
+    if (rc) return rc;
+    DFH_HIP(hipEventRecord(s->cnt_ev, st));
+    s->counts_ready = true;
+    s->counts_for = nb;
+  }
+  if (is_train && W > 1 && (rc = flight_G(s, f, st))) return rc;
+  if (f.nrecv && (rc = flight_P(s, f, is_train))) return rc;
+  return b ? main_end(b) : DFH_OK;
+}
+
+// ---- the overlap schedule: two minibatches in flight (dfh_shard_set_exchange(s, 1)); world > 1.  K, RW and G on the
+// collectives' stream, events between the stages.
+// cur = the minibatch this call trains.  If it was announced to the previous call (dfh_shard_prefetch_counts) its
+// counts, keys and rows were exchanged in there; otherwise (first step of an epoch) they are exchanged now.
+int shard_step_overlap(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int* any_active) {
+  dfh_comm* c = s->c;
+  dfh_ctx* ctx = s->t->ctx;
+  DFH_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream, cs = s->cs;
+  int rc;
+  if (s->timing) ++s->stage_steps;
+  static const bool trace = getenv("DFH_SHARD_TRACE") != nullptr;
+  Flight& cur = s->fl[s->cur];
+  if (trace)
+    fprintf(stderr, "[shard %d] step %llu: b=%p cur{slot %d described %d pulled %d b=%p} armed %d next_b=%p\n", c->rank,
+            (unsigned long long)s->steps, (void*)b, s->cur, (int)cur.described, (int)cur.pulled, (void*)cur.b, (int)s->next_armed,
+            (void*)s->next_b);
+  if (!(cur.described && cur.b == b)) {
+    // not announced: describe it now (its counts over the collectives' stream, one host wait)
+    DFH_ARG(!cur.described || !cur.pulled, "dfh_shard_step: the batch differs from the one announced to dfh_shard_prefetch_counts");
+    if (b && b->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, b->ev_ready, 0));
+    {
+      StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
+      rc = queue_counts(s, b, cs);
+      if (rc) return rc;
+    }
+    DFH_HIP(hipStreamSynchronize(cs));
+    flight_sizes(s, cur, b, s->cur);
+  }
+  if (any_active) *any_active = cur.active != 0 ? 1 : 0;
+  ++s->steps;
+  if (b) b->nrows_seen += (float)b->nrows;
+  // the minibatch after this one, if the caller named it
+  const bool look = s->next_armed;
+  dfh_batch* nb = look ? s->next_b : nullptr;
+  s->next_armed = false;
+  Flight& nxt = s->fl[s->cur ^ 1];
+  nxt = Flight();
+  if (cur.active == 0) {
+    // nobody has a minibatch: the epoch is over (nothing can have been announced behind it)
+    cur = Flight();
+    return b ? main_end(b) : DFH_OK;
+  }
+  // K of a minibatch on the collectives' stream, behind its Localizer (preparation stream) and behind P (or the release)
+  // of the minibatch that last received into its slot; then R on the main stream and RW on the collectives'
+  auto keys_out = [&](Flight& f) {
+    const int q = f.slot;
+    hipEvent_t ready = f.b && f.b->ready_pending ? f.b->ev_ready : nullptr;
+    hipEvent_t freed = s->p_pending[q] ? s->ev_p[q] : nullptr;
+    s->p_pending[q] = false;
+    return flight_K(s, f, push_cnt, cs, ready, freed, s->ev_k[q]);
+  };
+  auto rows_back = [&](Flight& f) {
+    const int q = f.slot;
+    int r = flight_R(s, f, push_cnt, s->ev_k[q], s->ev_r[q]);
+    if (!r) r = flight_RW(s, f, cs, s->ev_r[q], s->ev_rw[q]);
+    f.pulled = r == DFH_OK;  // the other owners' rows are on their way to w_rows[q]
+    return r;
+  };
+  rc = flight_bufs(s, cur);
+  if (rc) return rc;
+  if (b) {
+    rc = main_begin(b);  // its Localizer (preparation stream) -> main stream
+    if (rc) return rc;
+    // (the split list of THIS minibatch: every launch that appends to it — L's, or F's k_uw_remote at the pipeline fill — is
+    // made below, in this call, on this stream, behind this batch object's previous update; none for the next minibatch)
+  }
+  const int q = cur.slot;
+  // L runs after everything the previous step applied: own keys are read with zero staleness.  The row words of the
+  // others' keys ride in its launch when their rows are already on their way (every step but an epoch's first)
+  const bool uw_folded = cur.any_own && cur.pulled && cur.any_remote && b != nullptr;
+  if ((rc = flight_L(s, cur, is_train, push_cnt, uw_folded ? s->ev_rw[q] : nullptr))) return rc;
+  if (!cur.pulled) {  // pipeline fill: K, R, RW of this very minibatch, in the sync step's order (after L)
+    if ((rc = keys_out(cur)) || (rc = rows_back(cur))) return rc;
+  }
+  // ---- counts of the next minibatch: on their way while F is queued and runs
+  if (look) {
+    if (nb && nb->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, nb->ev_ready, 0));
+    StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
+    rc = queue_counts(s, nb, cs);
+    if (rc) return rc;
+    DFH_HIP(hipEventRecord(s->cnt_ev, cs));
+  }
+  if ((rc = flight_F(s, cur, is_train, push_cnt, uw_folded, uw_folded ? nullptr : s->ev_rw[q], s->ev_f))) return rc;
+  // ---- the next minibatch's sizes (the one host wait; the device is busy with F), then its keys
+  bool ahead = false;
+  if (look) {
+    DFH_HIP(hipEventSynchronize(s->cnt_ev));
+    flight_sizes(s, nxt, nb, s->cur ^ 1);
+    ahead = nxt.active != 0;
+    if (trace)
+      fprintf(stderr, "[shard %d]   next: active %zu U %zu nrecv %zu own [%u, %u) -> ahead %d\n", c->rank, nxt.active, nxt.U, nxt.nrecv,
+              nxt.own_lo, nxt.own_hi, (int)ahead);
+    if (ahead) {
+      rc = flight_bufs(s, nxt);
+      if (rc) return rc;
+      rc = keys_out(nxt);  // small; travels while F computes
+      if (rc) return rc;
+    }
+  }
+  if (is_train && (rc = flight_G(s, cur, cs, s->ev_f, s->ev_g))) return rc;
+  // ---- R, RW of the next minibatch: the owners pull while this step's gradients travel — before they are applied
+  // (staleness 1 for the rows of other owners) — and the rows travel while they are applied
+  if (ahead && (rc = rows_back(nxt))) return rc;
+  if ((rc = flight_P(s, cur, is_train, s->ev_g))) return rc;
+  if (cur.nrecv) {  // r_keys[q] / r_rowid[q] / r_rows[q] are free again once this point of the main stream is reached
+    DFH_HIP(hipEventRecord(s->ev_p[q], st));
+    s->p_pending[q] = true;
+  }
+  cur = Flight();
+  if (look) s->cur ^= 1;  // the announced minibatch (described, maybe pulled) is the next call's
+  return b ? main_end(b) : DFH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1076,8 +1436,8 @@ int dfh_shard_set_exchange(dfh_shard* s, int mode) {
   if (s->cs) DFH_HIP(hipStreamSynchronize(s->cs));
   s->exchange = mode;
   s->p_pending[0] = s->p_pending[1] = false;  // everything was drained above
-  s->fl[0] = dfh_shard::Flight();
-  s->fl[1] = dfh_shard::Flight();
+  s->fl[0] = Flight();
+  s->fl[1] = Flight();
   s->cur = 0;
   s->next_armed = false;
   return DFH_OK;
@@ -1089,31 +1449,11 @@ int dfh_shard_reserve(dfh_shard* s, size_t batch_keys, size_t recv_keys) {
     set_error("dfh_shard_reserve: a minibatch is under way (call it before the first step or between epochs)");
     return DFH_ERR_STATE;
   }
-  dfh_ctx* ctx = s->t->ctx;
-  DFH_HIP(hipSetDevice(ctx->device));
-  if (s->cs) DFH_HIP(hipStreamSynchronize(s->cs));
-  int rc = sync_all(ctx);
-  if (rc) return rc;
-  hipStream_t st = ctx->stream;
-  const size_t stride = dfh_row_stride(s->t->v.k);
+  DFH_HIP(hipSetDevice(s->t->ctx->device));
+  const size_t w = s->c->world > 1 ? batch_keys : 0;
   const int nslots = s->exchange == 1 ? 2 : 1;
-  for (int q = 0; q < nslots; ++q) {
-    if (recv_keys > s->r_cap[q]) {
-      const size_t cap = recv_keys;
-      if ((rc = grow(&s->r_keys[q], cap, st)) || (rc = grow(&s->r_cnt[q], cap, st)) ||
-          (rc = grow(&s->r_rowid[q], multi_words(cap, s->c->world), st)) || (rc = grow(&s->r_rows[q], cap * stride, st)))
-        return rc;
-      s->r_cap[q] = cap;
-    }
-    if (s->c->world > 1 && batch_keys > s->w_cap[q]) {
-      if ((rc = grow(&s->w_rows[q], batch_keys * stride, st))) return rc;
-      s->w_cap[q] = batch_keys;
-    }
-    if (s->c->world > 1 && batch_keys > s->g_cap[q]) {
-      if ((rc = grow(&s->w_grads[q], batch_keys * stride, st))) return rc;
-      s->g_cap[q] = batch_keys;
-    }
-  }
+  for (int q = 0; q < nslots; ++q)
+    if (int rc = slot_bufs(s, q, recv_keys, w, w, false)) return rc;
   return DFH_OK;
 }
 
@@ -1147,471 +1487,20 @@ int dfh_shard_get_timing(dfh_shard* s, int reset, double* ms, uint64_t* steps) {
 
 int dfh_shard_step(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int* any_active) {
   DFH_ARG(s, "dfh_shard_step: NULL shard");
-  dfh_table* t = s->t;
-  dfh_comm* c = s->c;
-  dfh_ctx* ctx = t->ctx;
-  DFH_ARG(!b || b->ctx == ctx, "batch and shard must share a context");
+  DFH_ARG(!b || b->ctx == s->t->ctx, "batch and shard must share a context");
   if (b && !b->localized) {
     set_error("dfh_shard_step: batch is not localized (call dfh_localize first)");
     return DFH_ERR_STATE;
   }
   if (is_train) {
-    if (int rca = require_aux(t, "dfh_shard_step(is_train)")) return rca;
+    if (int rca = require_aux(s->t, "dfh_shard_step(is_train)")) return rca;
   }
-  if (s->exchange == 1 && c->world > 1) return shard_step_overlap(s, b, is_train, push_cnt, any_active);
-  if (s->timing) ++s->stage_steps;
-  DFH_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int W = c->world, me = c->rank;
-  const int k = t->v.k, kp = t->v.kp;
-  const size_t stride = dfh_row_stride(k);
-  int rc;
-  const bool have = b != nullptr && b->nnz > 0;
-  if (b) {
-    rc = main_begin(b);
-    if (rc) return rc;
-  }
-  // ---- counts: {keys for every owner, "I have a minibatch"} -> every peer, then to the host (the step's one
-  // host wait).  One rank: every key is its own, nothing to count, nothing to wait for.
-  std::vector<size_t> send(W, 0), recv(W, 0), seg(W + 1, 0), off(W + 1, 0);
-  size_t nrecv = 0, active = b != nullptr ? 1 : 0;
-  uint32_t own_lo = 0, own_hi = 0xFFFFFFFFu;  // ranks [own_lo, own_hi) of the minibatch's unique keys are this rank's
-  if (W > 1) {
-    if (s->counts_ready && s->counts_for == b) {
-      // exchanged inside the previous step: long arrived
-      DFH_HIP(hipEventSynchronize(s->cnt_ev));
-    } else {
-      DFH_ARG(!s->counts_ready, "dfh_shard_step: the batch differs from the one announced to dfh_shard_prefetch_counts");
-      {
-        StageScope ts(s, DFH_SHARD_STAGE_COUNTS, st);
-        rc = queue_counts(s, b);
-        if (rc) return rc;
-      }
-      DFH_HIP(hipStreamSynchronize(st));
-    }
-    s->counts_ready = false;
-    active = 0;
-    for (int p = 0; p < W; ++p) {
-      send[p] = (size_t)s->h_cnt[2 * p];
-      recv[p] = (size_t)s->h_cnt[2 * W + 2 * p];
-      active += s->h_cnt[2 * W + 2 * p + 1] != 0 ? 1 : 0;
-      off[p + 1] = off[p] + send[p];   // = bounds[p + 1]: owner p's keys are ranks [off[p], off[p+1]) of the minibatch
-    }
-    own_lo = (uint32_t)off[me];
-    own_hi = (uint32_t)off[me + 1];
-    send[me] = recv[me] = 0;           // the rank's own keys are not exchanged
-    for (int p = 0; p < W; ++p) {
-      nrecv += recv[p];
-      seg[p + 1] = seg[p] + recv[p];
-    }
-  }
-  const size_t U = off[W];             // W > 1 only; with one rank the count stays on the device (d_U)
-  const bool any_own = W == 1 ? have : (have && own_hi > own_lo);
-  const bool any_remote = W > 1 && have && (own_lo > 0 || (size_t)own_hi < U);
-  if (any_active) *any_active = active != 0 ? 1 : 0;
-  ++s->steps;
-  if (b) b->nrows_seen += (float)b->nrows;
-  if (active == 0) {
-    s->next_armed = false;  // the epoch is over: nothing follows
-    return b ? main_end(b) : DFH_OK;
-  }
-  // ---- buffers
-  if (nrecv > s->r_cap[0]) {
-    const size_t cap = nrecv + nrecv / 2 + 1024;
-    if ((rc = grow(&s->r_keys[0], cap, st)) || (rc = grow(&s->r_cnt[0], cap, st)) || (rc = grow(&s->r_rowid[0], multi_words(cap, s->c->world), st)) ||
-        (rc = grow(&s->r_rows[0], cap * stride, st)))
-      return rc;
-    s->r_cap[0] = cap;
-  }
-  if (any_remote && U > s->w_cap[0]) {
-    const size_t cap = U + U / 2 + 1024;
-    if ((rc = grow(&s->w_rows[0], cap * stride, st))) return rc;
-    s->w_cap[0] = cap;
-  }
-  if (any_remote && U > s->g_cap[0]) {
-    const size_t cap = U + U / 2 + 1024;
-    if ((rc = grow(&s->w_grads[0], cap * stride, st))) return rc;
-    s->g_cap[0] = cap;
-  }
-  std::vector<size_t> sb(W), rb(W), so(W), sb2(W), rb2(W), so2(W);
-  auto bytes = [&](size_t unit, std::vector<size_t>& sbv, std::vector<size_t>& rbv, std::vector<size_t>& sov) {
-    for (int p = 0; p < W; ++p) {
-      sbv[p] = send[p] * unit;
-      rbv[p] = recv[p] * unit;
-      sov[p] = off[p] * unit;          // worker-side buffers are indexed by the key's rank u: owner p's slice starts at off[p]
-    }
-  };
-  const uint32_t n_own = own_hi - own_lo;  // meaningless for W == 1 (the kernels clamp to *d_U)
-  // ---- L: this rank's own keys: rows + Push(kFeaCount) on its own table, {row, w} per key for the forward
-  if (any_own) {
-    if (int rcr = table_reserve(t, W == 1 ? b->nnz : n_own)) return rcr;
-    StageScope ts(s, DFH_SHARD_STAGE_L, st);
-    const bool counts = push_cnt != 0;
-    hipLaunchKernelGGL(k_lookup_step, dim3(grid_for_threads(W == 1 ? b->nnz : n_own, ctx)), dim3(256), 0, st, t->v, b->d_feaids + own_lo,
-                       W == 1 ? b->d_U : (const uint32_t*)nullptr, W == 1 ? 0u : n_own, b->d_urow + own_lo,
-                       (counts && b->has_cnt) ? b->d_feacnt + own_lo : (const float*)nullptr, b->d_col_ptr + own_lo,
-                       counts ? ((is_train && ctx->upd_kernel) ? 2 : 1) : 0, (uint32_t*)nullptr, 0, b->d_uw + own_lo, auc_pending(b),
-                       split_out(ctx, b, is_train, own_lo));
-    b->auc_pending_n = 0;  // (the lookup's first block added up the AUC slots this batch object's previous step left)
-    DFH_HIP(hipGetLastError());
-  }
-  // ---- K: the other keys (+ counts in epoch 0) to their owners.  Two message groups, one send and one receive
-  // per peer each — the pattern every RCCL release serves (several sends to one peer inside a group are not)
-  if (W > 1) {
-    StageScope ts(s, DFH_SHARD_STAGE_K, st);
-    bytes(sizeof(uint64_t), sb, rb, so);
-    XPart xk{have ? b->d_feaids : nullptr, sb.data(), so.data(), s->r_keys[0], rb.data(), nullptr};
-    rc = comm_exchange(c, &xk, 1, nullptr, DFH_XCHG_KEYS);
-    if (rc) return rc;
-    if (push_cnt) {
-      if (have && !b->has_cnt) {
-        hipLaunchKernelGGL(k_loc_counts, dim3(grid_for_threads(b->nnz, ctx)), dim3(256), 0, st, b->d_col_ptr, b->d_U, b->d_feacnt);
-        DFH_HIP(hipGetLastError());
-        b->has_cnt = true;
-      }
-      bytes(sizeof(float), sb2, rb2, so2);
-      XPart xc{have ? b->d_feacnt : nullptr, sb2.data(), so2.data(), s->r_cnt[0], rb2.data(), nullptr};
-      rc = comm_exchange(c, &xc, 1, nullptr, DFH_XCHG_CNT);
-      if (rc) return rc;
-    }
-  }
-  // ---- R: owners resolve once, count-push, pull (every source reads the same model version)
-  const bool per_entry = owner_per_entry(t);
-  if (nrecv) {
-    StageScope ts(s, DFH_SHARD_STAGE_R, st);
-    rc = dfh_shard_resolve_multi(t, s->r_keys[0], seg.data(), W, 0, s->r_rowid[0]);
-    if (rc) return rc;
-    if (per_entry) {
-      if (push_cnt) {
-        rc = dfh_shard_push_count_multi(t, s->r_rowid[0], s->r_keys[0], seg.data(), W, 0, s->r_cnt[0]);
-        if (rc) return rc;
-      }
-      rc = dfh_shard_pull_resolved(t, s->r_rowid[0], nrecv, s->r_rows[0]);
-    } else {
-      rc = dfh_shard_count_pull_multi(t, s->r_rowid[0], s->r_keys[0], seg.data(), W, 0, push_cnt ? s->r_cnt[0] : nullptr, s->r_rows[0]);
-    }
-    if (rc) return rc;
-  }
-  // ---- RW: rows back to the workers, each owner's slice to its place among the minibatch's keys
-  if (W > 1) {
-    StageScope ts(s, DFH_SHARD_STAGE_RW, st);
-    bytes(stride * sizeof(float), sb, rb, so);
-    XPart x{s->r_rows[0], rb.data(), nullptr, s->w_rows[0], sb.data(), so.data()};
-    rc = comm_exchange(c, &x, 1, nullptr, DFH_XCHG_ROWS);
-    if (rc) return rc;
-  }
-  // ---- F: the worker's math: own keys on the table, the others on the pulled rows
-  const KeyRange own{own_lo, own_hi, 0u}, others{own_lo, own_hi, 1u}, others_pen{own_lo, own_hi, 3u};
-  if (b) {
-    StageScope ts(s, DFH_SHARD_STAGE_F, st);
-    rc = ensure_xv(b, kp);
-    if (rc) return rc;
-    const RowSrc tsrc = table_src(t, b->d_urow);
-    if (any_remote) {
-      hipLaunchKernelGGL(k_uw_remote, dim3(grid_for_threads(U, ctx)), dim3(256), 0, st, s->w_rows[0], stride, b->d_U, own_lo, own_hi,
-                         b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err);
-      DFH_HIP(hipGetLastError());
-    }
-    MixSrc mix{any_remote ? s->w_rows[0] + 4 : nullptr, stride};
-    rc = launch_forward(b, tsrc, k, kp, b->d_uw, W > 1 ? &mix : nullptr);
-    if (rc) return rc;
-    // BinClassMetric::AUC of the minibatch: rides in the own keys' update launch of a training step (k_update_fused has idle
-    // VALUs), a launch of its own otherwise
-    // round 5: with keys of other ranks in the minibatch ONE launch of k_update_fused<MIXED> serves all keys — gradient rows for
-    // the others' keys, the in-place update for the own ones (ctx option shard_mixed_update = 0: the two launches of round 4)
-    const bool mixed = is_train && any_remote && ctx->upd_kernel != 0 && ctx->shard_mixed_update != 0;
-    bool auc_rides = b->compute_auc && is_train && (any_own || mixed) && ctx->auc_in_update != 0 && ctx->upd_kernel != 0;
-    if (b->compute_auc && !auc_rides) {
-      rc = launch_auc(b);
-      if (rc) return rc;
-    }
-    BatchView bv = batch_view(b);
-    const int pgrid = have ? std::min(grid_for_waves(b->nnz, ctx), PROG_SLOTS) : 1;
-    if (any_remote && !is_train) {  // EvaluatePenalty over the pulled weights (sgd_learner.cc:249-273)
-      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, bv, packed_src(s->w_rows[0], k), t->v, k, kp, others);
-      DFH_HIP(hipGetLastError());
-    }
-    if (mixed) {
-      const bool with_auc = auc_rides && b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
-      rc = launch_update_fused(b, t->v, k, kp, b->d_need, b->d_uw, kAllKeys, push_cnt != 0, with_auc, s->w_rows[0], s->w_grads[0], stride);
-      if (rc) return rc;
-      if (auc_rides && !with_auc) {  // the minibatch is beyond the pair-counting size
-        rc = launch_auc(b);
-        if (rc) return rc;
-      }
-    } else {
-      if (is_train && any_remote) {  // the gradient-row launch reads every pulled row anyway: it adds up their penalty too
-        rc = launch_backward<false>(b, packed_src(s->w_rows[0], k), t->v, s->w_grads[0], stride, k, kp, nullptr, others_pen);
-        if (rc) return rc;
-      }
-      if (is_train && any_own) {  // the fused in-place update accumulates the own keys' penalty itself
-        const bool auc_wanted = auc_rides;
-        rc = launch_backward<true>(b, tsrc, t->v, nullptr, 0, k, kp, b->d_need, own, b->d_uw, push_cnt != 0 && ctx->upd_kernel != 0,
-                                   &auc_rides);
-        if (rc) return rc;
-        if (auc_wanted && !auc_rides) {  // the minibatch is beyond the pair-counting size
-          rc = launch_auc(b);
-          if (rc) return rc;
-        }
-      } else if (any_own) {
-        hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, bv, tsrc, t->v, k, kp, own);
-        DFH_HIP(hipGetLastError());
-      }
-    }
-  }
-  // ---- the counts of the FOLLOWING step (dfh_shard_prefetch_counts): on their way to the host while this
-  // step's gradients travel and are applied, so that the next call finds them there
-  if (s->next_armed) {
-    s->next_armed = false;
-    dfh_batch* nb = s->next_b;
-    if (nb) {
-      rc = main_begin(nb);  // its Localizer (preparation stream) has to be through
-      if (rc) return rc;
-    }
-    rc = queue_counts(s, nb);
-    if (rc) return rc;
-    DFH_HIP(hipEventRecord(s->cnt_ev, st));
-    s->counts_ready = true;
-    s->counts_for = nb;
-  }
-  // ---- G + P: gradients to the owners, applied source rank after source rank
-  if (is_train && W > 1) {
-    bytes(stride * sizeof(float), sb, rb, so);
-    XPart x{s->w_grads[0], sb.data(), so.data(), s->r_rows[0], rb.data(), nullptr};
-    {
-      StageScope ts(s, DFH_SHARD_STAGE_G, st);
-      rc = comm_exchange(c, &x, 1, nullptr, DFH_XCHG_GRADS);
-      if (rc) return rc;
-    }
-    if (nrecv) {
-      StageScope ts(s, DFH_SHARD_STAGE_P, st);
-      rc = per_entry ? dfh_shard_push_grad_multi(t, s->r_rowid[0], s->r_keys[0], seg.data(), W, 0, s->r_rows[0])
-                             : dfh_shard_push_grad_listed(t, s->r_rowid[0], s->r_keys[0], seg.data(), W, 0, s->r_rows[0]);
-      if (rc) return rc;
-    }
-  } else if (nrecv) {
-    rc = dfh_shard_release(t, s->r_rowid[0], nrecv, 0);
-    if (rc) return rc;
-  }
-  return b ? main_end(b) : DFH_OK;
+  // one rank takes the sync schedule whatever the mode: there is nothing to overlap
+  return (s->exchange == 1 && s->c->world > 1) ? shard_step_overlap(s, b, is_train, push_cnt, any_active)
+                                              : shard_step_sync(s, b, is_train, push_cnt, any_active);
 }
 
 }  // extern "C"
-
-namespace {
-// ---- dfh_shard_step with two minibatches in flight (dfh_shard_set_exchange(s, 1)); world > 1.
-// cur = the minibatch this call trains.  If it was announced to the previous call (dfh_shard_prefetch_counts) its
-// counts, keys and rows were exchanged in there; otherwise (first step of an epoch) they are exchanged now.
-int shard_step_overlap(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int* any_active) {
-  dfh_table* t = s->t;
-  dfh_comm* c = s->c;
-  dfh_ctx* ctx = t->ctx;
-  DFH_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream, cs = s->cs;
-  const int W = c->world;
-  const int k = t->v.k, kp = t->v.kp;
-  const size_t stride = dfh_row_stride(k);
-  int rc;
-  if (s->timing) ++s->stage_steps;
-  static const bool trace = getenv("DFH_SHARD_TRACE") != nullptr;
-  dfh_shard::Flight& cur = s->fl[s->cur];
-  if (trace)
-    fprintf(stderr, "[shard %d] step %llu: b=%p cur{slot %d described %d pulled %d b=%p} armed %d next_b=%p\n", c->rank,
-            (unsigned long long)s->steps, (void*)b, s->cur, (int)cur.described, (int)cur.pulled, (void*)cur.b, (int)s->next_armed,
-            (void*)s->next_b);
-  if (!(cur.described && cur.b == b)) {
-    // not announced: describe it now (its counts over the collectives' stream, one host wait)
-    DFH_ARG(!cur.described || !cur.pulled, "dfh_shard_step: the batch differs from the one announced to dfh_shard_prefetch_counts");
-    if (b && b->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, b->ev_ready, 0));
-    {
-      StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
-      rc = queue_counts(s, b, cs);
-      if (rc) return rc;
-    }
-    DFH_HIP(hipStreamSynchronize(cs));
-    flight_sizes(s, cur, b, s->cur);
-  }
-  if (any_active) *any_active = cur.active != 0 ? 1 : 0;
-  ++s->steps;
-  if (b) b->nrows_seen += (float)b->nrows;
-  // the minibatch after this one, if the caller named it
-  const bool look = s->next_armed;
-  dfh_batch* nb = look ? s->next_b : nullptr;
-  s->next_armed = false;
-  dfh_shard::Flight& nxt = s->fl[s->cur ^ 1];
-  nxt = dfh_shard::Flight();
-  if (cur.active == 0) {
-    // nobody has a minibatch: the epoch is over (nothing can have been announced behind it)
-    cur = dfh_shard::Flight();
-    return b ? main_end(b) : DFH_OK;
-  }
-  rc = flight_bufs(s, cur, stride);
-  if (rc) return rc;
-  if (b) {
-    rc = main_begin(b);  // its Localizer (preparation stream) -> main stream
-    if (rc) return rc;
-    // (the split list of THIS minibatch: every launch that appends to it — L's, or F's k_uw_remote at the pipeline fill — is
-    // made below, in this call, on this stream, behind this batch object's previous update; none for the next minibatch)
-  }
-  // ---- L: this rank's own keys: rows + Push(kFeaCount) on its own table, {row, w} per key for the forward.  Runs
-  // after everything the previous step applied: own keys are read with zero staleness.
-  const uint32_t n_own = cur.own_hi - cur.own_lo;
-  // the row words of the others' keys ride in this launch when their rows are already on their way (every step but an
-  // epoch's first): one launch boundary less on the main stream
-  const bool uw_folded = cur.any_own && cur.pulled && cur.any_remote && b != nullptr;
-  if (cur.any_own) {
-    if (int rcr = table_reserve(t, n_own)) return rcr;
-    StageScope ts(s, DFH_SHARD_STAGE_L, st);
-    const bool counts = push_cnt != 0;
-    const float* cntp = (counts && b->has_cnt) ? b->d_feacnt + cur.own_lo : (const float*)nullptr;
-    const int mode = counts ? ((is_train && ctx->upd_kernel) ? 2 : 1) : 0;
-    if (uw_folded) {
-      DFH_HIP(hipStreamWaitEvent(st, s->ev_rw[cur.slot], 0));  // the rows of the other owners have arrived
-      const UwRemote m{s->w_rows[cur.slot], stride, b->d_U, cur.own_lo, cur.own_hi, b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err};
-      hipLaunchKernelGGL(k_lookup_uw_remote, dim3(grid_for_threads(cur.U, ctx)), dim3(256), 0, st, t->v, b->d_feaids + cur.own_lo, n_own,
-                         b->d_urow + cur.own_lo, cntp, b->d_col_ptr + cur.own_lo, mode, b->d_uw + cur.own_lo, auc_pending(b), m,
-                         split_out(ctx, b, is_train, cur.own_lo));
-    } else {
-      hipLaunchKernelGGL(k_lookup_step, dim3(grid_for_threads(n_own, ctx)), dim3(256), 0, st, t->v, b->d_feaids + cur.own_lo,
-                         (const uint32_t*)nullptr, n_own, b->d_urow + cur.own_lo, cntp, b->d_col_ptr + cur.own_lo, mode, (uint32_t*)nullptr,
-                         0, b->d_uw + cur.own_lo, auc_pending(b), split_out(ctx, b, is_train, cur.own_lo));
-    }
-    b->auc_pending_n = 0;
-    DFH_HIP(hipGetLastError());
-  }
-  if (!cur.pulled) {  // pipeline fill: K, R, RW of this very minibatch, in the sync step's order (after L)
-    rc = flight_K(s, cur, push_cnt);
-    if (rc) return rc;
-    rc = flight_R_RW(s, cur, push_cnt);
-    if (rc) return rc;
-  }
-  // ---- counts of the next minibatch: on their way while F is queued and runs
-  if (look) {
-    if (nb && nb->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, nb->ev_ready, 0));
-    StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
-    rc = queue_counts(s, nb, cs);
-    if (rc) return rc;
-    DFH_HIP(hipEventRecord(s->cnt_ev, cs));
-  }
-  // ---- F: the worker's math: own keys on the table, the others on the pulled rows
-  const KeyRange own{cur.own_lo, cur.own_hi, 0u}, others{cur.own_lo, cur.own_hi, 1u}, others_pen{cur.own_lo, cur.own_hi, 3u};
-  const int q = cur.slot;
-  // BinClassMetric::AUC of the minibatch: rides in the own keys' update launch of a training step (k_update_fused has idle
-  // VALUs), a launch of its own otherwise
-  const bool mixed = b && is_train && cur.any_remote && ctx->upd_kernel != 0 && ctx->shard_mixed_update != 0;  // (see the sync step)
-  bool auc_rides = b && b->compute_auc && is_train && (cur.any_own || mixed) && ctx->auc_in_update != 0 && ctx->upd_kernel != 0;
-  if (b) {
-    StageScope ts(s, DFH_SHARD_STAGE_F, st);
-    rc = ensure_xv(b, kp);
-    if (rc) return rc;
-    if (!uw_folded) DFH_HIP(hipStreamWaitEvent(st, s->ev_rw[q], 0));  // the rows of the other owners have arrived
-    const RowSrc tsrc = table_src(t, b->d_urow);
-    if (cur.any_remote && !uw_folded) {
-      hipLaunchKernelGGL(k_uw_remote, dim3(grid_for_threads(cur.U, ctx)), dim3(256), 0, st, s->w_rows[q], stride, b->d_U, cur.own_lo,
-                         cur.own_hi, b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err);
-      DFH_HIP(hipGetLastError());
-    }
-    MixSrc mix{cur.any_remote ? s->w_rows[q] + 4 : nullptr, stride};
-    rc = launch_forward(b, tsrc, k, kp, b->d_uw, &mix);
-    if (rc) return rc;
-    if (b->compute_auc && !auc_rides) {
-      rc = launch_auc(b);
-      if (rc) return rc;
-    }
-    BatchView bv = batch_view(b);
-    const int pgrid = cur.have ? std::min(grid_for_waves(b->nnz, ctx), PROG_SLOTS) : 1;
-    if (cur.any_remote && !is_train) {  // EvaluatePenalty over the pulled weights (sgd_learner.cc:249-273)
-      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, bv, packed_src(s->w_rows[q], k), t->v, k, kp, others);
-      DFH_HIP(hipGetLastError());
-    }
-    if (mixed) {  // gradient rows of the others' keys AND the own keys' in-place update, one launch
-      const bool with_auc = auc_rides && b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
-      rc = launch_update_fused(b, t->v, k, kp, b->d_need, b->d_uw, kAllKeys, push_cnt != 0, with_auc, s->w_rows[q], s->w_grads[q], stride);
-      if (rc) return rc;
-      if (auc_rides && !with_auc) {
-        rc = launch_auc(b);
-        if (rc) return rc;
-      }
-    } else if (is_train && cur.any_remote) {  // the gradient-row launch reads every pulled row anyway: it adds up their penalty too
-      rc = launch_backward<false>(b, packed_src(s->w_rows[q], k), t->v, s->w_grads[q], stride, k, kp, nullptr, others_pen);
-      if (rc) return rc;
-    }
-  }
-  if (is_train) DFH_HIP(hipEventRecord(s->ev_f, st));  // the gradient rows are complete: G may start ...
-  if (b && !mixed) {  // ... while the own keys are updated in place
-    StageScope ts(s, DFH_SHARD_STAGE_F, st);
-    const RowSrc tsrc = table_src(t, b->d_urow);
-    if (is_train && cur.any_own) {  // the fused in-place update accumulates the own keys' penalty itself
-      const bool auc_wanted = auc_rides;
-      rc = launch_backward<true>(b, tsrc, t->v, nullptr, 0, k, kp, b->d_need, own, b->d_uw, push_cnt != 0 && ctx->upd_kernel != 0,
-                                 &auc_rides);
-      if (rc) return rc;
-      if (auc_wanted && !auc_rides) {  // the minibatch is beyond the pair-counting size
-        rc = launch_auc(b);
-        if (rc) return rc;
-      }
-    } else if (cur.any_own) {
-      BatchView bv = batch_view(b);
-      const int pgrid = cur.have ? std::min(grid_for_waves(b->nnz, ctx), PROG_SLOTS) : 1;
-      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, bv, tsrc, t->v, k, kp, own);
-      DFH_HIP(hipGetLastError());
-    }
-  }
-  // ---- the next minibatch's sizes (the one host wait; the device is busy with F), then its keys
-  bool ahead = false;
-  if (look) {
-    DFH_HIP(hipEventSynchronize(s->cnt_ev));
-    flight_sizes(s, nxt, nb, s->cur ^ 1);
-    ahead = nxt.active != 0;
-    if (trace)
-      fprintf(stderr, "[shard %d]   next: active %zu U %zu nrecv %zu own [%u, %u) -> ahead %d\n", c->rank, nxt.active, nxt.U, nxt.nrecv,
-              nxt.own_lo, nxt.own_hi, (int)ahead);
-    if (ahead) {
-      rc = flight_bufs(s, nxt, stride);
-      if (rc) return rc;
-      rc = flight_K(s, nxt, push_cnt);  // small; travels while F computes
-      if (rc) return rc;
-    }
-  }
-  // ---- G: gradient rows to the owners (into the buffer their rows came from)
-  std::vector<size_t> sb, rb, so;
-  if (is_train) {
-    StageScope ts(s, DFH_SHARD_STAGE_G, cs);
-    DFH_HIP(hipStreamWaitEvent(cs, s->ev_f, 0));
-    flight_bytes(cur, W, stride * sizeof(float), sb, rb, so);
-    XPart x{s->w_grads[q], sb.data(), so.data(), s->r_rows[q], rb.data(), nullptr};
-    rc = comm_exchange(c, &x, 1, cs, DFH_XCHG_GRADS);
-    if (rc) return rc;
-    DFH_HIP(hipEventRecord(s->ev_g, cs));
-  }
-  // ---- R, RW of the next minibatch: the owners pull while this step's gradients travel — before they are applied
-  // (staleness 1 for the rows of other owners) — and the rows travel while they are applied
-  if (ahead) {
-    rc = flight_R_RW(s, nxt, push_cnt);
-    if (rc) return rc;
-  }
-  // ---- P: the other sources' gradients, applied source rank after source rank
-  if (is_train) {
-    StageScope ts(s, DFH_SHARD_STAGE_P, st);
-    DFH_HIP(hipStreamWaitEvent(st, s->ev_g, 0));
-    if (cur.nrecv) {
-      rc = !cur.listed ? dfh_shard_push_grad_multi(t, s->r_rowid[q], s->r_keys[q], cur.seg.data(), W, q, s->r_rows[q])
-                             : dfh_shard_push_grad_listed(t, s->r_rowid[q], s->r_keys[q], cur.seg.data(), W, q, s->r_rows[q]);
-      if (rc) return rc;
-    }
-  } else if (cur.nrecv) {
-    rc = dfh_shard_release(t, s->r_rowid[q], cur.nrecv, q);
-    if (rc) return rc;
-  }
-  if (cur.nrecv) {  // r_keys[q] / r_rowid[q] / r_rows[q] are free again once this point of the main stream is reached
-    DFH_HIP(hipEventRecord(s->ev_p[q], st));
-    s->p_pending[q] = true;
-  }
-  cur = dfh_shard::Flight();
-  if (look) s->cur ^= 1;  // the announced minibatch (described, maybe pulled) is the next call's
-  return b ? main_end(b) : DFH_OK;
-}
-}  // namespace
 
 namespace {
 // ---- the literal, call-by-call Store::Pull / Push on the sharded model (dfh_shard_pull_host / dfh_shard_push_host)
@@ -1642,24 +1531,6 @@ int host_call_sizes(dfh_shard* s, const uint64_t* keys, size_t n, HostCall* h) {
     h->seg[p + 1] = h->seg[p] + h->recv[p];
   }
   h->nrecv = h->seg[W];
-  return DFH_OK;
-}
-
-int host_call_bufs(dfh_shard* s, size_t nrecv, size_t n, size_t stride) {
-  hipStream_t st = s->t->ctx->stream;
-  int rc;
-  if (nrecv > s->r_cap[0]) {
-    const size_t cap = nrecv + nrecv / 2 + 1024;
-    if ((rc = grow(&s->r_keys[0], cap, st)) || (rc = grow(&s->r_cnt[0], cap, st)) || (rc = grow(&s->r_rowid[0], multi_words(cap, s->c->world), st)) ||
-        (rc = grow(&s->r_rows[0], cap * stride, st)))
-      return rc;
-    s->r_cap[0] = cap;
-  }
-  if (n > s->w_cap[0]) {
-    const size_t cap = n + n / 2 + 1024;
-    if ((rc = grow(&s->w_rows[0], cap * stride, st))) return rc;
-    s->w_cap[0] = cap;
-  }
   return DFH_OK;
 }
 
@@ -1699,7 +1570,7 @@ int dfh_shard_pull_host(dfh_shard* s, const uint64_t* keys, size_t n, float* val
   HostCall h;
   int rc = host_call_sizes(s, keys, n, &h);
   if (rc) return rc;
-  rc = host_call_bufs(s, h.nrecv, n, stride);
+  rc = slot_bufs(s, 0, h.nrecv, n, 0, true);
   if (rc) return rc;
   rc = ensure_scratch(ctx, padded<uint64_t>(std::max<size_t>(n, 1)));
   if (rc) return rc;
@@ -1785,7 +1656,7 @@ int dfh_shard_push_host(dfh_shard* s, const uint64_t* keys, size_t n, int val_ty
   HostCall h;
   int rc = host_call_sizes(s, keys, n, &h);
   if (rc) return rc;
-  rc = host_call_bufs(s, h.nrecv, n, stride);
+  rc = slot_bufs(s, 0, h.nrecv, n, 0, true);
   if (rc) return rc;
   rc = ensure_scratch(ctx, padded<uint64_t>(std::max<size_t>(n, 1)) + padded<float>(std::max<size_t>(n, 1)));
   if (rc) return rc;
