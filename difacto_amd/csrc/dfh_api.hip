@@ -618,6 +618,27 @@ constexpr size_t kSmallBatchPairs = 16384;  // at or below: no probe ahead on th
 // (forward declared: the rider helpers live next to the Localizer's host code further down)
 void collect_riders(dfh_ctx* c, int slot, bool can_ride, uint32_t main_groups, RiderSet* rs);
 
+// One kernel launch.  timed: the dispatch itself carries the two events (hipExtLaunchKernelGGL), so the span is the kernel's
+// own begin / end as the command processor stamps them — what a profiler reports — and no marker packet drains the stream
+// around it.  Otherwise the plain launch.  (The arguments are converted to the kernel's parameter types here: the timed
+// form packs them as it gets them.)
+template <typename... P, typename... A>
+void launch_span(dfh_ctx* c, bool timed, int kid, int ride, void (*kernel)(P...), dim3 grid, dim3 block, size_t shm, hipStream_t s,
+                 const A&... args) {
+  hipEvent_t ea = timed ? TimeScope::get(c) : nullptr, eb = timed ? TimeScope::get(c) : nullptr;
+  if (ea && eb) {
+    hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)shm, s, ea, eb, 0, static_cast<P>(args)...);
+    c->spans.push_back({kid, ea, eb, ride});
+  } else {
+    hipLaunchKernelGGL(kernel, grid, block, shm, s, static_cast<P>(args)...);
+  }
+}
+// a launch of kernel class kid (DFH_K_*): timed when dfh_ctx_set_timing turned that class on
+template <typename... P, typename... A>
+void launch_k(dfh_ctx* c, int kid, void (*kernel)(P...), dim3 grid, dim3 block, size_t shm, hipStream_t s, const A&... args) {
+  launch_span(c, ((c->timing >> kid) & 1u) != 0, kid, 0, kernel, grid, block, shm, s, args...);
+}
+
 int launch_forward(dfh_batch* b, const RowSrc& src, int k, int kp, const uint2* uw = nullptr, const MixSrc* mix = nullptr,
                    bool riders = false) {
   BatchView bv = batch_view(b);
@@ -625,55 +646,33 @@ int launch_forward(dfh_batch* b, const RowSrc& src, int k, int kp, const uint2* 
   // one wave per example, all resident at once where possible: the kernel is
   // bound by the latency of its dependent gathers, not by launch size
   int grid = (int)std::max<size_t>(1, std::min<size_t>((b->nrows + 3) / 4, PROG_SLOTS));
-  hipStream_t s = b->ctx->stream;
-  const int fwd_depth = b->ctx->fwd_depth;
-  if (b->ctx->fwd_blocks > 0) grid = std::min(grid, b->ctx->fwd_blocks);
-  // timing: the dispatch itself carries the two events (hipExtLaunchKernelGGL), so the span is the
-  // kernel's own begin/end as the command processor stamps them — what a profiler reports — and no
-  // marker packet drains the stream around it
   dfh_ctx* c = b->ctx;
-  hipEvent_t ea = nullptr, eb = nullptr;
-  if ((c->timing >> DFH_K_FORWARD) & 1u) {
-    ea = TimeScope::get(c);
-    eb = TimeScope::get(c);
-  }
+  hipStream_t s = c->stream;
+  const int fwd_depth = c->fwd_depth;
+  if (c->fwd_blocks > 0) grid = std::min(grid, c->fwd_blocks);
   MixSrc mx{nullptr, 0};
   if (mix) mx = *mix;
   // single-queue step: the stages of later minibatches' Localizer that belong into a forward launch ride in this one
   RiderSet rs;
   rs.n = 0;
   if (riders && c->single_queue) collect_riders(c, 1, !mix && fwd_depth == 5, ((uint32_t)grid + 7u) / 8u, &rs);
-  if (rs.n) {
-    const dim3 rgrid((((unsigned)grid + 7u) / 8u + rs.ngroups) * 8u);
-    const size_t shm = std::max<size_t>(rider_smem(rs), 4 * sizeof(double));
-    int rcr = dispatch_L(kp, [&](auto Lc) {
-      constexpr int L = decltype(Lc)::value;
-      if (ea && eb) hipExtLaunchKernelGGL((k_forward_riders<L, 5>), rgrid, dim3(256), shm, s, ea, eb, 0, bv, src, k, kp, (uint32_t)grid, rs);
-      else hipLaunchKernelGGL((k_forward_riders<L, 5>), rgrid, dim3(256), shm, s, bv, src, k, kp, (uint32_t)grid, rs);
-    });
-    if (ea && eb) c->spans.push_back({DFH_K_FORWARD, ea, eb});
-    if (rcr) return rcr;
-    DFH_HIP(hipGetLastError());
-    return DFH_OK;
-  }
   int rc = dispatch_L(kp, [&](auto Lc) {
     constexpr int L = decltype(Lc)::value;
-#define DFH_FWD1(D, M)                                                                                                       \
-  if (ea && eb) hipExtLaunchKernelGGL((k_forward<L, D, M>), dim3(grid), dim3(256), 0, s, ea, eb, 0, bv, src, k, kp, mx); \
-  else hipLaunchKernelGGL((k_forward<L, D, M>), dim3(grid), dim3(256), 0, s, bv, src, k, kp, mx)
-#define DFH_FWD(D)                      \
-  if (mix) { DFH_FWD1(D, true); }       \
-  else { DFH_FWD1(D, false); }
+    if (rs.n) {
+      launch_k(c, DFH_K_FORWARD, k_forward_riders<L, 5>, dim3((((unsigned)grid + 7u) / 8u + rs.ngroups) * 8u), dim3(256),
+               std::max<size_t>(rider_smem(rs), 4 * sizeof(double)), s, bv, src, k, kp, (uint32_t)grid, rs);
+      return;
+    }
+    auto fwd = [&](auto kernel) { launch_k(c, DFH_K_FORWARD, kernel, dim3(grid), dim3(256), 0, s, bv, src, k, kp, mx); };
+#define DFH_FWD(D) mix ? fwd(k_forward<L, D, true>) : fwd(k_forward<L, D, false>)
     switch (fwd_depth) {
       case 4: DFH_FWD(4); break;
       case 10: DFH_FWD(10); break;
       case 8: DFH_FWD(8); break;
       default: DFH_FWD(5); break;
     }
-#undef DFH_FWD1
 #undef DFH_FWD
   });
-  if (ea && eb) c->spans.push_back({DFH_K_FORWARD, ea, eb});
   if (rc) return rc;
   DFH_HIP(hipGetLastError());
   return DFH_OK;
@@ -798,70 +797,41 @@ int launch_update_fused(dfh_batch* b, const TableView& tv, int k, int kp, uint32
   // the parts of keys with more than HOT_SPLIT_MIN occurrences: taken by the hot role's blocks before their own lists
   a.nb_split = (c->upd_split && nnz > HOT_SPLIT_MIN) ? (uint32_t)b->split_cap : 0u;
   const size_t nb_single = std::max<size_t>(1, std::min<size_t>((b->nrows + UPD_NW - 1) / UPD_NW, (size_t)c->upd_single_blocks));
-  hipEvent_t ea = nullptr, eb = nullptr;  // timing rides on the dispatch, like the forward's
-  if ((c->timing >> DFH_K_BACKWARD) & 1u) {
-    ea = TimeScope::get(c);
-    eb = TimeScope::get(c);
-  }
   const dim3 grid((unsigned)(a.nb_auc + a.nb_hot + a.nb_mid + a.nb_few + nb_single)), block(UPD_THREADS);
   // single-queue step: the stages of later minibatches' Localizer that belong into an update launch ride in this one
   RiderSet rs;
   rs.n = 0;
   if (riders && c->single_queue) collect_riders(c, 2, !mixed && UPD_THREADS == RID_THREADS, (grid.x + 7u) / 8u, &rs);
-  if (rs.n) {
-    const dim3 rgrid(((grid.x + 7u) / 8u + rs.ngroups) * 8u);
-    const size_t shm = std::max<size_t>(rider_smem(rs), UPD_SMEM);
-    int rcr = dispatch_L(kp, [&](auto Lc) {
-      constexpr int LL = decltype(Lc)::value;
-#define DFH_UPDR(EXACT, HV)                                                                                                 \
-  if (ea && eb) hipExtLaunchKernelGGL((k_update_fused_riders<LL, EXACT, HV>), rgrid, block, shm, s, ea, eb, 0, a, grid.x, rs); \
-  else hipLaunchKernelGGL((k_update_fused_riders<LL, EXACT, HV>), rgrid, block, shm, s, a, grid.x, rs)
-      if (kp == 4 * LL) {
-        if (b->has_value) { DFH_UPDR(true, true); } else { DFH_UPDR(true, false); }
-      } else {
-        if (b->has_value) { DFH_UPDR(false, true); } else { DFH_UPDR(false, false); }
-      }
-#undef DFH_UPDR
-    });
-    if (ea && eb) c->spans.push_back({DFH_K_BACKWARD, ea, eb});
-    if (rcr) return rcr;
-    DFH_HIP(hipGetLastError());
-    return DFH_OK;
-  }
+  const bool exact = kp == 4 * L, hv = b->has_value;
   int rc = dispatch_L(kp, [&](auto Lc) {
     constexpr int LL = decltype(Lc)::value;
-#define DFH_UPD(EXACT, HV)                                                                                         \
-  if (mixed) {                                                                                                     \
-    if (ea && eb) hipExtLaunchKernelGGL((k_update_fused<LL, EXACT, HV, true>), grid, block, 0, s, ea, eb, 0, a);    \
-    else hipLaunchKernelGGL((k_update_fused<LL, EXACT, HV, true>), grid, block, 0, s, a);                           \
-  } else {                                                                                                         \
-    if (ea && eb) hipExtLaunchKernelGGL((k_update_fused<LL, EXACT, HV, false>), grid, block, 0, s, ea, eb, 0, a);   \
-    else hipLaunchKernelGGL((k_update_fused<LL, EXACT, HV, false>), grid, block, 0, s, a);                          \
-  }
-    if (kp == 4 * LL) {
-      if (b->has_value) { DFH_UPD(true, true); } else { DFH_UPD(true, false); }
-    } else {
-      if (b->has_value) { DFH_UPD(false, true); } else { DFH_UPD(false, false); }
+    if (rs.n) {
+      auto upd = [&](auto kernel) {
+        launch_k(c, DFH_K_BACKWARD, kernel, dim3(((grid.x + 7u) / 8u + rs.ngroups) * 8u), block, std::max<size_t>(rider_smem(rs), UPD_SMEM), s,
+                 a, grid.x, rs);
+      };
+#define DFH_UPD(EXACT, HV) upd(k_update_fused_riders<LL, EXACT, HV>)
+      exact ? (hv ? DFH_UPD(true, true) : DFH_UPD(true, false)) : (hv ? DFH_UPD(false, true) : DFH_UPD(false, false));
+#undef DFH_UPD
+      return;
     }
+    auto upd = [&](auto kernel) { launch_k(c, DFH_K_BACKWARD, kernel, grid, block, 0, s, a); };
+#define DFH_UPD(EXACT, HV) (mixed ? upd(k_update_fused<LL, EXACT, HV, true>) : upd(k_update_fused<LL, EXACT, HV, false>))
+    exact ? (hv ? DFH_UPD(true, true) : DFH_UPD(true, false)) : (hv ? DFH_UPD(false, true) : DFH_UPD(false, false));
 #undef DFH_UPD
   });
-  if (ea && eb) c->spans.push_back({DFH_K_BACKWARD, ea, eb});
   if (rc) return rc;
   DFH_HIP(hipGetLastError());
   return DFH_OK;
 }
 
+// with_auc: the minibatch's AUC rides in the launch — the caller has made sure that the launch is k_update_fused (step_math)
 template <bool FUSED>
 int launch_backward(dfh_batch* b, const RowSrc& src, const TableView& tv, float* grads, size_t gstride, int k, int kp,
-                    uint32_t* need, KeyRange rg = kAllKeys, const uint2* uw = nullptr, bool add_cnt = false, bool* auc_rides = nullptr,
+                    uint32_t* need, KeyRange rg = kAllKeys, const uint2* uw = nullptr, bool add_cnt = false, bool with_auc = false,
                     bool riders = false) {
-  if (FUSED && src.urow && uw && b->ctx->upd_kernel) {
-    // auc_rides: in: the caller wants the minibatch's AUC; out: this launch computed it
-    const bool with_auc = auc_rides && *auc_rides && b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
-    if (auc_rides) *auc_rides = with_auc;
+  if (FUSED && src.urow && uw && b->ctx->upd_kernel)
     return launch_update_fused(b, tv, k, kp, need, uw, rg, add_cnt, with_auc, nullptr, nullptr, 0, riders);
-  }
-  if (auc_rides) *auc_rides = false;
   if (riders) {  // no rider form of k_backward_all: the stages due in an update launch run alone
     RiderSet none;
     collect_riders(b->ctx, 2, false, 0, &none);
@@ -884,34 +854,137 @@ int launch_backward(dfh_batch* b, const RowSrc& src, const TableView& tv, float*
   const size_t small_cap = (size_t)c->bwd_small_blocks;
   const size_t keys_per_block = NWB * (64 / L);
   const size_t nb_small = std::max<size_t>(1, std::min<size_t>((b->nnz + keys_per_block - 1) / keys_per_block, small_cap));
-  hipEvent_t ea = nullptr, eb = nullptr;  // timing rides on the dispatch, like the forward's
-  if ((c->timing >> DFH_K_BACKWARD) & 1u) {
-    ea = TimeScope::get(c);
-    eb = TimeScope::get(c);
-  }
   const dim3 grid((unsigned)(nb_hot + nb_mid + nb_small)), block(BWD_THREADS);
   const uint32_t nh = (uint32_t)nb_hot, nm = (uint32_t)nb_mid, nlist = b->seg_nb;
   int rc = dispatch_L(kp, [&](auto Lc) {
     constexpr int LL = decltype(Lc)::value;
     const bool lean = FUSED && src.urow;
-#define DFH_BWD(LEAN, EXACT)                                                                                          \
-  if (ea && eb)                                                                                                       \
-    hipExtLaunchKernelGGL((k_backward_all<LL, FUSED, LEAN, EXACT>), grid, block, 0, s, ea, eb, 0, bv, src, tv, grads, \
-                          gstride, k, kp, need, nh, nm, nlist, rg);                                                   \
-  else                                                                                                                \
-    hipLaunchKernelGGL((k_backward_all<LL, FUSED, LEAN, EXACT>), grid, block, 0, s, bv, src, tv, grads, gstride, k, kp, \
-                       need, nh, nm, nlist, rg)
-    if (lean && kp == 4 * LL) {
-      DFH_BWD(FUSED, true);
-    } else if (lean) {
-      DFH_BWD(FUSED, false);
-    } else {
-      DFH_BWD(false, false);
-    }
-#undef DFH_BWD
+    auto bwd = [&](auto kernel) {
+      launch_k(c, DFH_K_BACKWARD, kernel, grid, block, 0, s, bv, src, tv, grads, gstride, k, kp, need, nh, nm, nlist, rg);
+    };
+    if (lean && kp == 4 * LL) bwd(k_backward_all<LL, FUSED, FUSED, true>);
+    else if (lean) bwd(k_backward_all<LL, FUSED, FUSED, false>);
+    else bwd(k_backward_all<LL, FUSED, false, false>);
   });
-  if (ea && eb) c->spans.push_back({DFH_K_BACKWARD, ea, eb});
   if (rc) return rc;
+  DFH_HIP(hipGetLastError());
+  return DFH_OK;
+}
+
+// ---- The worker's two stages of a training step, each written once.  dfh_sgd_step is the schedule "every key is this
+// rank's own" over them; flight_L and flight_F (dfh_shard.hip) are the sharded store's, for the slice of the minibatch's
+// keys the rank owns, with the rows of the other owners beside it.
+
+// Push(kFeaCount) of a step: 0 none, 1 by the lookup, 2 deferred — a training step's update kernel rewrites every key's
+// header, so it takes the count push of the keys that have their V along (k_lookup then only reads them)
+inline int count_mode(const dfh_ctx* c, int is_train, int push_cnt) { return push_cnt ? ((is_train && c->upd_kernel) ? 2 : 1) : 0; }
+
+// what only the single-GPU schedule turns on: the sharded store refuses REFRAND tables, never resolves rows ahead of the
+// step, carries no riders and times its stages (StageScope) rather than the launches inside them
+struct StepExtras {
+  uint32_t* need = nullptr;  // REFRAND: the rows to initialise in key order after the launch (refrand_flush)
+  bool pre = false;          // the rows are resolved (dfh_batch_lookup on a preparation stream): no probe of the index
+  bool riders = false;       // single-queue step: stages of later minibatches' Localizer may ride in the launches
+  bool spans = false;        // the lookup and a separate AUC are timed like the ctx's other kernel classes
+};
+
+// Pull (key -> row) and, with push_cnt, Push(kFeaCount) (sgd_learner.cc:214-217) of keys [lo, lo + n) of the minibatch on
+// this rank's table, and {row, w} per key into d_uw for the forward (w is current: the previous step's update precedes this
+// launch on the stream), so that the forward touches nothing of a row but its V lines.  d_n: the count is *d_n (n bounds
+// it for the grid).  With pre what remains is one pass over the known rows; the count push stays here because it must
+// stay ordered with the previous step's update.  The pass that sees every unique key's segment also lists the parts of
+// the very hot ones for the update's split role, and its first block adds up the AUC slots the batch object's previous
+// step left behind.  rrows (overlap schedule): the rows of the other owners, U keys in all, complete at rows_in — the
+// launch waits for them and writes the row words of the others' keys too (k_lookup_uw_remote: one launch boundary less).
+int step_lookup(dfh_table* t, dfh_batch* b, int is_train, int push_cnt, uint32_t lo, const uint32_t* d_n, size_t n, const StepExtras& x,
+                const float* rrows = nullptr, size_t U = 0, hipEvent_t rows_in = nullptr) {
+  dfh_ctx* c = t->ctx;
+  hipStream_t s = c->stream;
+  const float* cnt = b->has_cnt ? b->d_feacnt + lo : (const float*)nullptr;
+  const int mode = count_mode(c, is_train, push_cnt), gl = grid_for_threads(n, c);
+  const uint32_t n_static = d_n ? 0u : (uint32_t)n;
+  // DFH_GAP_TRACE=1 (measurement): the lookup dispatch carries its own start / stop events, like the forward and the update,
+  // and dfh_ctx_get_timing prints the time between the end of one timed launch and the start of the next
+  static const bool gap_trace = getenv("DFH_GAP_TRACE") != nullptr;
+  const bool ride = x.spans && gap_trace && ((c->timing >> DFH_K_LOOKUP) & 1u);
+  TimeScope ts(c, (x.spans && !ride) ? DFH_K_LOOKUP : DFH_K_COUNT);
+  const SplitOut so = split_out(c, b, is_train, lo);
+  RiderSet rs;
+  rs.n = 0;
+  if (x.riders) collect_riders(c, 0, true, ((uint32_t)gl + 7u) / 8u, &rs);
+  if (rrows) {
+    DFH_HIP(hipStreamWaitEvent(s, rows_in, 0));
+    const UwRemote m{rrows, dfh_row_stride(t->v.k), b->d_U, lo, lo + (uint32_t)n, b->d_uw, b->d_col_ptr, split_out(c, b, is_train, 0u), t->v.err};
+    hipLaunchKernelGGL(k_lookup_uw_remote, dim3(grid_for_threads(U, c)), dim3(256), 0, s, t->v, b->d_feaids + lo, n_static, b->d_urow + lo,
+                       cnt, b->d_col_ptr + lo, mode, b->d_uw + lo, auc_pending(b), m, so);
+  } else if (rs.n) {
+    hipLaunchKernelGGL(k_lookup_riders, dim3((((unsigned)gl + 7u) / 8u + rs.ngroups) * 8u), dim3(256), rider_smem(rs), s, t->v,
+                       b->d_feaids + lo, d_n, n_static, b->d_urow + lo, cnt, b->d_col_ptr + lo, mode, x.need, x.pre ? 1 : 0, b->d_uw + lo,
+                       auc_pending(b), so, (uint32_t)gl, rs);
+  } else {
+    launch_span(c, ride, DFH_K_LOOKUP, 1, k_lookup_step, dim3(gl), dim3(256), 0, s, t->v, b->d_feaids + lo, d_n, n_static, b->d_urow + lo,
+                cnt, b->d_col_ptr + lo, mode, x.need, x.pre ? 1 : 0, b->d_uw + lo, auc_pending(b), so);
+  }
+  b->auc_pending_n = 0;
+  DFH_HIP(hipGetLastError());
+  return DFH_OK;
+}
+
+// the keys of other ranks in the minibatch (sharded store): the rows their owners sent, the gradient rows that go back
+struct StepRemote {
+  const float* rows;  // row u belongs to key u of the minibatch; NULL: this minibatch has keys of this rank only
+  float* grads;
+  size_t stride;
+};
+
+// FMLoss::Predict, BinClassMetric::AUC of the minibatch (sgd_learner.cc:153-155), then EvaluatePenalty (a validation step)
+// or CalcGrad and the update: the keys in `own` on the table in place; with rem, the others on the pulled rows — their
+// part leaves gradient rows and comes first.  d_uw holds {row, w} of every key (step_lookup, k_uw_remote).  between(bool):
+// called once the others' gradient rows are queued, told whether a launch for the own keys is still to come.
+template <typename Between>
+int step_math(dfh_table* t, dfh_batch* b, int is_train, int push_cnt, KeyRange own, const StepRemote* rem, const StepExtras& x,
+              Between&& between) {
+  dfh_ctx* c = t->ctx;
+  hipStream_t s = c->stream;
+  const int k = t->v.k, kp = t->v.kp;
+  const bool any_own = b->nnz > 0 && own.hi > own.lo, any_remote = rem && rem->rows;
+  const bool add_cnt = count_mode(c, is_train, push_cnt) == 2;
+  // with keys of other ranks in the minibatch ONE launch of k_update_fused<MIXED> serves all keys — gradient rows for the
+  // others' keys, the in-place update for the own ones (ctx option shard_mixed_update = 0: a launch each)
+  const bool mixed = is_train && any_remote && c->upd_kernel != 0 && c->shard_mixed_update != 0;
+  // the AUC rides in the update launch of a training step's own keys (k_update_fused: the pair counting is VALU work beside
+  // a memory-bound kernel); where there is no such launch, or the minibatch is beyond the pair-counting size, it is a
+  // launch of its own behind the forward
+  const bool auc_rides = b->compute_auc && is_train && (any_own || mixed) && c->auc_in_update != 0 && c->upd_kernel != 0 &&
+                         b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
+  const int pgrid = std::min(grid_for_waves(b->nnz, c), PROG_SLOTS);
+  const RowSrc src = table_src(t, b->d_urow);
+  RiderSet none;  // (stages of later minibatches due in a launch this step does not make: they run alone)
+  // one rank: no MixSrc at all, the forward that reads the table only
+  const MixSrc mix{any_remote ? rem->rows + 4 : nullptr, rem ? rem->stride : 0};
+  int rc = launch_forward(b, src, k, kp, b->d_uw, rem ? &mix : nullptr, x.riders);
+  if (rc) return rc;
+  if (b->compute_auc && !auc_rides) {
+    TimeScope ts(c, x.spans ? DFH_K_AUC : DFH_K_COUNT);
+    rc = launch_auc(b);
+    if (rc) return rc;
+  }
+  if (mixed) {
+    rc = launch_update_fused(b, t->v, k, kp, b->d_need, b->d_uw, kAllKeys, add_cnt, auc_rides, rem->rows, rem->grads, rem->stride);
+  } else if (any_remote && is_train) {  // the gradient-row launch reads every pulled row anyway: it adds up their penalty too
+    rc = launch_backward<false>(b, packed_src(rem->rows, k), t->v, rem->grads, rem->stride, k, kp, nullptr, KeyRange{own.lo, own.hi, 3u});
+  } else if (any_remote) {  // EvaluatePenalty over the pulled weights (sgd_learner.cc:249-273)
+    hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, s, batch_view(b), packed_src(rem->rows, k), t->v, k, kp,
+                       KeyRange{own.lo, own.hi, 1u});
+    DFH_HIP(hipGetLastError());
+  }
+  if (rc) return rc;
+  if ((rc = between(!mixed))) return rc;
+  if (mixed || !any_own) return DFH_OK;
+  if (is_train)  // the fused in-place update accumulates the own keys' penalty itself
+    return launch_backward<true>(b, src, t->v, nullptr, 0, k, kp, b->d_need, own, b->d_uw, add_cnt, auc_rides, x.riders);
+  if (x.riders) collect_riders(c, 2, false, 0, &none);
+  hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, s, batch_view(b), src, t->v, k, kp, own);
   DFH_HIP(hipGetLastError());
   return DFH_OK;
 }
@@ -1367,11 +1440,12 @@ int dfh_shard_push_grad(dfh_table* t, const uint64_t* d_keys, size_t n, const fl
     int rc = ensure_table_aux(t, n);
     if (rc) return rc;
   }
-  TimeScope* ts = new TimeScope(t->ctx, DFH_K_PUSH);
-  hipLaunchKernelGGL(k_push_grad, dim3(grid_for_waves(n, t->ctx)), dim3(256), 0, t->ctx->stream, t->v, d_keys,
-                     (uint32_t)n, d_grads, dfh_row_stride(t->v.k), refrand ? t->d_need : (uint32_t*)nullptr,
-                     refrand ? t->d_urow : (uint32_t*)nullptr);
-  delete ts;
+  {
+    TimeScope ts(t->ctx, DFH_K_PUSH);
+    hipLaunchKernelGGL(k_push_grad, dim3(grid_for_waves(n, t->ctx)), dim3(256), 0, t->ctx->stream, t->v, d_keys,
+                       (uint32_t)n, d_grads, dfh_row_stride(t->v.k), refrand ? t->d_need : (uint32_t*)nullptr,
+                       refrand ? t->d_urow : (uint32_t*)nullptr);
+  }
   DFH_HIP(hipGetLastError());
   if (refrand) return refrand_flush(t, d_keys, nullptr, (uint32_t)n, t->d_urow, t->d_need, t->d_rank, t->d_total);
   return DFH_OK;
@@ -3460,89 +3534,28 @@ int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt) {
   }
   const bool refrand = t->v.p.init_mode == DFH_INIT_REFRAND && k > 0;
   const uint32_t Nb = (uint32_t)b->nnz;  // upper bound of U for grids
-  if (b->looked_up != t) {  // the step's own lookup probes the index: up to U <= nnz new keys
+  // every key is this rank's own; what dfh_batch_lookup resolved on a preparation stream is not probed again
+  const StepExtras x{refrand ? b->d_need : nullptr, b->looked_up == t, true, true};
+  if (!x.pre) {  // the step's own lookup probes the index: up to U <= nnz new keys
     rc = table_reserve(t, Nb);
     if (rc) return rc;
   }
   rc = main_begin(b);
   if (rc) return rc;
-  // Pull: key -> row (+ epoch-0 Push(kFeaCount), sgd_learner.cc:214-217).  When dfh_batch_lookup
-  // already resolved the rows on a preparation stream, what remains here is one pass over the
-  // known rows: the count push (it must stay ordered with the previous step's update) and
-  // {row, w} per key for the forward (w is current: the previous step's update precedes it on this
-  // stream), so that the forward touches nothing of a row but its V lines.
-  const bool pre = b->looked_up == t;
-  uint2* uw = b->d_uw;
-  // a training step's update kernel rewrites every key's header: it takes the count push of the keys that have their V
-  // along (k_lookup then only reads them)
-  const bool defer_cnt = push_cnt && is_train && c->upd_kernel != 0;
-  {
-    // DFH_GAP_TRACE=1 (measurement): the step's lookup dispatch carries its own start / stop events, like the forward and the
-    // update, and dfh_ctx_get_timing prints the time between the end of one timed launch and the start of the next
-    static const bool gap_trace = getenv("DFH_GAP_TRACE") != nullptr;
-    hipEvent_t la = nullptr, lb = nullptr;
-    if (gap_trace && ((c->timing >> DFH_K_LOOKUP) & 1u)) {
-      la = TimeScope::get(c);
-      lb = TimeScope::get(c);
-    }
-    TimeScope ts(c, (la && lb) ? DFH_K_COUNT : DFH_K_LOOKUP);
-    // (the lookup's first block also adds up the AUC slots this batch object's previous step left behind)
-    const int gl = grid_for_threads(Nb, c);
-    // the pass that sees every unique key's segment lists the parts of the very hot ones for the update's split role
-    const SplitOut so = split_out(c, b, is_train, 0u);
-    RiderSet rs;  // single-queue step: the stages of later minibatches' Localizer that belong into this launch
-    collect_riders(c, 0, true, ((uint32_t)gl + 7u) / 8u, &rs);
-    if (rs.n)
-      hipLaunchKernelGGL(k_lookup_riders, dim3((((unsigned)gl + 7u) / 8u + rs.ngroups) * 8u), dim3(256), rider_smem(rs), s, t->v, b->d_feaids,
-                         b->d_U, 0u, b->d_urow, b->has_cnt ? b->d_feacnt : (const float*)nullptr, b->d_col_ptr,
-                         push_cnt ? (defer_cnt ? 2 : 1) : 0, refrand ? b->d_need : (uint32_t*)nullptr, pre ? 1 : 0, uw, auc_pending(b),
-                         so, (uint32_t)gl, rs);
-    else if (la && lb) {
-      hipExtLaunchKernelGGL(k_lookup_step, dim3(gl), dim3(256), 0, s, la, lb, 0, t->v, b->d_feaids, b->d_U, 0u, b->d_urow,
-                            b->has_cnt ? b->d_feacnt : (const float*)nullptr, b->d_col_ptr, push_cnt ? (defer_cnt ? 2 : 1) : 0,
-                            refrand ? b->d_need : (uint32_t*)nullptr, pre ? 1 : 0, uw, auc_pending(b), so);
-      c->spans.push_back({DFH_K_LOOKUP, la, lb, 1});
-    } else
-    hipLaunchKernelGGL(k_lookup_step, dim3(gl), dim3(256), 0, s, t->v, b->d_feaids, b->d_U, 0u, b->d_urow,
-                       b->has_cnt ? b->d_feacnt : (const float*)nullptr, b->d_col_ptr, push_cnt ? (defer_cnt ? 2 : 1) : 0,
-                       refrand ? b->d_need : (uint32_t*)nullptr, pre ? 1 : 0, uw, auc_pending(b), so);
-    b->auc_pending_n = 0;
-  }
-  DFH_HIP(hipGetLastError());
+  rc = step_lookup(t, b, is_train, push_cnt, 0u, b->d_U, Nb, x);
+  if (rc) return rc;
   if (push_cnt && refrand) {
     rc = refrand_flush(t, b->d_feaids, b->d_U, Nb, b->d_urow, b->d_need, b->d_rank, b->d_total);
     if (rc) return rc;
   }
-  RowSrc src = table_src(t, b->d_urow);
-  rc = launch_forward(b, src, k, kp, uw, nullptr, true);
+  rc = step_math(t, b, is_train, push_cnt, kAllKeys, nullptr, x, [&](bool) -> int {
+    if (is_train && refrand) DFH_HIP(hipMemsetAsync(b->d_need, 0, (size_t)Nb * 4, s));  // (the update flags the rows it wants initialised)
+    return DFH_OK;
+  });
   if (rc) return rc;
-  // BinClassMetric::AUC of every minibatch (sgd_learner.cc:153-155): in a training step it rides in the update launch
-  // (k_update_fused: the pair counting is VALU work beside a memory-bound kernel), otherwise it is a launch of its own
-  bool auc_rides = b->compute_auc && is_train && c->auc_in_update != 0;
-  if (b->compute_auc && !auc_rides) {
-    TimeScope ts(c, DFH_K_AUC);
-    rc = launch_auc(b);
+  if (is_train && refrand) {
+    rc = refrand_flush(t, b->d_feaids, b->d_U, Nb, b->d_urow, b->d_need, b->d_rank, b->d_total);
     if (rc) return rc;
-  }
-  if (is_train) {
-    if (refrand) DFH_HIP(hipMemsetAsync(b->d_need, 0, (size_t)Nb * 4, s));
-    const bool wanted = auc_rides;
-    rc = launch_backward<true>(b, src, t->v, nullptr, 0, k, kp, b->d_need, kAllKeys, uw, defer_cnt, &auc_rides, true);
-    if (rc) return rc;
-    if (wanted && !auc_rides) {  // k_backward_all ran (upd_kernel = 0) or the minibatch is beyond the pair-counting size
-      TimeScope ts(c, DFH_K_AUC);
-      rc = launch_auc(b);
-      if (rc) return rc;
-    }
-    if (refrand) {
-      rc = refrand_flush(t, b->d_feaids, b->d_U, Nb, b->d_urow, b->d_need, b->d_rank, b->d_total);
-      if (rc) return rc;
-    }
-  } else {
-    BatchView bv = batch_view(b);
-    collect_riders(c, 2, false, 0, &none);
-    hipLaunchKernelGGL((k_penalty<1>), dim3(std::min(grid_for_waves(Nb, c), PROG_SLOTS)), dim3(256), 0, s, bv, src, t->v, k, kp, kAllKeys);
-    DFH_HIP(hipGetLastError());
   }
   return main_end(b);
 }

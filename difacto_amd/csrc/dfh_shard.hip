@@ -14,13 +14,15 @@
 //     R        owners: resolve keys -> rows once, Push(kFeaCount) per source, Pull (one gather)
 //     RW       rows --alltoallv--> workers          fixed stride dfh_row_stride(V_dim)
 //     F        FMLoss::Predict / Evaluate on a mixed source: own keys read the table in place, the others
-//              the pulled rows (k_forward<MIXED>); CalcGrad in two launches of k_backward_all: the others'
-//              keys into gradient rows, the own keys straight into the fused in-place update
+//              the pulled rows (k_forward<MIXED>); CalcGrad and the update in ONE launch of k_update_fused<MIXED>:
+//              gradient rows for the others' keys, the in-place update for the own ones (ctx option
+//              shard_mixed_update = 0: a launch each, the others' gradient rows first)
 //     G        gradients --alltoallv--> owners
 //     P        owners: Push(kGradient) of the other sources, applied in ascending rank order in ONE launch
 // A key's pushes are applied owner first, then the other sources in ascending rank order — one legal
 // execution of the reference's asynchronous Push protocol, the same on every run.  With one rank
-// nothing is exchanged and nothing waits for the host: the step is dfh_sgd_step.
+// nothing is exchanged and nothing waits for the host.  L and F are step_lookup and step_math (dfh_api.hip), the two
+// worker stages dfh_sgd_step is made of as well: with one rank both steps queue the same launches.
 // Every stage is one function of the minibatch's Flight (flight_L, flight_K, flight_R, flight_RW, flight_F, flight_G,
 // flight_P); the two exchange modes are two schedules over them: shard_step_sync (every stage on the context's stream, one
 // minibatch at a time in exchange slot 0) and shard_step_overlap (K, RW, G on a collectives' stream, two minibatches in
@@ -1006,39 +1008,19 @@ void flight_bytes(dfh_shard* s, const Flight& f, size_t unit) {
 // (profiles/r06o_owner_side_per_key.txt) — the default stays per entry.
 bool owner_per_entry(const dfh_table* t) { return !t->ctx->owner_per_key; }
 
-// L: this rank's own keys: rows + Push(kFeaCount) on its own table, {row, w} per key for the forward.  rows_in: the rows
-// of the other owners are already on their way (the overlap schedule, every step but an epoch's first) — the launch waits
-// for them and writes the row words of the others' keys too (k_lookup_uw_remote: one launch boundary less on the main
-// stream; F is then told uw_done)
+// L: this rank's own keys: rows + Push(kFeaCount) on its own table, {row, w} per key for the forward (step_lookup on
+// [own_lo, own_hi)).  rows_in: the rows of the other owners are already on their way (the overlap schedule, every step but
+// an epoch's first) — the launch waits for them and writes the row words of the others' keys too (F is then told uw_done)
 int flight_L(dfh_shard* s, Flight& f, int is_train, int push_cnt, hipEvent_t rows_in = nullptr) {
   if (!f.any_own) return DFH_OK;
   dfh_table* t = s->t;
-  dfh_ctx* ctx = t->ctx;
   dfh_batch* b = f.b;
-  hipStream_t st = ctx->stream;
-  const bool one = s->c->world == 1;           // the number of keys is on the device: rows and threads for nnz of them
-  const uint32_t n_own = f.own_hi - f.own_lo;  // meaningless with one rank (the kernel clamps to *d_U)
-  const size_t n = one ? (size_t)b->nnz : (size_t)n_own;
+  const bool one = s->c->world == 1;  // the number of keys is on the device (the kernel clamps to *d_U): rows and threads for nnz of them
+  const size_t n = one ? (size_t)b->nnz : (size_t)(f.own_hi - f.own_lo);
   if (int rcr = table_reserve(t, n)) return rcr;
-  StageScope ts(s, DFH_SHARD_STAGE_L, st);
-  const bool counts = push_cnt != 0;
-  const float* cntp = (counts && b->has_cnt) ? b->d_feacnt + f.own_lo : (const float*)nullptr;
-  const int mode = counts ? ((is_train && ctx->upd_kernel) ? 2 : 1) : 0;
-  if (rows_in) {
-    DFH_HIP(hipStreamWaitEvent(st, rows_in, 0));  // the rows of the other owners have arrived
-    const size_t stride = dfh_row_stride(t->v.k);
-    const UwRemote m{s->w_rows[f.slot], stride, b->d_U, f.own_lo, f.own_hi, b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err};
-    hipLaunchKernelGGL(k_lookup_uw_remote, dim3(grid_for_threads(f.U, ctx)), dim3(256), 0, st, t->v, b->d_feaids + f.own_lo, n_own,
-                       b->d_urow + f.own_lo, cntp, b->d_col_ptr + f.own_lo, mode, b->d_uw + f.own_lo, auc_pending(b), m,
-                       split_out(ctx, b, is_train, f.own_lo));
-  } else {
-    hipLaunchKernelGGL(k_lookup_step, dim3(grid_for_threads(n, ctx)), dim3(256), 0, st, t->v, b->d_feaids + f.own_lo,
-                       one ? b->d_U : (const uint32_t*)nullptr, one ? 0u : n_own, b->d_urow + f.own_lo, cntp, b->d_col_ptr + f.own_lo, mode,
-                       (uint32_t*)nullptr, 0, b->d_uw + f.own_lo, auc_pending(b), split_out(ctx, b, is_train, f.own_lo));
-  }
-  b->auc_pending_n = 0;  // (the lookup's first block added up the AUC slots this batch object's previous step left)
-  DFH_HIP(hipGetLastError());
-  return DFH_OK;
+  StageScope ts(s, DFH_SHARD_STAGE_L, t->ctx->stream);
+  return step_lookup(t, b, is_train, push_cnt, f.own_lo, one ? b->d_U : (const uint32_t*)nullptr, n, StepExtras{},
+                     rows_in ? s->w_rows[f.slot] : (const float*)nullptr, f.U, rows_in);
 }
 
 // K: the keys other ranks own (+ their epoch-0 counts) to their owners.  Two message groups, one send and one receive per
@@ -1110,84 +1092,36 @@ int flight_RW(dfh_shard* s, Flight& f, hipStream_t st, hipEvent_t rows_out = nul
   return record_on(st, done);
 }
 
-// F: the worker's math: own keys on the table, the others on the pulled rows.  uw_done: L wrote the others' row words
-// (and waited for their rows); rows_in: the event to wait for otherwise.  grads_done: recorded between the gradient rows of
-// the others' keys and the own keys' in-place update, so that G may start while that runs — the stage is then timed in two
-// brackets around it
+// F: the worker's math (step_math): own keys on the table, the others on the pulled rows.  uw_done: L wrote the others' row
+// words (and waited for their rows); rows_in: the event to wait for otherwise.  grads_done: recorded between the gradient
+// rows of the others' keys and the own keys' in-place update, so that G may start while that runs — the stage is then
+// timed in two brackets around it
 int flight_F(dfh_shard* s, Flight& f, int is_train, int push_cnt, bool uw_done = false, hipEvent_t rows_in = nullptr,
              hipEvent_t grads_done = nullptr) {
   dfh_table* t = s->t;
   dfh_ctx* ctx = t->ctx;
   dfh_batch* b = f.b;
   hipStream_t st = ctx->stream;
-  const int q = f.slot, k = t->v.k, kp = t->v.kp;
-  const size_t stride = dfh_row_stride(k);
-  const KeyRange own{f.own_lo, f.own_hi, 0u}, others{f.own_lo, f.own_hi, 1u}, others_pen{f.own_lo, f.own_hi, 3u};
-  // round 5: with keys of other ranks in the minibatch ONE launch of k_update_fused<MIXED> serves all keys — gradient rows for
-  // the others' keys, the in-place update for the own ones (ctx option shard_mixed_update = 0: the two launches of round 4)
-  const bool mixed = b && is_train && f.any_remote && ctx->upd_kernel != 0 && ctx->shard_mixed_update != 0;
-  // BinClassMetric::AUC of the minibatch: rides in the own keys' update launch of a training step (k_update_fused has idle
-  // VALUs), a launch of its own otherwise
-  bool auc_rides = b && b->compute_auc && is_train && (f.any_own || mixed) && ctx->auc_in_update != 0 && ctx->upd_kernel != 0;
-  const int pgrid = f.have ? std::min(grid_for_waves(b->nnz, ctx), PROG_SLOTS) : 1;
-  int rc;
-  std::optional<StageScope> ts;
-  if (b) {
-    ts.emplace(s, DFH_SHARD_STAGE_F, st);
-    rc = ensure_xv(b, kp);
-    if (rc) return rc;
-    if ((rc = wait_on(st, rows_in))) return rc;  // the rows of the other owners have arrived
-    if (f.any_remote && !uw_done) {
-      hipLaunchKernelGGL(k_uw_remote, dim3(grid_for_threads(f.U, ctx)), dim3(256), 0, st, s->w_rows[q], stride, b->d_U, f.own_lo, f.own_hi,
-                         b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err);
-      DFH_HIP(hipGetLastError());
-    }
-    // one rank: no MixSrc at all, the forward that reads the table only
-    MixSrc mix{f.any_remote ? s->w_rows[q] + 4 : nullptr, stride};
-    rc = launch_forward(b, table_src(t, b->d_urow), k, kp, b->d_uw, s->c->world > 1 ? &mix : nullptr);
-    if (rc) return rc;
-    if (b->compute_auc && !auc_rides) {
-      rc = launch_auc(b);
-      if (rc) return rc;
-    }
-    if (f.any_remote && !is_train) {  // EvaluatePenalty over the pulled weights (sgd_learner.cc:249-273)
-      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, batch_view(b), packed_src(s->w_rows[q], k), t->v, k, kp, others);
-      DFH_HIP(hipGetLastError());
-    }
-    if (mixed) {  // gradient rows of the others' keys AND the own keys' in-place update, one launch
-      const bool with_auc = auc_rides && b->nrows <= AUC_PAIRS_MAX_N && UPD_THREADS == 256;
-      rc = launch_update_fused(b, t->v, k, kp, b->d_need, b->d_uw, kAllKeys, push_cnt != 0, with_auc, s->w_rows[q], s->w_grads[q], stride);
-      if (rc) return rc;
-      if (auc_rides && !with_auc) {  // the minibatch is beyond the pair-counting size
-        rc = launch_auc(b);
-        if (rc) return rc;
-      }
-    } else if (is_train && f.any_remote) {  // the gradient-row launch reads every pulled row anyway: it adds up their penalty too
-      rc = launch_backward<false>(b, packed_src(s->w_rows[q], k), t->v, s->w_grads[q], stride, k, kp, nullptr, others_pen);
-      if (rc) return rc;
-    }
+  const int q = f.slot;
+  if (!b) return record_on(st, is_train ? grads_done : nullptr);  // a rank out of data: nothing to wait for
+  std::optional<StageScope> ts(std::in_place, s, DFH_SHARD_STAGE_F, st);
+  int rc = ensure_xv(b, t->v.kp);
+  if (rc) return rc;
+  if ((rc = wait_on(st, rows_in))) return rc;  // the rows of the other owners have arrived
+  const StepRemote rem{f.any_remote ? s->w_rows[q] : nullptr, s->w_grads[q], dfh_row_stride(t->v.k)};
+  if (f.any_remote && !uw_done) {
+    hipLaunchKernelGGL(k_uw_remote, dim3(grid_for_threads(f.U, ctx)), dim3(256), 0, st, rem.rows, rem.stride, b->d_U, f.own_lo, f.own_hi,
+                       b->d_uw, b->d_col_ptr, split_out(ctx, b, is_train, 0u), t->v.err);
+    DFH_HIP(hipGetLastError());
   }
-  if (grads_done) {
-    ts.reset();
-    if (is_train) DFH_HIP(hipEventRecord(grads_done, st));  // the gradient rows are complete: G may start ...
-    if (b && !mixed) ts.emplace(s, DFH_SHARD_STAGE_F, st);  // ... while the own keys are updated in place
-  }
-  if (b && !mixed) {
-    if (is_train && f.any_own) {  // the fused in-place update accumulates the own keys' penalty itself
-      const bool auc_wanted = auc_rides;
-      rc = launch_backward<true>(b, table_src(t, b->d_urow), t->v, nullptr, 0, k, kp, b->d_need, own, b->d_uw,
-                                 push_cnt != 0 && ctx->upd_kernel != 0, &auc_rides);
-      if (rc) return rc;
-      if (auc_wanted && !auc_rides) {  // the minibatch is beyond the pair-counting size
-        rc = launch_auc(b);
-        if (rc) return rc;
-      }
-    } else if (f.any_own) {
-      hipLaunchKernelGGL((k_penalty<1>), dim3(pgrid), dim3(256), 0, st, batch_view(b), table_src(t, b->d_urow), t->v, k, kp, own);
-      DFH_HIP(hipGetLastError());
-    }
-  }
-  return DFH_OK;
+  return step_math(t, b, is_train, push_cnt, KeyRange{f.own_lo, f.own_hi, 0u}, s->c->world > 1 ? &rem : nullptr, StepExtras{},
+                   [&](bool own_follows) -> int {
+                     if (!grads_done) return DFH_OK;
+                     ts.reset();
+                     if (is_train) DFH_HIP(hipEventRecord(grads_done, st));  // the gradient rows are complete: G may start ...
+                     if (own_follows) ts.emplace(s, DFH_SHARD_STAGE_F, st);  // ... while the own keys are updated in place
+                     return DFH_OK;
+                   });
 }
 
 // G: gradient rows to the owners (into the buffer their rows came from)

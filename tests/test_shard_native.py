@@ -460,8 +460,9 @@ def test_shard_step_hot_keys_split_role(tmp_path, oracle, WORLD, balanced, prefe
 @pytest.mark.parametrize("shape", ["mixed", "hot"])
 def test_shard_step_world1_over_rccl_matches_fused(shape):
     """one rank over the real transport (RCCL loaded at run time): every key is the rank's own, so the step
-    is the fused step (k_lookup -> k_forward<MIXED> on the table -> k_backward_all with the in-place
-    update) and must give what dfh_sgd_step gives.
+    queues what the fused step queues (k_lookup_step -> k_forward on the table -> k_update_fused, the in-place
+    update; both steps are schedules over the stage functions step_lookup and step_math) and must give what
+    dfh_sgd_step gives.
     shape `hot`: minibatches with two keys beyond 4 096 occurrences (u_base = 0, the lookup clamps to *d_U): with one rank
     dfh_shard_step makes the launches of dfh_sgd_step with the same arguments but the key range (all keys either way) — the
     same k_lookup_step with the same count-push mode, the same forward, the same k_update_fused on the same lists, no AUC
