@@ -32,6 +32,7 @@ SYMBOLS = [
     "dfh_comm_allreduce_sum", "dfh_shard_create", "dfh_shard_destroy", "dfh_shard_owned_range", "dfh_shard_step", "dfh_shard_prefetch_counts",
     "dfh_shard_pull_host", "dfh_shard_push_host", "dfh_comm_allgather", "dfh_shard_balanced_splits", "dfh_shard_set_exchange", "dfh_shard_set_timing", "dfh_shard_get_timing",
     "dfh_comm_stats", "dfh_comm_info", "dfh_comm_selfcheck", "dfh_comm_wire_probe", "dfh_table_capacity", "dfh_batch_prepare_rows", "dfh_rowbuf_load_host_slices",
+    "dfh_rowbuf_set_labels", "dfh_batch_prepare_cached", "dfh_batch_get_rows",
     "dfh_batch_create_many", "dfh_shard_multi_words", "dfh_shard_reserve", "dfh_comm_create_loopback", "dfh_comm_loopback_feed", "dfh_comm_loopback_wire", "dfh_comm_loopback_wire_time",
     "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
@@ -156,6 +157,9 @@ def lib():
     L.dfh_rowbuf_load_host.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
+    L.dfh_rowbuf_set_labels.argtypes = [vp, C.c_size_t, vp]
+    L.dfh_batch_get_rows.argtypes = [vp, vp, vp]
+    L.dfh_batch_prepare_cached.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
     L.dfh_batch_set_option.argtypes = [vp, C.c_char_p, i32]
     L.dfh_batch_key_ranges.argtypes = [vp, i32, vp]
     L.dfh_batch_key_ranges_device.argtypes = [vp, i32, vp, vp]
@@ -526,6 +530,11 @@ class RowBuf:
         value = None if value is None else np.ascontiguousarray(value, np.float32)
         _ck(lib().dfh_rowbuf_load_host(self.h, len(offset) - 1, _p(offset), _p(index), _p(value)))
 
+    def set_labels(self, label):
+        """dfh_rowbuf_set_labels: the labels of the loaded rows (a buffer that stays: Batch.prepare_cached)"""
+        label = np.ascontiguousarray(label, np.float32)
+        _ck(lib().dfh_rowbuf_set_labels(self.h, len(label), _p(label)))
+
     def close(self):
         if self.h:
             lib().dfh_rowbuf_destroy(self.h)
@@ -608,6 +617,16 @@ class Batch:
         cnts = (C.c_size_t * n)(*[len(r) for r in rows])
         _ck(lib().dfh_batch_prepare_rows(table.h, self.h, len(label), _p(offset), _p(label), n, bufs, ptrs, cnts, max_index))
 
+    def prepare_cached(self, table, segments, max_index=2 ** 64 - 1):
+        """dfh_batch_prepare_cached: prepare_rows out of row buffers that carry their labels — the row numbers are all the host
+        sends, the minibatch's offsets and labels are derived on the device"""
+        rows = [np.ascontiguousarray(r, np.uint32) for _, r in segments]
+        n = len(segments)
+        bufs = (C.c_void_p * n)(*[rb.h for rb, _ in segments])
+        ptrs = (C.c_void_p * n)(*[r.ctypes.data for r in rows])
+        cnts = (C.c_size_t * n)(*[len(r) for r in rows])
+        _ck(lib().dfh_batch_prepare_cached(table.h, self.h, sum(len(r) for r in rows), n, bufs, ptrs, cnts, max_index))
+
     def load_localized_host(self, offset, index, value, label, feaids, feacnt=None):
         offset = np.ascontiguousarray(offset, np.uint64)
         index = np.ascontiguousarray(index, np.uint32)
@@ -631,6 +650,14 @@ class Batch:
         u = C.c_size_t(0)
         _ck(lib().dfh_batch_get_localized(self.h, C.byref(u), _p(feaids), _p(cnt), _p(index)))
         return dict(U=U, feaids=feaids[:U], feacnt=cnt[:U], index=index[:nnz])
+
+    def get_rows(self):
+        """the loaded minibatch's offsets and labels as the device holds them"""
+        nrows, _, _ = self.shape(want_U=False)
+        off = np.zeros(nrows + 1, np.uint32)
+        lab = np.zeros(nrows, np.float32)
+        _ck(lib().dfh_batch_get_rows(self.h, _p(off), _p(lab)))
+        return off, lab
 
     def sgd_step(self, table, is_train=True, push_cnt=False):
         """the batch executor of SGDLearner::IterateData, on device (async)"""

@@ -2499,7 +2499,8 @@ struct dfh_rowbuf {
   uint32_t* d_off = nullptr;   // [max_rows + 1]
   uint64_t* d_idx = nullptr;   // [max_nnz]
   float* d_val = nullptr;      // [max_nnz]
-  bool has_value = false;
+  float* d_lab = nullptr;      // [max_rows] the rows' labels (dfh_rowbuf_set_labels: allocated by the first call)
+  bool has_value = false, has_labels = false;
   hipStream_t up = nullptr;    // uploads: the feed thread's own stream
   hipEvent_t ev_loaded = nullptr;
   // one "gathered" event per stream that has gathered out of this buffer (the two batch objects of a worker loop gather on
@@ -2576,7 +2577,7 @@ int dfh_rowbuf_destroy(dfh_rowbuf* rb) {
     hipStreamDestroy(rb->up);
   }
   if (rb->ev_loaded) hipEventDestroy(rb->ev_loaded);
-  for (void* p : {(void*)rb->d_off, (void*)rb->d_idx, (void*)rb->d_val})
+  for (void* p : {(void*)rb->d_off, (void*)rb->d_idx, (void*)rb->d_val, (void*)rb->d_lab})
     if (p) hipFree(p);
   delete rb;
   return DFH_OK;
@@ -2617,6 +2618,7 @@ int dfh_rowbuf_load_host(dfh_rowbuf* rb, size_t nrows, const size_t* offset, con
   rb->nrows = nrows;
   rb->nnz = nnz;
   rb->has_value = value != nullptr;
+  rb->has_labels = false;   // (they were the previous contents')
   return DFH_OK;
 }
 
@@ -2685,6 +2687,25 @@ int dfh_rowbuf_load_host_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offs
   rb->nrows = nrows;
   rb->nnz = nnz;
   rb->has_value = any_value;
+  rb->has_labels = false;   // (they were the previous contents')
+  return DFH_OK;
+}
+
+// The labels of the rows a row buffer holds (after dfh_rowbuf_load_host / _slices, same thread): with them — and its own
+// offsets, which the buffer keeps on the device and, 4 B per row, on the host — a minibatch out of this buffer is described by
+// its row numbers alone (dfh_batch_prepare_cached).  A reload drops them.
+int dfh_rowbuf_set_labels(dfh_rowbuf* rb, size_t nrows, const float* label) {
+  DFH_ARG(rb && label && nrows >= 1 && nrows == rb->nrows, "dfh_rowbuf_set_labels: one label per row of the loaded buffer");
+  DFH_HIP(hipSetDevice(rb->ctx->device));
+  if (!rb->d_lab) DFH_HIP(hipMalloc(reinterpret_cast<void**>(&rb->d_lab), rb->max_rows * sizeof(float)));
+  DFH_HIP(hipMemcpyAsync(rb->d_lab, label, nrows * sizeof(float), hipMemcpyHostToDevice, rb->up));
+  DFH_HIP(hipEventRecord(rb->ev_loaded, rb->up));   // whoever waits for the upload waits for the labels too
+  DFH_HIP(hipStreamSynchronize(rb->up));            // the caller's array is free again
+  {
+    std::lock_guard<std::mutex> lk(rb->mu);
+    rb->seen_loaded.clear();
+  }
+  rb->has_labels = true;
   return DFH_OK;
 }
 
@@ -3124,6 +3145,110 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
 }  // namespace
 
 
+namespace {
+// A described minibatch (dfh_batch_prepare_rows, dfh_batch_prepare_cached) whose description lies in the batch's page-locked
+// block: the gather is noted — the rows stay where they are, the Localizer's count pass gathers them as it reads them
+// (k_loc_count_gather), or localize_impl queues k_gather_rows_staged first where that pass cannot (see dfh_batch::gsegs) —
+// then Localizer::Compact + the key-index probe in the same phase, ONE ev_ready at the end.  `h_base` (cached only): the
+// minibatch's offsets and labels are not part of the description; k_loc_describe derives them first, into the minibatch's own
+// arrays, and the gather reads them there (v_off / v_lab are NULL).
+struct DescribedIn {
+  size_t nrows, nnz;
+  int nseg;
+  dfh_rowbuf* const* bufs;
+  const size_t* seg_rows;
+  bool any_value;
+  const uint32_t *v_rows, *v_off;
+  const float* v_lab;
+  const uint32_t* v_tile;
+  bool fusable;
+  const uint32_t* v_base;
+};
+int queue_described(dfh_table* t, dfh_batch* b, const DescribedIn& in, uint64_t max_index, bool prof, double tp) {
+  dfh_ctx* c = b->ctx;
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  auto lap = [&](int k) { if (prof) { const double x = now(); b->t_prof[k] += x - tp; tp = x; } };
+  hipStream_t s = prep_of(b);
+  const size_t nrows = in.nrows;
+  const bool cached = in.v_base != nullptr;
+  b->gsegs.clear();
+  size_t at = 0, blk0 = 0;
+  for (int g = 0; g < in.nseg; ++g) {
+    dfh_rowbuf* rb = in.bufs[g];
+    const size_t n = in.seg_rows[g];
+    if (n == 0) continue;
+    bool waited;
+    {
+      std::lock_guard<std::mutex> lk(rb->mu);
+      waited = std::find(rb->seen_loaded.begin(), rb->seen_loaded.end(), s) != rb->seen_loaded.end();
+      if (!waited) rb->seen_loaded.push_back(s);
+    }
+    if (!waited) DFH_HIP(hipStreamWaitEvent(s, rb->ev_loaded, 0));
+    if (cached) {
+      const unsigned blocks = (unsigned)((n + LOC_DESC_ROWS - 1) / LOC_DESC_ROWS);
+      hipLaunchKernelGGL(k_loc_describe, dim3(blocks), dim3(LOC_DESC_ROWS), 0, s, rb->d_off, rb->d_lab, in.v_rows + at, in.v_base + blk0,
+                         (uint32_t)n, b->d_offset + at, b->d_label + at, at + n == nrows ? 1 : 0);
+      blk0 += blocks;
+    }
+    b->gsegs.push_back({rb, at, n});
+    at += n;
+  }
+  if (cached) DFH_HIP(hipGetLastError());
+  const uint32_t* v_off = cached ? b->d_offset : in.v_off;
+  const float* v_lab = cached ? b->d_label : in.v_lab;
+  b->g_rows = in.v_rows;
+  b->g_off = v_off;
+  b->g_lab = v_lab;
+  b->gather_any_value = in.any_value;
+  b->gather_pending = true;
+  {
+    GatherSrc& gs = b->gsrc;
+    const bool ok = in.fusable;
+    b->gather_fusable = ok;
+    gs.nseg = (int)b->gsegs.size();
+    for (int g = 0; g <= LOC_GATHER_SEGS; ++g) gs.seg_row0[g] = (uint32_t)nrows;
+    for (int g = 0; g < LOC_GATHER_SEGS; ++g) {
+      const bool have = g < gs.nseg && ok;
+      gs.seg_row0[g] = have ? (uint32_t)b->gsegs[g].at : (uint32_t)nrows;
+      gs.src_off[g] = have ? b->gsegs[g].rb->d_off : nullptr;
+      gs.src_idx[g] = have ? b->gsegs[g].rb->d_idx : nullptr;
+      gs.src_val[g] = (have && b->gsegs[g].rb->has_value) ? b->gsegs[g].rb->d_val : nullptr;
+    }
+    gs.h_rows = in.v_rows;
+    gs.h_off = v_off;
+    gs.h_lab = v_lab;
+    gs.h_tile_row = in.v_tile;
+    gs.dst_raw = b->d_raw;
+    gs.dst_val = in.any_value ? b->d_value : nullptr;
+    gs.dst_off = b->d_offset;
+    gs.dst_lab = b->d_label;
+  }
+  b->nrows = nrows;
+  b->nnz = in.nnz;
+  b->has_value = in.any_value;
+  b->has_cnt = false;
+  b->localized = false;
+  b->looked_up = nullptr;
+  lap(3);  // gather queued
+  // Localizer::Compact + the key-index probe, same phase: ONE ev_ready at the end
+  b->defer_ready = true;
+  int rc = localize_impl(b, max_index, nullptr);
+  lap(4);  // Localizer queued
+  if (!rc && in.nnz > kSmallBatchPairs && !c->single_queue) {   // (a small minibatch: the step's own pass probes, see dfh_batch_lookup)
+    hipLaunchKernelGGL(k_lookup, dim3(grid_for_threads(b->nnz, c)), dim3(256), 0, s, t->v, b->d_feaids, b->d_U, 0u, b->d_urow,
+                       (const float*)nullptr, b->d_col_ptr, 0, (uint32_t*)nullptr, 0, (uint2*)nullptr, AucFin{nullptr, 0u, nullptr});
+    if (hipGetLastError() != hipSuccess) rc = DFH_ERR_HIP;
+    b->looked_up = t;
+  }
+  b->defer_ready = false;
+  if (rc) return rc;
+  rc = prep_end(b);
+  lap(5);  // lookup queued, ev_ready recorded
+  if (prof) ++b->n_prof;
+  return rc;
+}
+}  // namespace
+
 int dfh_batch_prepare_rows(dfh_table* t, dfh_batch* b, size_t nrows, const size_t* offset, const float* label, int nseg,
                            dfh_rowbuf* const* bufs, const uint32_t* const* rows, const size_t* seg_rows, uint64_t max_index) {
   DFH_ARG(t && b && t->ctx == b->ctx && offset && label && nseg >= 1 && bufs && rows && seg_rows, "dfh_batch_prepare_rows: NULL argument");
@@ -3152,7 +3277,6 @@ int dfh_batch_prepare_rows(dfh_table* t, dfh_batch* b, size_t nrows, const size_
   phase_begin(b);
   int rc = prep_begin(b);
   if (rc) return rc;
-  hipStream_t s = prep_of(b);
   b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
   // the same page-locked block as dfh_batch_load_host / dfh_batch_gather_rows: offsets | labels | (ids ->) row numbers
   const size_t o_off = 0, o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255),
@@ -3192,89 +3316,125 @@ int dfh_batch_prepare_rows(dfh_table* t, dfh_batch* b, size_t nrows, const size_
   const uint32_t* v_off = reinterpret_cast<const uint32_t*>(b->d_stage_view + o_off);
   const float* v_lab = reinterpret_cast<const float*>(b->d_stage_view + o_lab);
   const uint32_t* v_rows = reinterpret_cast<const uint32_t*>(b->d_stage_view + o_idx);
-  // the rows stay where they are for now: the Localizer's count pass gathers them as it reads them (k_loc_count_gather), or
-  // localize_impl queues k_gather_rows_staged first where that pass cannot (see dfh_batch::gsegs)
-  b->gsegs.clear();
-  at = 0;
-  for (int g = 0; g < nseg; ++g) {
-    dfh_rowbuf* rb = bufs[g];
-    if (seg_rows[g] == 0) continue;
-    bool waited;
-    {
-      std::lock_guard<std::mutex> lk(rb->mu);
-      waited = std::find(rb->seen_loaded.begin(), rb->seen_loaded.end(), s) != rb->seen_loaded.end();
-      if (!waited) rb->seen_loaded.push_back(s);
-    }
-    if (!waited) DFH_HIP(hipStreamWaitEvent(s, rb->ev_loaded, 0));
-    b->gsegs.push_back({rb, at, seg_rows[g]});
-    at += seg_rows[g];
-  }
-  b->g_rows = v_rows;
-  b->g_off = v_off;
-  b->g_lab = v_lab;
-  b->gather_any_value = any_value;
-  b->gather_pending = true;
   // what the count pass needs on top: the first row of every tile of LOC_TILE positions (the last row that starts at or before
   // the tile), behind the row numbers in the same page-locked block; a tile may span LOC_GATHER_ROWS rows, a minibatch
   // LOC_GATHER_SEGS buffers
-  {
-    GatherSrc& gs = b->gsrc;
-    const size_t ntiles = (nnz + LOC_TILE - 1) / LOC_TILE;
-    uint32_t* h_tile = reinterpret_cast<uint32_t*>(b->h_stage + o_tile);
-    bool ok = nnz > 0 && b->gsegs.size() <= (size_t)LOC_GATHER_SEGS;
-    size_t r = 0;
-    for (size_t t = 0; t < ntiles && ok; ++t) {
-      const uint32_t p = (uint32_t)(t * LOC_TILE);
-      while (r + 1 < nrows && h_off[r + 1] <= p) ++r;   // the last row with off[r] <= p
-      h_tile[t] = (uint32_t)r;
-      if (t > 0 && r - h_tile[t - 1] + 1 > (size_t)LOC_GATHER_ROWS) ok = false;
-    }
-    if (ok) {
-      h_tile[ntiles] = (uint32_t)nrows;
-      if (nrows - h_tile[ntiles - 1] > (size_t)LOC_GATHER_ROWS) ok = false;   // (the last tile's rows, trailing empty ones included)
-    }
-    b->gather_fusable = ok;
-    gs.nseg = (int)b->gsegs.size();
-    for (int g = 0; g <= LOC_GATHER_SEGS; ++g) gs.seg_row0[g] = (uint32_t)nrows;
-    for (int g = 0; g < LOC_GATHER_SEGS; ++g) {
-      const bool have = g < gs.nseg && ok;
-      gs.seg_row0[g] = have ? (uint32_t)b->gsegs[g].at : (uint32_t)nrows;
-      gs.src_off[g] = have ? b->gsegs[g].rb->d_off : nullptr;
-      gs.src_idx[g] = have ? b->gsegs[g].rb->d_idx : nullptr;
-      gs.src_val[g] = (have && b->gsegs[g].rb->has_value) ? b->gsegs[g].rb->d_val : nullptr;
-    }
-    gs.h_rows = v_rows;
-    gs.h_off = v_off;
-    gs.h_lab = v_lab;
-    gs.h_tile_row = reinterpret_cast<const uint32_t*>(b->d_stage_view + o_tile);
-    gs.dst_raw = b->d_raw;
-    gs.dst_val = any_value ? b->d_value : nullptr;
-    gs.dst_off = b->d_offset;
-    gs.dst_lab = b->d_label;
+  size_t nsegs_used = 0;
+  for (int g = 0; g < nseg; ++g) nsegs_used += seg_rows[g] != 0;
+  const size_t ntiles = (nnz + LOC_TILE - 1) / LOC_TILE;
+  uint32_t* h_tile = reinterpret_cast<uint32_t*>(b->h_stage + o_tile);
+  bool ok = nnz > 0 && nsegs_used <= (size_t)LOC_GATHER_SEGS;
+  size_t r = 0;
+  for (size_t t = 0; t < ntiles && ok; ++t) {
+    const uint32_t p = (uint32_t)(t * LOC_TILE);
+    while (r + 1 < nrows && h_off[r + 1] <= p) ++r;   // the last row with off[r] <= p
+    h_tile[t] = (uint32_t)r;
+    if (t > 0 && r - h_tile[t - 1] + 1 > (size_t)LOC_GATHER_ROWS) ok = false;
   }
-  b->nrows = nrows;
-  b->nnz = nnz;
-  b->has_value = any_value;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
-  lap(3);  // gather queued
-  // Localizer::Compact + the key-index probe, same phase: ONE ev_ready at the end
-  b->defer_ready = true;
-  rc = localize_impl(b, max_index, nullptr);
-  lap(4);  // Localizer queued
-  if (!rc && nnz > kSmallBatchPairs && !c->single_queue) {   // (a small minibatch: the step's own pass probes, see dfh_batch_lookup)
-    hipLaunchKernelGGL(k_lookup, dim3(grid_for_threads(b->nnz, c)), dim3(256), 0, s, t->v, b->d_feaids, b->d_U, 0u, b->d_urow,
-                       (const float*)nullptr, b->d_col_ptr, 0, (uint32_t*)nullptr, 0, (uint2*)nullptr, AucFin{nullptr, 0u, nullptr});
-    if (hipGetLastError() != hipSuccess) rc = DFH_ERR_HIP;
-    b->looked_up = t;
+  if (ok) {
+    h_tile[ntiles] = (uint32_t)nrows;
+    if (nrows - h_tile[ntiles - 1] > (size_t)LOC_GATHER_ROWS) ok = false;   // (the last tile's rows, trailing empty ones included)
   }
-  b->defer_ready = false;
+  DescribedIn in{nrows, nnz, nseg, bufs, seg_rows, any_value, v_rows, v_off, v_lab,
+                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_tile), ok, nullptr};
+  return queue_described(t, b, in, max_index, prof, tp);
+}
+
+// dfh_batch_prepare_rows for a minibatch out of buffers that carry their own labels (dfh_rowbuf_set_labels): the caller names
+// the rows, nothing else.  The host's share: the row numbers into the page-locked block (4 B per row), and — read off the
+// buffers' host-side offsets while it copies them — the minibatch's nnz (the launches that follow are sized by it), the running
+// total at every 256th row of a segment (k_loc_describe's block bases) and the first row of every tile (the count pass's
+// gather, as in dfh_batch_prepare_rows).  Offsets and labels are derived on the device (k_loc_describe, dfh_localize.hip).
+int dfh_batch_prepare_cached(dfh_table* t, dfh_batch* b, size_t nrows, int nseg, dfh_rowbuf* const* bufs, const uint32_t* const* rows,
+                             const size_t* seg_rows, uint64_t max_index) {
+  DFH_ARG(t && b && t->ctx == b->ctx && nseg >= 1 && bufs && rows && seg_rows, "dfh_batch_prepare_cached: NULL argument");
+  DFH_ARG(nrows >= 1 && nrows <= b->max_rows, "dfh_batch_prepare_cached: nrows out of range");
+  DFH_ARG(max_index != 0, "max_index must be nonzero");
+  size_t total = 0, nblk = 0, nsegs_used = 0;
+  bool any_value = false;
+  for (int g = 0; g < nseg; ++g) {
+    DFH_ARG(bufs[g] && bufs[g]->ctx == b->ctx && (seg_rows[g] == 0 || rows[g]), "dfh_batch_prepare_cached: bad segment");
+    DFH_ARG(bufs[g]->has_labels && bufs[g]->off32.size() == bufs[g]->nrows + 1,
+            "dfh_batch_prepare_cached: a row buffer without labels (dfh_rowbuf_set_labels)");
+    total += seg_rows[g];
+    nblk += (seg_rows[g] + LOC_DESC_ROWS - 1) / LOC_DESC_ROWS;
+    nsegs_used += seg_rows[g] != 0;
+    any_value = any_value || bufs[g]->has_value;
+  }
+  DFH_ARG(total == nrows, "dfh_batch_prepare_cached: the segments must hold nrows rows");
+  dfh_ctx* c = b->ctx;
+  static const bool prof = getenv("DFH_PROFILE_PREP") != nullptr;
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double tp = prof ? now() : 0;
+  auto lap = [&](int k) { if (prof) { const double x = now(); b->t_prof[k] += x - tp; tp = x; } };
+  DFH_HIP(hipSetDevice(c->device));
+  // the page-locked block of dfh_batch_prepare_rows: | (offsets) | (labels) | row numbers | tile rows | block bases
+  const size_t o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255);
+  const size_t o_tile = o_idx + (b->max_rows + 1) * 4, o_base = o_tile + (b->max_tiles + 2) * 4;
+  int rc = ensure_stage(b, o_base + (nblk + 1) * 4);
   if (rc) return rc;
-  rc = prep_end(b);
-  lap(5);  // lookup queued, ev_ready recorded
-  if (prof) ++b->n_prof;
-  return rc;
+  if (!b->d_stage_view) DFH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_stage_view), b->h_stage, 0));
+  if (b->staged_pending) {
+    if (hipEventQuery(b->ev_staged) != hipSuccess) DFH_HIP(hipEventSynchronize(b->ev_staged));
+    b->staged_pending = false;
+  }
+  lap(1);  // the previous description has been read
+  uint32_t* h_rows = reinterpret_cast<uint32_t*>(b->h_stage + o_idx);
+  uint32_t* h_tile = reinterpret_cast<uint32_t*>(b->h_stage + o_tile);
+  uint32_t* h_base = reinterpret_cast<uint32_t*>(b->h_stage + o_base);
+  // h_tile[t] = the last row that starts at or before position t * LOC_TILE: when row q starts beyond it, that row is q - 1
+  size_t at = 0, nnz = 0, nt = 0, nb = 0;
+  const size_t tile_cap = b->max_tiles + 1;   // (a minibatch beyond max_nnz is refused below; its surplus tiles are not written)
+  for (int g = 0; g < nseg; ++g) {
+    const uint32_t lim = (uint32_t)bufs[g]->nrows;
+    const uint32_t* src = rows[g];
+    const uint32_t* off = bufs[g]->off32.data();
+    for (size_t i = 0; i < seg_rows[g]; ++i) {
+      const uint32_t r = src[i];
+      DFH_ARG(r < lim, "dfh_batch_prepare_cached: row number beyond the buffer");
+      h_rows[at + i] = r;
+      if (i % LOC_DESC_ROWS == 0) h_base[nb++] = (uint32_t)nnz;
+      while (nt * (size_t)LOC_TILE < nnz && nt < tile_cap) h_tile[nt++] = (uint32_t)(at + i - 1);
+      nnz += off[r + 1] - off[r];
+    }
+    at += seg_rows[g];
+  }
+  DFH_ARG(nnz <= b->max_nnz && nnz < 0xFFFFFFFFULL, "dfh_batch_prepare_cached: nnz exceeds max_nnz");
+  const size_t ntiles = (nnz + LOC_TILE - 1) / LOC_TILE;
+  while (nt < ntiles) h_tile[nt++] = (uint32_t)(nrows - 1);
+  bool ok = nnz > 0 && nsegs_used <= (size_t)LOC_GATHER_SEGS;
+  for (size_t q = 1; q < ntiles && ok; ++q)
+    if ((size_t)h_tile[q] - h_tile[q - 1] + 1 > (size_t)LOC_GATHER_ROWS) ok = false;
+  if (ok) {
+    h_tile[ntiles] = (uint32_t)nrows;
+    if (nrows - h_tile[ntiles - 1] > (size_t)LOC_GATHER_ROWS) ok = false;   // (the last tile's rows, trailing empty ones included)
+  }
+  lap(2);  // description written
+  if (nnz) {
+    int rcr = table_reserve(t, nnz);  // U <= nnz keys may be new; before anything of this phase is queued
+    if (rcr) return rcr;
+  }
+  phase_begin(b);
+  rc = prep_begin(b);
+  if (rc) return rc;
+  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
+  lap(0);  // prep_begin (wait for the batch object's previous step)
+  DescribedIn in{nrows, nnz, nseg, bufs, seg_rows, any_value, reinterpret_cast<const uint32_t*>(b->d_stage_view + o_idx), nullptr, nullptr,
+                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_tile), ok,
+                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_base)};
+  return queue_described(t, b, in, max_index, prof, tp);
+}
+
+// the loaded minibatch's own offsets [nrows + 1] and labels [nrows] as the device holds them (tests: a described minibatch's
+// are written by the gather, a cached one's derived by k_loc_describe).  Synchronises.
+int dfh_batch_get_rows(dfh_batch* b, uint32_t* offset, float* label) {
+  DFH_ARG(b && b->nrows > 0 && offset && label, "dfh_batch_get_rows: no batch loaded / NULL argument");
+  DFH_HIP(hipSetDevice(b->ctx->device));
+  int rc = sync_all(b->ctx);
+  if (rc) return rc;
+  DFH_HIP(hipMemcpy(offset, b->d_offset, (b->nrows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  DFH_HIP(hipMemcpy(label, b->d_label, b->nrows * sizeof(float), hipMemcpyDeviceToHost));
+  return DFH_OK;
 }
 
 int dfh_localize(dfh_batch* b, uint64_t max_index) {

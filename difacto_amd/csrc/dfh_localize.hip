@@ -432,6 +432,44 @@ __global__ void __launch_bounds__(LOC_TILE_THREADS) k_loc_count_gather(LocView v
   loc_count_block<MAXB, LOC_TILE_THREADS, true>(v, blockIdx.x, gridDim.x, smem, &g);
 }
 
+// ---------------------------------------------------------------------------------------
+// Cached device feed (dfh_batch_prepare_cached): a minibatch out of row buffers that STAY in HBM (data_cache = hbm).  The
+// buffers carry their own offsets and labels (dfh_rowbuf_set_labels), so the host describes the minibatch by its row numbers
+// alone — 4 B per row of page-locked memory instead of 12 — and this kernel derives what dfh_batch_prepare_rows was sent:
+//   offsets  the exclusive scan of the gathered rows' lengths (wave-64 DPP scans, one cross-wave step through LDS)
+//   labels   a gather
+// written into the minibatch's OWN arrays (dfh_batch::d_offset / d_label), the ones k_gather_rows_staged and the count pass
+// fill for a described minibatch: both then read the description from there, and everything downstream is untouched.
+// One launch per segment (the rows of one buffer; a minibatch names one buffer, two at a buffer border), LOC_DESC_ROWS rows
+// per block, one row per thread.  No block waits for another: the host, which needs the minibatch's nnz to size the launches
+// that follow and reads the lengths off the buffer's host-side offsets for it, leaves the running total at every block's first
+// row beside the row numbers (h_base: 4 B per 256 rows).  Loads are unconditional (a thread beyond the segment re-reads its
+// last row), only the stores are guarded.
+// Binary values: whether the minibatch gets a value array is decided as for a described minibatch — it has one iff one of
+// the buffers it names has one (dfh_rowbuf::has_value, fixed when the buffer was uploaded); rows of a buffer without values
+// are gathered as ones.  Nothing of that depends on this kernel.
+// Registers: 13 VGPRs, 26 SGPRs, no scratch, 16 B of LDS (the count pass: 18 VGPRs, 20 when it gathers).
+// ---------------------------------------------------------------------------------------
+constexpr int LOC_DESC_ROWS = 256;
+__global__ void __launch_bounds__(LOC_DESC_ROWS) k_loc_describe(const uint32_t* __restrict__ src_off, const float* __restrict__ src_lab,
+                                                                const uint32_t* __restrict__ h_rows, const uint32_t* __restrict__ h_base,
+                                                                uint32_t n, uint32_t* __restrict__ dst_off, float* __restrict__ dst_lab,
+                                                                int write_end) {
+  __shared__ uint32_t wsum[LOC_DESC_ROWS / 64];
+  const uint32_t q = blockIdx.x * LOC_DESC_ROWS + threadIdx.x;
+  const bool in = q < n;
+  const uint32_t r = h_rows[in ? q : n - 1u];
+  const uint32_t lo = src_off[r], hi = src_off[r + 1u];
+  const float lab = src_lab[r];
+  const uint32_t len = in ? hi - lo : 0u;
+  const uint32_t at = h_base[blockIdx.x] + block_exclusive_scan<LOC_DESC_ROWS / 64>(len, wsum, nullptr);
+  if (in) {
+    dst_off[q] = at;
+    dst_lab[q] = lab;
+    if (write_end && q + 1u == n) dst_off[n] = at + len;
+  }
+}
+
 
 // ---- scatter into bucket-major order; every block derives the bucket starts from the totals
 // (block 0 publishes them)

@@ -1027,8 +1027,9 @@ class BatchReader : public BatchSource {
    *  buffer AHEAD of the one being cut into minibatches: where the device feed starts its upload, so that the copy
    *  is over when the first minibatch of the buffer wants its rows */
   BatchReader(const std::string& uri, const std::string& format, unsigned part_index, unsigned num_parts, unsigned batch_size,
-              unsigned shuffle_buf_size = 0, float neg_sampling = 1.0f, bool slice_buffers = false, SliceFn on_built = nullptr)
-      : batch_size_(batch_size), shuf_buf_(shuffle_buf_size), neg_sampling_(neg_sampling) {
+              unsigned shuffle_buf_size = 0, float neg_sampling = 1.0f, bool slice_buffers = false, SliceFn on_built = nullptr,
+              bool permute = true)
+      : batch_size_(batch_size), shuf_buf_(shuffle_buf_size), neg_sampling_(neg_sampling), permute_(permute) {
     CHECK_GT(batch_size, 0u);
     if (shuf_buf_) {
       CHECK_GE(shuf_buf_, batch_size_);
@@ -1044,6 +1045,21 @@ class BatchReader : public BatchSource {
       CHECK(!slice_buffers) << "slice_buffers needs a shuffle buffer";
       reader_.reset(new Reader(uri, format, part_index, num_parts, 1 << 24));
     }
+  }
+
+  /*! \brief a reader whose shuffle buffers come from `buffers` (owned) instead of from a file: blocks of offsets and labels,
+   *  their rows wherever the source's owner keeps them under the serial 1, 2, .. (the SGD learner's data_cache = hbm,
+   *  sgd_data_cache.h).  Its minibatches are DESCRIBED (Aux()); from "the next buffer has arrived" on Next() is the one
+   *  code path.  permute = false (both constructors): the buffers are read through in order — a shuffle buffer used as a
+   *  plain read-ahead buffer, nothing drawn from the permutation's stream */
+  BatchReader(BatchSource* buffers, unsigned batch_size, unsigned shuffle_buf_size, float neg_sampling, bool permute)
+      : batch_size_(batch_size), shuf_buf_(shuffle_buf_size), neg_sampling_(neg_sampling), permute_(permute) {
+    CHECK_GT(batch_size, 0u);
+    CHECK_GE(shuf_buf_, batch_size_);
+    buf_reader_.reset(buffers);
+    sliced_ = true;
+    uploaded_early_ = true;   // nobody takes the buffers: they are where they belong already
+    describe_ = true;
   }
 
   /**
@@ -1143,7 +1159,7 @@ class BatchReader : public BatchSource {
             rdp_.resize(in_blk_.size);
             for (size_t i = 0; i < in_blk_.size; ++i) rdp_[i] = static_cast<unsigned>(i);
           }
-          {  // the reference's std::random_shuffle on its own rand() stream (RefRand above)
+          if (permute_) {  // the reference's std::random_shuffle on its own rand() stream (RefRand above)
             std::lock_guard<std::mutex> lk(*RefRand::GlobalLock());
             RefRand::Global()->Shuffle(&rdp_);
           }
@@ -1299,6 +1315,7 @@ class BatchReader : public BatchSource {
   }
   unsigned batch_size_, shuf_buf_;
   float neg_sampling_;
+  bool permute_ = true;        // false: the shuffle buffer's rows are taken in order
   std::unique_ptr<Reader> reader_;
   std::unique_ptr<BatchSource> buf_reader_;
   bool view_ = false;  // Value() points into the current chunk, not into batch_

@@ -41,6 +41,20 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
   CHECK(param_.data_format == "libsvm" || param_.data_format == "criteo" || param_.data_format == "criteo_test" ||
         param_.data_format == "adfea" || param_.data_format == "rec")
       << "data_format " << param_.data_format << " is not one of the reference's (libsvm, criteo, criteo_test, adfea, rec)";
+  // data_cache: checked before anything touches the device
+  CHECK(param_.data_cache.empty() || param_.data_cache == "hbm")
+      << "data_cache=" << param_.data_cache << " is not one of \"\" (off, the default) and hbm";
+  CHECK_GE(param_.data_cache_max_gb, 0) << "data_cache_max_gb is a size in GB (0: no budget)";
+  if (param_.data_cache == "hbm") {
+    CHECK(param_.task != "predict") << "data_cache=hbm with task=predict: a prediction is one pass over the data, no later epoch "
+                                       "would read the cache (caching is for task=train)";
+    CHECK(!IsDistributed()) << "data_cache=hbm with a sharded store (DMLC_ROLE is set): the sharded worker loop does not read "
+                               "through the device feed yet; run one process, or leave data_cache out";
+    for (const auto& kv : remain)
+      CHECK(!(kv.first == "device_path" && kv.second == "literal"))
+          << "data_cache=hbm with device_path=literal: the literal loop hands host arrays to Store and Loss, only "
+             "device_path=fused gathers its minibatches out of device row buffers";
+  }
   auto updater = new DeviceSGDUpdater();
   remain = updater->Init(remain);
   remain.push_back(std::make_pair("V_dim", std::to_string(updater->param().V_dim)));
@@ -232,9 +246,60 @@ struct DeviceFeed {
   // the buffer's ten minibatches)
   struct Job {
     std::vector<size_t> offset;     // the buffer's own offsets (copied: the builder's container moves on)
+    std::vector<real_t> label;      // (retain) the buffer's labels
     std::vector<BufSlice> slices;   // shared ownership of the parsed chunks
     uint64_t serial;
   };
+  // data_cache = hbm (sgd_data_cache.h).  `cached`: the job reads a part that is in the cache — Of() names its buffers, nothing
+  // is uploaded or handed back.  `retain`: the job fills the cache — every buffer gets an allocation of its own size and its
+  // labels, and Release() moves it to `kept` instead of `spare`.  Before a buffer is retained its bytes are added to the part's;
+  // when they exceed `budget` (or the allocation fails) the part is given up: what was kept goes to `spare` and the job goes on
+  // as an uncached one does.
+  const CachedPart* cached = nullptr;
+  bool retain = false, overflow = false;
+  size_t budget = ~static_cast<size_t>(0), kept_bytes = 0, need_bytes = 0, rows_seen = 0;
+  std::map<uint64_t, CachedBuffer> desc, kept;   // serial -> retained buffer: still live / handed back
+  static size_t BytesOf(size_t rows, size_t nnz) { return nnz * 12 + (rows + 1) * 4 + rows * 4; }   // dfh_rowbuf's arrays + labels
+  void GiveUp() {   // under mu
+    overflow = true;
+    for (auto& k : kept) spare.push_back(k.second.rb);
+    kept.clear();
+    desc.clear();   // (their buffers are live: Release recycles them)
+    kept_bytes = 0;
+  }
+  /*! \brief after the job's last minibatch: the part's buffers in order, or NULL (it did not fit) */
+  std::unique_ptr<CachedPart> TakeCache() {
+    StopWorkers();   // an upload nobody waited for (a buffer none of whose rows was drawn) ends here
+    std::lock_guard<std::mutex> lk(mu);
+    if (!retain || overflow) return nullptr;
+    for (auto& l : live) {
+      auto it = desc.find(l.first);
+      CHECK(it != desc.end());
+      kept.emplace(l.first, std::move(it->second));
+    }
+    live.clear();
+    desc.clear();
+    std::unique_ptr<CachedPart> part(new CachedPart());
+    for (auto& k : kept) {
+      CHECK_EQ(k.first, part->bufs.size() + 1) << "a shuffle buffer is missing from the cache";
+      all.erase(std::remove(all.begin(), all.end(), k.second.rb), all.end());
+      cap.erase(k.second.rb);
+      part->rows += k.second.label.size();
+      part->bytes += k.second.bytes;
+      part->bufs.push_back(std::move(k.second));
+    }
+    kept.clear();
+    return part;
+  }
+  void StopWorkers() {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      stop = true;
+    }
+    cv.notify_all();
+    for (auto& w : workers)
+      if (w.joinable()) w.join();
+  }
   std::deque<Job> jobs;
   std::vector<std::thread> workers;
   bool stop = false;
@@ -268,6 +333,8 @@ struct DeviceFeed {
     j.serial = serial;
     {
       std::lock_guard<std::mutex> lk(mu);
+      rows_seen += blk.size;
+      if (retain && !overflow) j.label.assign(blk.label, blk.label + blk.size);
       jobs.push_back(std::move(j));
     }
     cv.notify_all();
@@ -291,7 +358,29 @@ struct DeviceFeed {
     const size_t nrows = j.offset.size() - 1;
     const size_t nnz = j.offset[nrows] - j.offset[0];
     dfh_rowbuf* rb = nullptr;
-    {
+    bool keep = false;
+    const size_t bytes = BytesOf(std::max<size_t>(nrows, 1), std::max<size_t>(nnz, 1));
+    if (retain) {   // a buffer that stays: an allocation of exactly its size, if the part still fits
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        need_bytes += bytes;
+        if (!overflow && j.label.size() == nrows) {
+          if (kept_bytes + bytes > budget) GiveUp(); else { keep = true; kept_bytes += bytes; }
+        }
+      }
+      if (keep && dfh_rowbuf_create(ctx, std::max<size_t>(nrows, 1), std::max<size_t>(nnz, 1), &rb) != DFH_OK) {
+        rb = nullptr;   // no room on the device: the part streams
+        keep = false;
+        std::lock_guard<std::mutex> lk(mu);
+        GiveUp();
+      }
+      if (rb) {
+        std::lock_guard<std::mutex> lk(mu);
+        all.push_back(rb);
+        cap[rb] = {std::max<size_t>(nrows, 1), std::max<size_t>(nnz, 1)};
+      }
+    }
+    if (!rb) {
       std::lock_guard<std::mutex> lk(mu);
       for (size_t i = 0; i < spare.size() && !rb; ++i) {
         const auto& c = cap[spare[i]];
@@ -329,13 +418,26 @@ struct DeviceFeed {
       cnt[g] = slices[g].nnz();
     }
     DFH_CALL(dfh_rowbuf_load_host_slices(rb, nrows, j.offset.data(), static_cast<int>(slices.size()), idx.data(), val.data(), cnt.data()));
+    if (keep) DFH_CALL(dfh_rowbuf_set_labels(rb, nrows, j.label.data()));
     {
       std::lock_guard<std::mutex> lk(mu);
       CHECK(live.emplace(serial, rb).second) << "shuffle buffer " << serial << " uploaded twice";
+      if (keep && !overflow) {
+        CachedBuffer& d = desc[serial];
+        d.rb = rb;
+        d.offset.resize(nrows + 1);
+        for (size_t i = 0; i <= nrows; ++i) d.offset[i] = j.offset[i] - j.offset[0];
+        d.label = j.label;
+        d.bytes = bytes;
+      }
     }
     cv.notify_all();
   }
   dfh_rowbuf* Of(uint64_t serial) {   // on the worker loop's thread: waits for an upload still under way
+    if (cached) {
+      CHECK(serial >= 1 && serial <= cached->bufs.size()) << "minibatch names buffer " << serial << ", which the cache does not hold";
+      return cached->bufs[serial - 1].rb;
+    }
     std::unique_lock<std::mutex> lk(mu);
     cv.wait(lk, [&] { return live.count(serial) != 0; });
     auto it = live.find(serial);
@@ -344,20 +446,21 @@ struct DeviceFeed {
   }
   // the gathers of every minibatch that names a buffer below `serial` have been queued
   void Release(uint64_t serial) {
+    if (cached) return;
     std::lock_guard<std::mutex> lk(mu);
     while (!live.empty() && live.begin()->first < serial) {
-      spare.push_back(live.begin()->second);
+      auto d = desc.find(live.begin()->first);
+      if (d != desc.end()) {   // (retain, and the part still fits)
+        kept.emplace(d->first, std::move(d->second));
+        desc.erase(d);
+      } else {
+        spare.push_back(live.begin()->second);
+      }
       live.erase(live.begin());
     }
   }
   ~DeviceFeed() {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      stop = true;
-    }
-    cv.notify_all();
-    for (auto& w : workers)
-      if (w.joinable()) w.join();
+    StopWorkers();
     for (auto* rb : all) dfh_rowbuf_destroy(rb);
   }
 };
@@ -375,7 +478,17 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   // same box, by this loop's clock, .rec 53.6 -> 59.4 and criteo text 48.0 -> 50.6 M rows/s (tools/gpu_r04x.sh).  bench.py,
   // whose inputs are already in HBM (no gather), loses 5 % with two: it keeps one
   const char* ps = getenv("DIFACTO_PREP_STREAMS");
-  const bool feed_wanted = job.type == sgd::Job::kTraining && param_.shuffle > 0 && getenv("DIFACTO_HOST_FEED") == nullptr;
+  // data_cache = hbm: a part that is in the cache is read from there (cpart); one that is not yet is read through the device
+  // feed whatever the job — training without a shuffle buffer and validation too, in buffers of batch_size x max(shuffle, 1)
+  // rows that are read through in order — and its buffers are kept (cache_fill)
+  const bool cache_on = param_.data_cache == "hbm" && !predict;
+  const std::pair<int, int> ckey(job.type, job.part_idx);
+  const CachedPart* cpart = cache_on ? cache_.Find(job.type, job.part_idx) : nullptr;
+  const bool cache_fill = cache_on && !cpart && !cache_.refused.count(ckey);
+  const unsigned cache_buf_rows = static_cast<unsigned>(param_.batch_size) * static_cast<unsigned>(std::max(param_.shuffle, 1));
+  const bool permute = train && param_.shuffle > 0;
+  const bool feed_wanted = cpart || cache_fill ||
+                           (job.type == sgd::Job::kTraining && param_.shuffle > 0 && getenv("DIFACTO_HOST_FEED") == nullptr);
   // DIFACTO_SINGLE_QUEUE=1: the single-queue step (csrc/dfh_riders.hip: the Localizer's stages riding in the step's own three
   // launches, no preparation stream, no events; minibatches then prepared TWO ahead so that every stage finds a launch to ride
   // in).  Off by default: measured through this loop it loses at every size (profiles/r06m_*: batch 100, V_dim 8 from libsvm 2.22
@@ -403,20 +516,31 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   // gathered there (device feed; DIFACTO_HOST_FEED=1 keeps the host-side gather)
   DeviceFeed feed;   // outlives the reader, whose thread uploads into it
   feed.ctx = ctx;
-  const bool device_feed = train && param_.shuffle > 0 && getenv("DIFACTO_HOST_FEED") == nullptr;
+  const bool device_feed = feed_wanted;
+  feed.cached = cpart;
+  feed.retain = cache_fill;
+  if (cache_fill && param_.data_cache_max_gb > 0) {
+    const double cap = static_cast<double>(param_.data_cache_max_gb) * (1ULL << 30);
+    feed.budget = cap > static_cast<double>(cache_.bytes) ? static_cast<size_t>(cap - static_cast<double>(cache_.bytes)) : 0;
+  }
   BatchReader::SliceFn upload;
   // (feed_ids_per_row, default 48: the criteo rows of the reference's example have 39)
   const size_t ids_per_row = static_cast<size_t>(GetUpdater()->device_param().feed_ids_per_row);
-  if (device_feed) feed.Start(static_cast<size_t>(param_.batch_size) * param_.shuffle, static_cast<size_t>(param_.batch_size) * param_.shuffle * ids_per_row);
-  if (device_feed)
+  // (a buffer that is kept gets an allocation of its own size: nothing is created ahead)
+  if (device_feed && !cpart)
+    feed.Start(cache_fill ? 0 : static_cast<size_t>(param_.batch_size) * param_.shuffle,
+               static_cast<size_t>(param_.batch_size) * param_.shuffle * ids_per_row);
+  if (device_feed && !cpart)
     upload = [&feed](const dmlc::RowBlock<feaid_t>& blk, const std::vector<BufSlice>& slices, uint64_t serial) {
       feed.Upload(blk, slices, serial);
     };
   // device feed: buffers as slices of the parsed chunks (no host assembly), uploaded by the thread that builds them
-  BatchReader* batch_reader = new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
-                                              train ? param_.batch_size * param_.shuffle : 0, train ? param_.neg_sampling : 1.0f,
-                                              device_feed, upload);
-  if (device_feed) batch_reader->DescribeSlices(nullptr);
+  BatchReader* batch_reader =
+      cpart ? new BatchReader(new CachedBuffers(cpart), param_.batch_size, cache_buf_rows, train ? param_.neg_sampling : 1.0f, permute)
+            : new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
+                              cache_fill ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0),
+                              train ? param_.neg_sampling : 1.0f, device_feed, upload, cache_fill ? permute : true);
+  if (device_feed && !cpart) batch_reader->DescribeSlices(nullptr);
   // described minibatches are ~120 KB each: a deeper queue lets the loop ride out the reader's pause at a buffer boundary
   PrefetchSource reader(batch_reader, device_feed ? kFusedBatches : 2);
   // objects in rotation: a dozen only where a dozen steps can be queued (the device feed's bursts); validation, prediction
@@ -492,7 +616,9 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
       if (prof) t_feed += now() - tf;
       // gather + Localizer (Localizer lc(-1, ...), sgd_learner.cc:203) + key lookup as one preparation phase
       // (DIFACTO_SPLIT_PREP=1: the three calls of round 3, for A/B)
-      if (split_prep) {
+      if (cpart) {   // the buffers carry their offsets and labels: the row numbers are all that is sent
+        DFH_CALL(dfh_batch_prepare_cached(table, b, blk.size, static_cast<int>(segs.size()), bufs.data(), rows.data(), cnts.data(), ~0ULL));
+      } else if (split_prep) {
         DFH_CALL(dfh_batch_gather_rows(b, blk.size, blk.offset, blk.label, static_cast<int>(segs.size()), bufs.data(), rows.data(),
                                        cnts.data()));
       } else {
@@ -503,7 +629,7 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
       uint64_t last = 0;
       for (const auto& g : segs) last = std::max<uint64_t>(last, g.buf);
       feed.Release(last);
-      if (!split_prep) return;
+      if (!split_prep || cpart) return;
     } else {
       DFH_CALL(dfh_batch_load_host(b, blk.size, blk.offset, blk.index, blk.value, blk.label));
     }
@@ -572,6 +698,28 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   }
   uint64_t nkeys;
   DFH_CALL(dfh_table_size(table, &nkeys));  // surfaces a full table as an error
+  if (cache_on) {   // one line per job: where its rows came from
+    const std::string what = "part " + std::to_string(job.part_idx) + " of " + std::to_string(job.num_parts) +
+                             (train ? " (training): " : " (validation): ");
+    if (cpart) {
+      LOG(INFO) << what << cpart->rows << " rows from the HBM cache";
+    } else if (cache_fill) {
+      std::unique_ptr<CachedPart> part = feed.TakeCache();
+      if (part) {
+        LOG(INFO) << what << part->rows << " rows parsed from " << JobData(job) << ", cached " << (part->bytes + (1 << 19)) / (1 << 20) << " MB";
+        cache_.bytes += part->bytes;
+        cache_.parts[ckey] = std::move(part);
+      } else {
+        LOG(WARNING) << what << "does not fit the HBM cache: its " << feed.rows_seen << " rows need " << feed.need_bytes << " bytes, "
+                     << feed.budget << " are left of data_cache_max_gb=" << param_.data_cache_max_gb << "; it is read from "
+                     << JobData(job) << " in every epoch";
+        LOG(INFO) << what << feed.rows_seen << " rows parsed from " << JobData(job) << ", not cached";
+        cache_.refused[ckey] = true;
+      }
+    } else {
+      LOG(INFO) << what << "parsed from " << JobData(job) << ", not cached";
+    }
+  }
 }
 
 // ---- the sharded worker loop: sgd_learner.cc:129-227 with Store::Pull / Push turned into the exchange of

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "./device_store.h"
+#include "./sgd_data_cache.h"
 #include "./sgd_param.h"
 #include "./sgd_utils.h"
 #include "difacto/learner.h"
@@ -83,6 +84,7 @@ class SGDLearner : public Learner {
   dfh_batch* batch_[kFusedBatches] = {};
   size_t batch_rows_ = 0, batch_nnz_ = 0;
   bool batch_arena_ = false;   // batch_[] were carved from ONE device allocation (dfh_batch_create_many): freed when the last one goes
+  SGDDataCache cache_;              // data_cache = hbm: the row buffers of the parts read so far; destroyed with the learner
   FILE* pred_file_ = nullptr;       // open while a prediction job runs
   std::vector<float> pred_buf_;
 };

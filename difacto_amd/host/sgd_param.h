@@ -31,10 +31,16 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   std::string task;          // "train" (default) | "predict": forward pass of model_in over data_val (else data_in)
   std::string pred_out;      // predict: one line per example, in file order (<pred_out>.part-<i> per data part of a sharded run)
   int pred_prob;             // predict: 0 writes the logit FMLoss::Predict returns (default), 1 writes 1 / (1 + exp(-logit))
+  // data_cache = hbm (a key of this build; the reference's lbfgs and bcd params have one of that name): the parsed rows of
+  // every data part stay in device memory after the epoch that read them, later epochs open no file (sgd_data_cache.h)
+  std::string data_cache;    // "" (default: every epoch reads its files) | "hbm"
+  float data_cache_max_gb;   // > 0: device bytes the cache may hold, in GB (2^30); a part that does not fit is read every epoch
   DMLC_DECLARE_PARAMETER(SGDLearnerParam) {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
     DMLC_DECLARE_FIELD(pred_prob).set_default(0);
+    DMLC_DECLARE_FIELD(data_cache).set_default("");
+    DMLC_DECLARE_FIELD(data_cache_max_gb).set_default(0);
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_in);
     DMLC_DECLARE_FIELD(data_val).set_default("");

@@ -273,6 +273,15 @@ int dfh_batch_gather_rows(dfh_batch* b, size_t nrows, const size_t* offset, cons
  * Same results as the three calls; about half their host time per minibatch. */
 int dfh_batch_prepare_rows(dfh_table* t, dfh_batch* b, size_t nrows, const size_t* offset, const float* label, int nseg,
                            dfh_rowbuf* const* bufs, const uint32_t* const* rows, const size_t* seg_rows, uint64_t max_index);
+/* Row buffers that stay (the SGD learner's data_cache = hbm): dfh_rowbuf_set_labels gives a loaded buffer the labels of its
+ * rows [nrows = the rows it holds]; the buffer keeps its own offsets already.  A minibatch out of such buffers is then
+ * described by its row numbers alone: dfh_batch_prepare_cached is dfh_batch_prepare_rows without `offset` and `label` — the
+ * same phase (row gather + Localizer + lookup, one cross-stream event), the minibatch's offsets (an exclusive scan of the
+ * gathered rows' lengths) and labels (a gather) derived on the device (k_loc_describe) into the arrays
+ * dfh_batch_gather_rows fills.  The same batch, bit for bit.  A reload of the buffer drops its labels. */
+int dfh_rowbuf_set_labels(dfh_rowbuf* rb, size_t nrows, const float* label);
+int dfh_batch_prepare_cached(dfh_table* t, dfh_batch* b, size_t nrows, int nseg, dfh_rowbuf* const* bufs, const uint32_t* const* rows,
+                             const size_t* seg_rows, uint64_t max_index);
 
 /* already-localized batch from the host (what SGDLearner hands its batch thread,
  * src/sgd/sgd_learner.cc:203-212): feaids sorted unique, compact u32 index */
@@ -282,6 +291,8 @@ int dfh_batch_load_localized_host(dfh_batch* b, size_t nrows, const size_t* offs
 /* read back the localizer's outputs (any may be NULL); synchronises */
 int dfh_batch_get_localized(dfh_batch* b, size_t* U, uint64_t* feaids, float* feacnt, uint32_t* index);
 int dfh_batch_shape(dfh_batch* b, size_t* nrows, size_t* nnz, size_t* U); /* synchronises for U */
+/* the loaded minibatch's CSR offsets [nrows + 1] and labels [nrows] as the device holds them; synchronises */
+int dfh_batch_get_rows(dfh_batch* b, uint32_t* offset, float* label);
 
 /* ---------------------------------------------------------- the fused step */
 /* The batch executor of SGDLearner::IterateData (src/sgd/sgd_learner.cc:131-178)
