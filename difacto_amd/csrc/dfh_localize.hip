@@ -18,8 +18,9 @@
 //                  pair back from the tag and the CSR offsets instead of gathering it from a 1.5 MB array (LocView::tb).
 //                  A bucket's area is filled XCD group by XCD group (LocView::btotal), so that the short runs of the
 //                  tiles running on one XCD merge into whole lines in that XCD's L2.
-//   k_loc_sort     one block per bucket: merge sort by (key, pos) (64-wide runs ranked in registers with v_readlane
-//                  broadcasts, then log2(n/64) rounds of merge-by-binary-search in LDS); bucket summary
+//   k_loc_sort     one block per bucket: merge sort by (key, pos) (64-wide runs sorted in registers by a bitonic network over
+//                  the lanes of a wave — DPP and v_permlane swaps, no LDS — then log2(n/64) rounds of merge-by-binary-search
+//                  in LDS); bucket summary, counted in the pass that writes the bucket out
 //   k_loc_emit     one block per bucket: unique ids before the bucket from the summaries, then the
 //                  Localizer's outputs (dictionary, segment starts, compact index per nnz), the
 //                  key-ordered (row, value) view for the backward pass, the long-segment lists of
@@ -46,9 +47,10 @@
 // between blocks) — bit-exact, but every hand-off between blocks inside a launch is a device-scope
 // round trip across the 8 XCDs and costs more than the launch boundary it replaces (21 + 51 us against
 // 19 + 34 us; 66 + 233 us with release / acquire fences, which write back and invalidate the L2);
-// a bitonic network (60+ barrier-separated stages at one or two
-// waves per SIMD: ~1 us of dependent issue latency each), full O(n^2) ranking of a bucket
-// (VALU-bound: 7+ us even when perfectly balanced), an 8-pass LSD radix sort (18 launches).
+// a BLOCK-wide bitonic network (60+ barrier-separated stages at one or two
+// waves per SIMD: ~1 us of dependent issue latency each; the in-wave network of loc_net_sort64 has no barrier), full O(n^2)
+// ranking of a bucket (VALU-bound: 7+ us even when perfectly balanced), all-pairs ranking of the 64-runs with v_readlane
+// broadcasts (448 VALU instructions per run against the network's 204), an 8-pass LSD radix sort (18 launches).
 // The result is the fully sorted pair list (ties by position), i.e. bit-identical to the
 // reference's outputs.  Everything is deterministic.
 #ifndef DFH_LOCALIZE_HIP_
@@ -64,6 +66,8 @@ constexpr int LOC_BIG_BUCKETS = 4096;   // round 4: the large size class (miniba
 constexpr int LOC_AVG_BUCKET = 384;    // target pairs per bucket
 constexpr int LOC_MIN_AVG = 48;        // stored splitters are reused while N / P stays in [MIN, MAX]
 constexpr int LOC_MAX_AVG = 700;
+// (tests/test_loc_sort_runs.py shapes its minibatches by these two, by DFH_LOC_SMALL_AVG of dfh_api.hip and by emit's splitters so
+// that n = 1 .. 1 024 pairs land in ONE bucket; no getter shows the bucket count, so a change here must revisit its primers)
 constexpr int LOC_LDS_CAP = 1024;      // pairs a bucket may hold to be sorted in LDS
 #ifndef DFH_LOC_TILE
 #define DFH_LOC_TILE 2048
@@ -543,176 +547,251 @@ __global__ void __launch_bounds__(LOC_TILE_THREADS) k_loc_scatter(LocView v) {
   loc_scatter_block<MAXB, LOC_TILE_THREADS>(v, blockIdx.x, smem);
 }
 
+// ---- in-wave bitonic network: the 64 lanes of a wave sort their (key, tag) pairs, ascending by lane, in 21 compare-exchange
+// stages without LDS or barriers.  A stage pairs lane i with lane i ^ J inside blocks of K lanes that alternate between
+// ascending and descending.  J <= 8: the partner's pair arrives by DPP (quad_perm for 1 and 2, row_half_mirror followed by the
+// reversal of every quad for 4, row_ror:8 for 8).  J = 16 / 32: v_permlane16_swap / v_permlane32_swap of a register with
+// itself leave the pair's lower lane's word in one result and the upper lane's in the other, in both lanes.  Which lanes keep
+// the larger pair is a constant of the stage: it reaches the select as a 64-bit scalar mask (inverse ballot), so a stage is
+// three moves, three compares and three selects.  The composite (key, tag) is unique, equal padding pairs are interchangeable.
+template <int J>
+__device__ __forceinline__ uint32_t loc_net_partner(uint32_t x) {
+  static_assert(J == 1 || J == 2 || J == 4 || J == 8, "DPP reaches the partners inside a row of 16 lanes");
+  // (mov_dpp: every lane has a source lane under these controls, so no previous value of the destination has to be set up)
+  if constexpr (J == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
+  if constexpr (J == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xf, 0xf, false);  // quad_perm:[2,3,0,1]
+  if constexpr (J == 4) {  // i ^ 7, then i ^ 3
+    const int y = __builtin_amdgcn_mov_dpp((int)x, 0x141, 0xf, 0xf, false);   // row_half_mirror
+    return (uint32_t)__builtin_amdgcn_mov_dpp(y, 0x1B, 0xf, 0xf, false);     // quad_perm:[3,2,1,0]
+  }
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xf, 0xf, false);  // row_ror:8
+}
+// lanes that keep the LARGER pair of their couple in stage (K, J): the upper lane of an ascending block, the lower lane of a
+// descending one
+constexpr uint64_t loc_net_keeps_max(int K, int J) {
+  uint64_t m = 0;
+  for (int i = 0; i < 64; ++i) m |= (uint64_t)(((i & J) != 0) != ((i & K) != 0)) << i;
+  return m;
+}
+template <int K, int J>
+__device__ __forceinline__ void loc_net_stage(uint32_t& klo, uint32_t& khi, uint32_t& tag) {
+  // the mask is set up where it is used, by two scalar moves the compiler cannot move: left to it, the 21 constants are hoisted
+  // out of every loop of the kernel, where they take the scalar registers the kernel's pointers live in and push those out into
+  // lanes of a spill register (81 -> 100 SGPRs, 4 -> 20 v_readlane / v_writelane moves: profiles/r10_prep_registers.txt)
+  uint32_t mlo, mhi;
+  asm volatile("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3"
+               : "=s"(mlo), "=s"(mhi)
+               : "i"((int32_t)(uint32_t)loc_net_keeps_max(K, J)), "i"((int32_t)(uint32_t)(loc_net_keeps_max(K, J) >> 32)));
+  const uint64_t mask = ((uint64_t)mhi << 32) | mlo;
+  const bool keeps_max = __builtin_amdgcn_inverse_ballot_w64(mask);
+  if constexpr (J >= 16) {
+    uint32_t alo, ahi, at, blo, bhi, bt;  // a: the pair of the couple's lower lane, b: of its upper lane
+#define DFH_NET_SWAP(a, b, x)                                                                                       \
+    {                                                                                                                 \
+      const auto r = J == 16 ? __builtin_amdgcn_permlane16_swap(x, x, false, false) : __builtin_amdgcn_permlane32_swap(x, x, false, false); \
+      a = r[0];                                                                                                       \
+      b = r[1];                                                                                                       \
+    }
+    DFH_NET_SWAP(alo, blo, klo)
+    DFH_NET_SWAP(ahi, bhi, khi)
+    DFH_NET_SWAP(at, bt, tag)
+#undef DFH_NET_SWAP
+    // b < a: the couple is out of order for an ascending block.  A lane that keeps the smaller pair then takes b; a lane that
+    // keeps the larger pair takes b when the couple is in order.
+    const bool out_of_order = comp_less(((uint64_t)bhi << 32) | blo, bt, ((uint64_t)ahi << 32) | alo, at);
+    const bool take_b = out_of_order != keeps_max;
+    klo = take_b ? blo : alo;
+    khi = take_b ? bhi : ahi;
+    tag = take_b ? bt : at;
+  } else {
+    const uint32_t olo = loc_net_partner<J>(klo), ohi = loc_net_partner<J>(khi), ot = loc_net_partner<J>(tag);
+    const bool partner_less = comp_less(((uint64_t)ohi << 32) | olo, ot, ((uint64_t)khi << 32) | klo, tag);
+    const bool take = partner_less != keeps_max;
+    klo = take ? olo : klo;
+    khi = take ? ohi : khi;
+    tag = take ? ot : tag;
+  }
+}
+template <int K, int J>
+__device__ __forceinline__ void loc_net_merge(uint32_t& klo, uint32_t& khi, uint32_t& tag) {
+  loc_net_stage<K, J>(klo, khi, tag);
+  if constexpr (J > 1) loc_net_merge<K, J / 2>(klo, khi, tag);
+}
+template <int K = 2>
+__device__ __forceinline__ void loc_net_sort64(uint32_t& klo, uint32_t& khi, uint32_t& tag) {
+  loc_net_merge<K, K / 2>(klo, khi, tag);
+  if constexpr (K < 64) loc_net_sort64<K * 2>(klo, khi, tag);
+}
+
 // ---- sort of one bucket [beg, beg + n) of the bucket-major arrays by (key, pos).  Buckets of up to
-// LOC_LDS_CAP pairs are sorted in LDS and STAY there (*sk / *sp point into ak/ap or bk/bp); larger
-// ones (stale or unlucky splitters; kept for correctness and bounded at n log n) go through the same
-// rounds on the global arrays and end up in v.skeys / v.spos.  All threads of the block call it.
-__device__ __forceinline__ bool loc_sort_bucket(const LocView& v, uint32_t beg, uint32_t n, uint64_t* ak, uint32_t* ap,
-                                                uint64_t* bk, uint32_t* bp, const uint64_t** sk_out, const uint32_t** sp_out) {
+// LOC_LDS_CAP pairs are sorted in LDS and STAY there (loc_sort_bucket_lds: the result is in ak / ap when it returns true, in
+// bk / bp otherwise — a flag, not a pointer: the caller's reads stay LDS reads, through a pointer that may also be a global
+// one they are flat loads); larger ones (stale or unlucky splitters; kept for correctness and bounded at n log n) go through
+// the same rounds on the global arrays and end up in v.skeys / v.spos (loc_sort_bucket_global).  All threads of the block call it.
+__device__ __forceinline__ bool loc_sort_bucket_lds(const LocView& v, uint32_t beg, uint32_t n, uint64_t* ak, uint32_t* ap,
+                                                    uint64_t* bk, uint32_t* bp) {
   const uint64_t* gk = v.bkeys + beg;
   const uint32_t* gp = v.bpos + beg;
-  const bool in_lds = n <= LOC_LDS_CAP && !v.force_global;
-  uint64_t* sk = bk;  // where the sorted bucket ends up (LDS path)
+  uint64_t* sk = bk;  // where the sorted bucket ends up
   uint32_t* sp = bp;
-  if (in_lds) {
-    // runs of 64: a wave ranks its 64 pairs against each other in registers — lane j's pair is broadcast with v_readlane, 64
-    // unrolled compares, no LDS round trip per compare (round 5: the LDS form waited out one ds_read latency per compare,
-    // 3.5 us per run) — and writes the sorted run to LDS
-    const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < n; c0 += LOC_SORT_THREADS) {  // wave-uniform: every lane is active below
-      const uint32_t idx = c0 + lane;
-      const bool valid = idx < n;
-      const uint64_t mk = valid ? gk[idx] : ~0ULL;  // the padding pair is less than nothing
-      const uint32_t mp = valid ? gp[idx] : ~0u;
-      const int klo = (int)(uint32_t)mk, khi = (int)(uint32_t)(mk >> 32);
-      uint32_t rank = 0;
-      // (4 at a time: at 8 the 24 SGPRs of broadcasts spilled into a VGPR; fully unrolled, the compiler reads all 192 words first
-      // and spills them)
-#pragma unroll 4
-      for (int j = 0; j < 64; ++j) {
-        const uint64_t ok = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(khi, j) << 32) | (uint32_t)__builtin_amdgcn_readlane(klo, j);
-        const uint32_t op = (uint32_t)__builtin_amdgcn_readlane((int)mp, j);
-        rank += comp_less(ok, op, mk, mp) ? 1u : 0u;
+  // runs of 64: a wave sorts its 64 pairs with a bitonic network held in registers (loc_net_sort64: no LDS, no barrier) and
+  // writes the sorted run to LDS; the padding pairs end up behind the run's valid ones
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < n; c0 += LOC_SORT_THREADS) {  // wave-uniform: every lane is active below
+    const uint32_t idx = c0 + lane;
+    const bool valid = idx < n;
+    const uint64_t mk = valid ? gk[idx] : ~0ULL;  // the padding pair is less than nothing
+    uint32_t klo = (uint32_t)mk, khi = (uint32_t)(mk >> 32);
+    uint32_t mp = valid ? gp[idx] : ~0u;
+    loc_net_sort64(klo, khi, mp);
+    if (valid) {
+      bk[idx] = ((uint64_t)khi << 32) | klo;
+      bp[idx] = mp;
+    }
+  }
+  __syncthreads();
+  // merge rounds: element's slot = its offset in its run + (# smaller elements in the sibling run).  A thread carries G of its
+  // (up to) LOC_LDS_CAP / LOC_SORT_THREADS elements through the search together: one LDS latency per step for G elements, not
+  // one per element and step.  The count is built from descending powers of two (the sibling run has at most L elements).
+  // G = 2 and the sibling run's bounds recomputed from the index at every step keep the kernel in 32 registers (all four
+  // elements carried at once took 60, which no longer fit beside the training step's kernels); a bucket of up to
+  // 2 * LOC_SORT_THREADS pairs (all but the rare oversize ones) still takes one pass per round.
+  constexpr int E = LOC_LDS_CAP / LOC_SORT_THREADS;
+  constexpr int G = 2;
+  static_assert(E * LOC_SORT_THREADS == LOC_LDS_CAP && E % G == 0 && LOC_SORT_THREADS % 64 == 0,
+                "a thread carries E elements of a full bucket, G at a time");
+  uint64_t* dk = ak;
+  uint32_t* dp = ap;
+  uint32_t sh = 6;
+  for (uint32_t L = 64; L < n; L <<= 1, ++sh) {
+    for (int g = 0; g < E && g * LOC_SORT_THREADS < (int)n; g += G) {  // block-uniform
+      // per element: the pair, and the search state as slots of the sibling run [at, end): `at` advances by the powers of two
+      // whose last slot is smaller than the pair (two registers; a count plus the run's start and length took three)
+      uint64_t mk[G];
+      uint32_t mp[G], at[G], end[G];
+#pragma unroll
+      for (int e = 0; e < G; ++e) {
+        const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
+        const bool valid = idx < n;
+        const uint32_t sib = ((idx >> sh) ^ 1u) << sh;
+        mk[e] = valid ? sk[idx] : 0ULL;
+        mp[e] = valid ? sp[idx] : 0u;
+        at[e] = min(sib, n);
+        end[e] = valid ? min(sib + L, n) : at[e];  // (a slot past the bucket tests nothing)
       }
-      if (valid) {
-        bk[c0 + rank] = mk;
-        bp[c0 + rank] = mp;
+      for (uint32_t step = L; step; step >>= 1) {
+        uint64_t ok[G];
+        uint32_t op[G];
+#pragma unroll
+        for (int e = 0; e < G; ++e) {
+          const uint32_t q = at[e] + step <= end[e] ? at[e] + step - 1u : 0u;  // slot 0 when there is nothing to test: always readable
+          ok[e] = sk[q];
+          op[e] = sp[q];
+        }
+#pragma unroll
+        for (int e = 0; e < G; ++e)
+          if (at[e] + step <= end[e] && comp_less(ok[e], op[e], mk[e], mp[e])) at[e] += step;
+      }
+#pragma unroll
+      for (int e = 0; e < G; ++e) {
+        const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
+        if (idx < n) {
+          // slot = start of the run pair + offset in the own run + smaller pairs in the sibling run (at - sibling start)
+          //      = idx + at - (start of the pair's SECOND run, capped at n), whichever of the two runs the pair is in
+          const uint32_t dst = idx + at[e] - min((idx & ~(L - 1u)) | L, n);
+          dk[dst] = mk[e];
+          dp[dst] = mp[e];
+        }
       }
     }
     __syncthreads();
-    // merge rounds: element's slot = its offset in its run + (# smaller elements in the sibling run).  A thread carries G of its
-    // (up to) LOC_LDS_CAP / LOC_SORT_THREADS elements through the search together: one LDS latency per step for G elements, not
-    // one per element and step.  The count is built from descending powers of two (the sibling run has at most L elements).
-    // G = 2 and the sibling run's bounds recomputed from the index at every step keep the kernel in 32 registers (all four
-    // elements carried at once took 60, which no longer fit beside the training step's kernels); a bucket of up to
-    // 2 * LOC_SORT_THREADS pairs (all but the rare oversize ones) still takes one pass per round.
-    constexpr int E = LOC_LDS_CAP / LOC_SORT_THREADS;
-    constexpr int G = 2;
-    static_assert(E * LOC_SORT_THREADS == LOC_LDS_CAP && E % G == 0 && LOC_SORT_THREADS % 64 == 0,
-                  "a thread carries E elements of a full bucket, G at a time");
-    uint64_t* dk = ak;
-    uint32_t* dp = ap;
-    uint32_t sh = 6;
-    for (uint32_t L = 64; L < n; L <<= 1, ++sh) {
-      for (int g = 0; g < E && g * LOC_SORT_THREADS < (int)n; g += G) {  // block-uniform
-        // per element: the pair, and the search state as slots of the sibling run [at, end): `at` advances by the powers of two
-        // whose last slot is smaller than the pair (two registers; a count plus the run's start and length took three)
-        uint64_t mk[G];
-        uint32_t mp[G], at[G], end[G];
-#pragma unroll
-        for (int e = 0; e < G; ++e) {
-          const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
-          const bool valid = idx < n;
-          const uint32_t sib = ((idx >> sh) ^ 1u) << sh;
-          mk[e] = valid ? sk[idx] : 0ULL;
-          mp[e] = valid ? sp[idx] : 0u;
-          at[e] = min(sib, n);
-          end[e] = valid ? min(sib + L, n) : at[e];  // (a slot past the bucket tests nothing)
-        }
-        for (uint32_t step = L; step; step >>= 1) {
-          uint64_t ok[G];
-          uint32_t op[G];
-#pragma unroll
-          for (int e = 0; e < G; ++e) {
-            const uint32_t q = at[e] + step <= end[e] ? at[e] + step - 1u : 0u;  // slot 0 when there is nothing to test: always readable
-            ok[e] = sk[q];
-            op[e] = sp[q];
-          }
-#pragma unroll
-          for (int e = 0; e < G; ++e)
-            if (at[e] + step <= end[e] && comp_less(ok[e], op[e], mk[e], mp[e])) at[e] += step;
-        }
-#pragma unroll
-        for (int e = 0; e < G; ++e) {
-          const uint32_t idx = threadIdx.x + (g + e) * LOC_SORT_THREADS;
-          if (idx < n) {
-            // slot = start of the run pair + offset in the own run + smaller pairs in the sibling run (at - sibling start)
-            //      = idx + at - (start of the pair's SECOND run, capped at n), whichever of the two runs the pair is in
-            const uint32_t dst = idx + at[e] - min((idx & ~(L - 1u)) | L, n);
-            dk[dst] = mk[e];
-            dp[dst] = mp[e];
-          }
-        }
-      }
-      __syncthreads();
-      uint64_t* tk = sk; sk = dk; dk = tk;
-      uint32_t* tp = sp; sp = dp; dp = tp;
+    uint64_t* tk = sk; sk = dk; dk = tk;
+    uint32_t* tp = sp; sp = dp; dp = tp;
+  }
+  return sk == ak;
+}
+__device__ __forceinline__ void loc_sort_bucket_global(const LocView& v, uint32_t beg, uint32_t n) {
+  // oversize bucket (stale or unlucky splitters; kept for correctness and bounded at n log n):
+  // run ranking + merge rounds on the global arrays, ping-ponging between the
+  // bucket-major and the sorted buffers
+  uint64_t* xk = v.bkeys + beg;
+  uint32_t* xp = v.bpos + beg;
+  uint64_t* yk = v.skeys + beg;
+  uint32_t* yp = v.spos + beg;
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < n; c0 += LOC_SORT_THREADS) {
+    const uint32_t idx = c0 + lane;
+    const bool valid = idx < n;
+    const uint64_t mk = valid ? xk[idx] : ~0ULL;
+    const uint32_t mp = valid ? xp[idx] : ~0u;
+    const uint32_t lim = min(64u, n - c0);
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < lim; ++j) rank += comp_less(xk[c0 + j], xp[c0 + j], mk, mp) ? 1u : 0u;
+    if (valid) {
+      yk[c0 + rank] = mk;
+      yp[c0 + rank] = mp;
     }
-    *sk_out = sk;
-    *sp_out = sp;
-  } else {
-    // oversize bucket (stale or unlucky splitters; kept for correctness and bounded at n log n):
-    // the same run-ranking + merge rounds on the global arrays, ping-ponging between the
-    // bucket-major and the sorted buffers
-    uint64_t* xk = v.bkeys + beg;
-    uint32_t* xp = v.bpos + beg;
-    uint64_t* yk = v.skeys + beg;
-    uint32_t* yp = v.spos + beg;
-    const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < n; c0 += LOC_SORT_THREADS) {
-      const uint32_t idx = c0 + lane;
-      const bool valid = idx < n;
-      const uint64_t mk = valid ? xk[idx] : ~0ULL;
-      const uint32_t mp = valid ? xp[idx] : ~0u;
-      const uint32_t lim = min(64u, n - c0);
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < lim; ++j) rank += comp_less(xk[c0 + j], xp[c0 + j], mk, mp) ? 1u : 0u;
-      if (valid) {
-        yk[c0 + rank] = mk;
-        yp[c0 + rank] = mp;
+  }
+  __syncthreads();  // block-scope visibility of global stores
+  uint64_t* srck = yk; uint32_t* srcp = yp;
+  uint64_t* dstk = xk; uint32_t* dstp = xp;
+  for (uint32_t L = 64; L < n; L <<= 1) {
+    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
+      const uint64_t mk = srck[idx];
+      const uint32_t mp = srcp[idx];
+      const uint32_t r = idx / L;
+      const uint32_t pair_base = (r & ~1u) * L;
+      const uint32_t sib = (r ^ 1u) * L;
+      uint32_t lo = min(sib, n), hi = min(sib + L, n);
+      const uint32_t sib_beg = lo;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (comp_less(srck[mid], srcp[mid], mk, mp)) lo = mid + 1; else hi = mid;
       }
-    }
-    __syncthreads();  // block-scope visibility of global stores
-    uint64_t* srck = yk; uint32_t* srcp = yp;
-    uint64_t* dstk = xk; uint32_t* dstp = xp;
-    for (uint32_t L = 64; L < n; L <<= 1) {
-      for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
-        const uint64_t mk = srck[idx];
-        const uint32_t mp = srcp[idx];
-        const uint32_t r = idx / L;
-        const uint32_t pair_base = (r & ~1u) * L;
-        const uint32_t sib = (r ^ 1u) * L;
-        uint32_t lo = min(sib, n), hi = min(sib + L, n);
-        const uint32_t sib_beg = lo;
-        while (lo < hi) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if (comp_less(srck[mid], srcp[mid], mk, mp)) lo = mid + 1; else hi = mid;
-        }
-        const uint32_t dst = pair_base + (idx - r * L) + (lo - sib_beg);
-        dstk[dst] = mk;
-        dstp[dst] = mp;
-      }
-      __syncthreads();
-      uint64_t* tk = srck; srck = dstk; dstk = tk;
-      uint32_t* tp = srcp; srcp = dstp; dstp = tp;
-    }
-    if (srck != yk) {  // result must live in skeys/spos
-      for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
-        yk[t] = srck[t];
-        yp[t] = srcp[t];
-      }
+      const uint32_t dst = pair_base + (idx - r * L) + (lo - sib_beg);
+      dstk[dst] = mk;
+      dstp[dst] = mp;
     }
     __syncthreads();
+    uint64_t* tk = srck; srck = dstk; dstk = tk;
+    uint32_t* tp = srcp; srcp = dstp; dstp = tp;
   }
-  if (!in_lds) {
-    *sk_out = v.skeys + beg;
-    *sp_out = v.spos + beg;
+  if (srck != yk) {  // result must live in skeys/spos
+    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x) {
+      yk[t] = srck[t];
+      yp[t] = srcp[t];
+    }
   }
-  return in_lds;
+  __syncthreads();
 }
 
 // bucket summary: {runs of equal keys, local index of the last run head, first key, last key}; valid in
-// thread 0 only.  red: [2][LOC_SORT_THREADS / 64] shared words.
+// thread 0 only.  red: [2][LOC_SORT_THREADS / 64] shared words.  WRITE: the sorted bucket (in LDS) goes to ok / op on the
+// way: the run heads are counted in the pass that writes the bucket out, which reads every key anyway.
 struct BucketSummary {
   uint32_t nheads, lh;
   uint64_t first_key, last_key;
 };
-__device__ __forceinline__ BucketSummary loc_bucket_summary(const uint64_t* sk, uint32_t n, uint32_t (*red)[LOC_SORT_THREADS / 64]) {
+template <bool WRITE>
+__device__ __forceinline__ BucketSummary loc_bucket_summary(const uint64_t* sk, const uint32_t* sp, uint32_t n, uint64_t* ok,
+                                                            uint32_t* op, uint32_t (*red)[LOC_SORT_THREADS / 64]) {
   uint32_t cnt = 0, last = 0;
-  for (uint32_t t = 1 + threadIdx.x; t < n; t += blockDim.x) {
-    if (sk[t] != sk[t - 1]) {
+  // (the thread's first index is opaque to the compiler: it computed this loop's six address registers once per kernel and
+  // kept them live through the merge rounds, which takes the kernel past 32 registers: 34 used, 40 allocated without this line,
+  // profiles/r10_prep_registers.txt)
+  uint32_t t0 = threadIdx.x;
+  asm volatile("" : "+v"(t0));
+  for (uint32_t t = t0; t < n; t += LOC_SORT_THREADS) {
+    const uint64_t k = sk[t];
+    if (WRITE) {
+      ok[t] = k;
+      op[t] = sp[t];
+    }
+    // the thread tests the pair that FOLLOWS its own for a run head (the pair before it would make the loop's address
+    // register start 8 bytes below the array, in front of the LDS when the bucket sits at its start)
+    if (t + 1 < n && sk[t + 1] != k) {
       ++cnt;
-      last = t;  // ascending t per thread
+      last = t + 1;  // ascending t per thread
     }
   }
   // wave totals: lane 63 of the in-wave scans (the __shfl_xor butterfly kept six lane-address registers live through the kernel)
@@ -761,15 +840,14 @@ __device__ __forceinline__ void loc_sort_block(const LocView& v, const uint32_t 
       }
       continue;
     }
-    const uint64_t* sk;
-    const uint32_t* sp;
-    if (loc_sort_bucket(v, beg, n, ak, ap, bk, bp, &sk, &sp)) {
-      for (uint32_t t = threadIdx.x; t < n; t += LOC_SORT_THREADS) {
-        v.skeys[beg + t] = sk[t];
-        v.spos[beg + t] = sp[t];
-      }
+    BucketSummary sm;
+    if (n <= LOC_LDS_CAP && !v.force_global) {
+      const bool in_a = loc_sort_bucket_lds(v, beg, n, ak, ap, bk, bp);
+      sm = loc_bucket_summary<true>(in_a ? ak : bk, in_a ? ap : bp, n, v.skeys + beg, v.spos + beg, red);
+    } else {
+      loc_sort_bucket_global(v, beg, n);
+      sm = loc_bucket_summary<false>(v.skeys + beg, v.spos + beg, n, nullptr, nullptr, red);
     }
-    const BucketSummary sm = loc_bucket_summary(sk, n, red);
     if (threadIdx.x == 0) {
       v.nheads[b] = sm.nheads;
       v.lh[b] = sm.lh;
