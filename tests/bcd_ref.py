@@ -250,3 +250,168 @@ def split_rows(off, ids, val, lab, rows):
         r0 += n
     assert r0 == len(off) - 1
     return out
+
+
+# ---- designed inputs and censuses: what tests/test_bcd_shapes.py builds its cases from and proves them with
+
+def bcd_with_ranges(train, val, ranges, **kw):
+    """BCD over explicit block ranges (of ReverseBytes keys, sorted and disjoint) in place of PartitionFeature's"""
+    ref = BCD(train, val, stats=np.ones(3, np.float32), **kw)
+    ref.ranges = [tuple(int(v) for v in r) for r in ranges]
+    ref.pos = [(int(np.searchsorted(ref.keys, np.uint64(b))), int(np.searchsorted(ref.keys, np.uint64(e))))
+               for b, e in ref.ranges]
+    return ref
+
+
+def designed_chunk(counts_per_block, nrows, seed, binary=False, dup=(), empty_rows=0, solo=(), zero_keys=(), scale=1.0,
+                   bands=False, dyadic=False):
+    """A chunk whose key-ordered layout is chosen: counts_per_block[b] lists the entry count of every key of block b
+    (0: the key is absent).  Keys are 1, 2, 3, ... in ReverseBytes space (raw id = reverse_bytes(key)), block b owns the
+    contiguous key range of its list, so the chunk's key-ordered entries are key 1's, then key 2's, ...: a key's place
+    in its block's slice is the sum of the counts before it.  Each key goes into `count` distinct rows drawn from the
+    seeded generator; the entries of a row come in shuffled key order.
+      dup         keys whose last entry repeats the row of their first (count - 1 distinct rows)
+      empty_rows  this many rows (the last ones) hold nothing
+      solo        keys whose entries each get a row that no other key shares
+      zero_keys   keys whose values are all 0.0
+      scale       factor on the N(0, 1) values
+      bands       block b's keys draw their rows from the b-th band of rows only: no row is shared between blocks
+      dyadic      values rounded to multiples of 2^-10 (with pred = 0 every fp64 sum of terms is then exact)
+    -> (offset, ids, value or None, label), ranges"""
+    rng = np.random.default_rng(seed)
+    nkeys = [len(c) for c in counts_per_block]
+    first = np.concatenate([[1], 1 + np.cumsum(nkeys)]).astype(np.int64)
+    ranges = [(int(first[b]), int(first[b + 1])) for b in range(len(nkeys))]
+    nsolo = sum(int(c) for b, cs in enumerate(counts_per_block) for i, c in enumerate(cs) if first[b] + i in solo)
+    free = nrows - empty_rows - nsolo          # rows [0, free) take the drawn keys, [free, free + nsolo) the solo ones
+    assert free > 0
+    nb = len(nkeys)
+    rows, keys = [], []
+    next_solo = free
+    for b, cs in enumerate(counts_per_block):
+        lo, hi = (b * free // nb, (b + 1) * free // nb) if bands else (0, free)
+        for i, c in enumerate(cs):
+            k, c = int(first[b] + i), int(c)
+            if c == 0:
+                continue
+            if k in solo:
+                r = np.arange(next_solo, next_solo + c)
+                next_solo += c
+            elif k in dup:
+                assert c >= 2
+                r = lo + rng.choice(hi - lo, c - 1, replace=False)
+                r = np.concatenate([r, r[:1]])
+            else:
+                r = lo + rng.choice(hi - lo, c, replace=False)
+            rows.append(r)
+            keys.append(np.full(c, k, np.int64))
+    rows, keys = np.concatenate(rows), np.concatenate(keys)
+    o = np.lexsort((rng.random(len(rows)), rows))          # row order, a row's entries shuffled
+    rows, keys = rows[o], keys[o]
+    off = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=nrows))]).astype(np.uint64)
+    ids = reverse_bytes_np(keys.astype(np.uint64))
+    val = None
+    if not binary:
+        val = (rng.normal(size=len(keys)) * scale).astype(np.float32)
+        if dyadic:
+            val = (np.round(val * 1024) / 1024).astype(np.float32)
+        val[np.isin(keys, list(zero_keys))] = 0
+    lab = (rng.random(nrows) < 0.4).astype(np.float32)
+    return (off, ids, val, lab), ranges
+
+
+def share_census(ref, c, blk):
+    """Where the keys of block blk lie in chunk c of ref, on the device's grid: 128-entry shares in two 64-entry steps
+    counted from the start of the block's slice of the key-ordered entries (filtered keys included, gk = -1).
+    -> dict: start (the slice's first entry), start_mod (start % 128), n (entries), nshares;
+       per key of the slice, in order: key, gk (-1 filtered), first, last (entry positions in the slice), count,
+         follow (shares after its first that its entries reach), begins_step / begins_share / ends_step / ends_share
+         (its first entry opens, its last entry closes a step / share);
+       per share boundary inside the slice: b_at (position of the entry behind it), b_lkey / b_rkey (the keys before
+         and behind it), b_lgk / b_rgk"""
+    lo, hi = ref.ranges[blk]
+    c0, c1 = int(np.searchsorted(c.keys, np.uint64(lo))), int(np.searchsorted(c.keys, np.uint64(hi)))
+    a, b = int(np.searchsorted(c.col, c0)), int(np.searchsorted(c.col, c1))
+    col, gk = c.col[a:b], c.gk[a:b]
+    n = b - a
+    head = np.flatnonzero(np.r_[True, col[1:] != col[:-1]]) if n else np.zeros(0, np.int64)
+    last = np.r_[head[1:], n] - 1 if n else np.zeros(0, np.int64)
+    at = np.arange(128, n, 128)
+    return dict(start=a, start_mod=a % 128, n=n, nshares=(n + 127) // 128,
+                key=c.keys[col[head]], gk=gk[head], first=head, last=last, count=last - head + 1,
+                follow=last // 128 - head // 128,
+                begins_step=head % 64 == 0, begins_share=head % 128 == 0,
+                ends_step=(last + 1) % 64 == 0, ends_share=(last + 1) % 128 == 0,
+                b_at=at, b_lkey=c.keys[col[at - 1]], b_rkey=c.keys[col[at]], b_lgk=gk[at - 1], b_rgk=gk[at])
+
+
+def update_census(g, h, w, delta, l1, lr):
+    """which branch of update_weight every key takes -> dict of masks: pos (g_pos <= u w), neg (g_neg >= u w),
+    zero_nz / zero_z (neither, with w != 0 / w == 0), clamp_lo, clamp_hi, cap (the new delta is max_val = 5),
+    h0 (h == 0, so u = 1e-10f), negzero (the step is -0.0)"""
+    g, h, w, delta = (np.asarray(a, np.float32) for a in (g, h, w, delta))
+    g_pos, g_neg = g + f32(l1), g - f32(l1)
+    u = ((h / f32(lr)).astype(np.float64) + 1e-10).astype(np.float32)
+    uw = u * w
+    pos = g_pos <= uw
+    neg = ~pos & (g_neg >= uw)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.where(pos, -g_pos / u, np.where(neg, -g_neg / u, -w)).astype(np.float32)
+    lo = d < -delta
+    d = np.where(lo, -delta, d)
+    hi = delta < d
+    d = np.where(hi, delta, d).astype(np.float32)
+    nd = (np.abs(d).astype(np.float64) * 2.0 + .1).astype(np.float32)
+    return dict(pos=pos, neg=neg, zero_nz=~pos & ~neg & (w != 0), zero_z=~pos & ~neg & (w == 0), clamp_lo=lo, clamp_hi=hi,
+                cap=~(nd < f32(5)), h0=h == 0, negzero=(d == 0) & np.signbit(d))
+
+
+# ---- a device object (capi.Bcd) against the restatement, shared by the GPU tests
+
+def make_device(capi, ctx, chunks, ranges, l1=.1, lr=.8, tail=0, val=()):
+    o = capi.Bcd(ctx)
+    for c in chunks:
+        o.add_chunk(*c)
+    for c in val:
+        o.add_chunk(*c, is_val=True)
+    o.build(ranges, tail_feature_filter=tail, l1=l1, lr=lr)
+    return o
+
+
+def device_preds(o, ref):
+    """the device's predictions of ref's chunks, training then validation"""
+    return [o.get_pred(i) for i in range(len(ref.tr))] + [o.get_pred(i, is_val=True) for i in range(len(ref.va))]
+
+
+def same_bits(a, b):
+    return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+def check_block(o, ref, blk):
+    """one step of block blk on the device against the restatement, from the device's own state: g and h within
+    1e-6 of the sums of |terms|; w, delta, delta w and every training and validation chunk's pred bit for bit"""
+    chunks = ref.tr + list(ref.va)
+    for c, p in zip(chunks, device_preds(o, ref)):
+        c.pred = p.copy()
+    m = o.get_model()
+    assert np.array_equal(m["keys"], ref.keys)
+    ref.w, ref.delta = m["w"].copy(), m["delta"].copy()
+    g_want, h_want, g_mag, h_mag = ref.grad(blk, mag=True)
+    g, h, _ = o.step(blk, grad=True)
+    # the float terms differ by the ulps of the two expf: relative to the sum of |terms| (the fp64 sums themselves are
+    # far tighter), which is |g| where no terms cancel
+    assert np.all(np.abs(g - g_want) <= 1e-6 * g_mag), np.max(np.abs(g - g_want) / np.maximum(g_mag, 1e-300))
+    assert np.all(np.abs(h - h_want) <= 1e-6 * h_mag), np.max(np.abs(h - h_want) / np.maximum(h_mag, 1e-300))
+    pb, pe = ref.pos[blk]
+    w, d, dw = update_weight(g.astype(np.float32), h.astype(np.float32), ref.w[pb:pe], ref.delta[pb:pe], ref.l1, ref.lr)
+    m2 = o.get_model()
+    assert np.array_equal(m2["w"][pb:pe].view(np.uint32), w.view(np.uint32))
+    assert np.array_equal(m2["delta"][pb:pe].view(np.uint32), d.view(np.uint32))
+    assert np.array_equal(m2["dw"][pb:pe].view(np.uint32), dw.view(np.uint32))
+    out = np.r_[0:pb, pe:len(ref.w)]   # the other blocks' keys stay as they were
+    assert same_bits(m2["w"][out], ref.w[out]) and same_bits(m2["delta"][out], ref.delta[out])
+    ref.w, ref.delta, ref.dw = m2["w"].copy(), m2["delta"].copy(), m2["dw"].copy()
+    ref.update_pred(blk)
+    for i, (c, p) in enumerate(zip(chunks, device_preds(o, ref))):
+        assert same_bits(p, c.pred), "pred of chunk %d (training first) not bit-identical" % i
+    return g

@@ -1,6 +1,8 @@
 """The kernels of learner = bcd (difacto_amd/csrc/dfh_bcd.hip) through capi.Bcd against the numpy restatement of the
 reference (tests/bcd_ref.py): one block's g and h (fp64), UpdateWeight in float, the float prediction update bit for bit,
-the split-key path, empty blocks, the AUC path beyond 32 768 rows and run-to-run determinism."""
+the split-key path, empty blocks, the AUC path beyond 32 768 rows and run-to-run determinism.  The step check itself
+(R.check_block) and R.make_device live in tests/bcd_ref.py, shared with tests/test_bcd_shapes.py, which runs the same
+check on inputs designed to sit on the kernels' share, step and chain boundaries."""
 import os
 
 import numpy as np
@@ -27,53 +29,17 @@ def ctx(capi):
     c.close()
 
 
-def _make(capi, ctx, chunks, ranges, l1=.1, lr=.8, tail=0, val=()):
-    o = capi.Bcd(ctx)
-    for c in chunks:
-        o.add_chunk(*c)
-    for c in val:
-        o.add_chunk(*c, is_val=True)
-    o.build(ranges, tail_feature_filter=tail, l1=l1, lr=lr)
-    return o
-
-
-def _check_block(o, ref, blk, chunks):
-    """one step of block blk on the device against the restatement, from the device's own state"""
-    for i, c in enumerate(ref.tr):
-        c.pred = o.get_pred(i).copy()
-    m = o.get_model()
-    assert np.array_equal(m["keys"], ref.keys)
-    ref.w, ref.delta = m["w"].copy(), m["delta"].copy()
-    g_want, h_want, g_mag, h_mag = ref.grad(blk, mag=True)
-    g, h, _ = o.step(blk, grad=True)
-    # the float terms differ by the ulps of the two expf: relative to the sum of |terms| (the fp64 sums themselves are
-    # far tighter), which is |g| where no terms cancel
-    assert np.all(np.abs(g - g_want) <= 1e-6 * g_mag), np.max(np.abs(g - g_want) / np.maximum(g_mag, 1e-300))
-    assert np.all(np.abs(h - h_want) <= 1e-6 * h_mag), np.max(np.abs(h - h_want) / np.maximum(h_mag, 1e-300))
-    pb, pe = ref.pos[blk]
-    w, d, dw = R.update_weight(g.astype(np.float32), h.astype(np.float32), ref.w[pb:pe], ref.delta[pb:pe], ref.l1, ref.lr)
-    m2 = o.get_model()
-    assert np.array_equal(m2["w"][pb:pe].view(np.uint32), w.view(np.uint32))
-    assert np.array_equal(m2["delta"][pb:pe].view(np.uint32), d.view(np.uint32))
-    assert np.array_equal(m2["dw"][pb:pe].view(np.uint32), dw.view(np.uint32))
-    ref.w, ref.delta, ref.dw = m2["w"].copy(), m2["delta"].copy(), m2["dw"].copy()
-    ref.update_pred(blk)
-    for i, c in enumerate(ref.tr):
-        assert np.array_equal(o.get_pred(i).view(np.uint32), c.pred.view(np.uint32)), "pred not bit-identical"
-    return g
-
-
 def test_block_step_matches_restatement(capi, ctx):
     d = R.read_libsvm(DATA)
     chunks = R.split_rows(*d, [30, 25, 45])
     ref = R.BCD(chunks, l1=.1, lr=.8, block_ratio=1, tail_feature_filter=0, stats=R.fea_group_stats([(d[0], d[1])], 0))
-    o = _make(capi, ctx, chunks, ref.ranges)
+    o = R.make_device(capi, ctx, chunks, ref.ranges)
     try:
         assert o.nkeys == len(ref.keys)
         rng = np.random.default_rng(0)
         steps = 0
         for blk in list(rng.permutation(len(ref.ranges)))[:30] * 2:   # every block twice: pred and w are non-zero the 2nd time
-            g = _check_block(o, ref, int(blk), chunks)
+            g = R.check_block(o, ref, int(blk))
             steps += len(g) > 0
         assert steps > 10
     finally:
@@ -94,10 +60,10 @@ def test_split_key_path_and_radix_auc(capi, ctx):
     ranges = [(0, R.U64)]
     ref = R.BCD([chunk], l1=.1, lr=.8, block_ratio=1, tail_feature_filter=0)
     ref.ranges, ref.pos = ranges, [(0, len(ref.keys))]
-    o = _make(capi, ctx, [chunk], ranges)
+    o = R.make_device(capi, ctx, [chunk], ranges)
     try:
         for _ in range(2):
-            _check_block(o, ref, 0, [chunk])
+            R.check_block(o, ref, 0)
         _, _, prog = o.step(0, progress=True)
         pred = o.get_pred(0)
         y = np.where(lab > 0, 1.0, -1.0)
@@ -115,7 +81,7 @@ def test_empty_blocks_and_epochs(capi, ctx):
     """block_ratio 10 on the golden data: 881 blocks for 2 775 keys, some of them empty; epochs follow the restatement"""
     d = R.read_libsvm(DATA)
     ref = R.BCD([d], l1=.1, lr=.8, block_ratio=10, tail_feature_filter=0)
-    o = _make(capi, ctx, [d], ref.ranges)
+    o = R.make_device(capi, ctx, [d], ref.ranges)
     try:
         info = [o.block_info(b) for b in range(len(ref.ranges))]
         empty = [b for b, i in enumerate(info) if i[2] == 0]
@@ -145,7 +111,7 @@ def test_epochs_are_deterministic(capi, ctx):
     ranges = R.partition_feature(0, [(0, 7)])
     out = []
     for _ in range(2):
-        o = _make(capi, ctx, chunks, ranges, val=[chunks[0]])
+        o = R.make_device(capi, ctx, chunks, ranges, val=[chunks[0]])
         try:
             progs = [o.epoch([3, 1, 6, 0, 2, 5, 4]) for _ in range(3)]
             out.append((np.array(progs), o.get_model()["w"], o.get_pred(0), o.get_pred(0, is_val=True)))
