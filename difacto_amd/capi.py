@@ -37,6 +37,7 @@ SYMBOLS = [
     "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
     "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate", "dfh_lbfgs_create_sharded",
+    "dfh_lbfgs_owned_range", "dfh_lbfgs_set_model", "dfh_bcd_set_model",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
 ]
@@ -226,6 +227,8 @@ def lib():
     L.dfh_lbfgs_shape.argtypes = [vp, PP(u64), PP(u64), PP(i32), PP(i32)]
     L.dfh_lbfgs_get_model.argtypes = [vp, vp, vp, vp, vp]
     L.dfh_lbfgs_set_weights.argtypes = [vp, vp]
+    L.dfh_lbfgs_owned_range.argtypes = [vp, PP(u64), PP(u64)]
+    L.dfh_lbfgs_set_model.argtypes = [vp, u64, vp, vp, vp, PP(u64)]
     L.dfh_lbfgs_calc_grad.argtypes = [vp, f32, PP(f32), PP(f32)]
     L.dfh_lbfgs_prepare_direction.argtypes = [vp, vp, PP(i32)]
     L.dfh_lbfgs_calc_direction.argtypes = [vp, vp, PP(f32)]
@@ -239,6 +242,7 @@ def lib():
     L.dfh_bcd_block_info.argtypes = [vp, i32, PP(i32), PP(i32), PP(u64), PP(u64)]
     L.dfh_bcd_epoch.argtypes = [vp, vp, i32, vp]
     L.dfh_bcd_step.argtypes = [vp, i32, vp, vp, vp]
+    L.dfh_bcd_set_model.argtypes = [vp, u64, vp, vp, PP(u64)]
     L.dfh_bcd_get_model.argtypes = [vp, vp, vp, vp, vp, vp]
     L.dfh_bcd_get_pred.argtypes = [vp, i32, i32, vp, PP(sz)]
     _lib = L
@@ -809,6 +813,23 @@ class Lbfgs:
         w = np.ascontiguousarray(w, np.float32)
         _ck(lib().dfh_lbfgs_set_weights(self.h, _p(w)))
 
+    def owned_range(self):
+        """-> [key_lo, key_hi) of this rank's keys (key_hi = 0: no upper bound)"""
+        lo, hi = C.c_uint64(0), C.c_uint64(0)
+        _ck(lib().dfh_lbfgs_owned_range(self.h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def set_model(self, keys, lens, vals):
+        """start from a model given by key (unique keys in any order, lens in {1, 1 + V_dim}, vals ragged: w then V);
+        -> the number of input keys that are keys of the model (summed over ranks on a sharded object)"""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        lens = np.ascontiguousarray(lens, np.int32)
+        vals = np.ascontiguousarray(vals, np.float32)
+        assert len(lens) == len(keys) and len(vals) == int(lens.sum())
+        m = C.c_uint64(0)
+        _ck(lib().dfh_lbfgs_set_model(self.h, len(keys), _p(keys), _p(lens), _p(vals), C.byref(m)))
+        return m.value
+
     def calc_grad(self, gamma=1.0):
         loss, auc = C.c_float(0), C.c_float(0)
         _ck(lib().dfh_lbfgs_calc_grad(self.h, gamma, C.byref(loss), C.byref(auc)))
@@ -893,6 +914,16 @@ class Bcd:
         prog = np.zeros(4, np.float32) if progress else None
         _ck(lib().dfh_bcd_step(self.h, blk, _p(g), _p(h), _p(prog)))
         return (g[:e - b] if grad else None), (h[:e - b] if grad else None), prog
+
+    def set_model(self, keys, w):
+        """start from a model (unique ReverseBytes keys in any order); the predictions of every chunk are rebuilt;
+        -> the number of input keys that are keys of the model"""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        w = np.ascontiguousarray(w, np.float32)
+        assert len(keys) == len(w)
+        m = C.c_uint64(0)
+        _ck(lib().dfh_bcd_set_model(self.h, len(keys), _p(keys), _p(w), C.byref(m)))
+        return m.value
 
     def get_model(self):
         n = max(self.nkeys, 1)

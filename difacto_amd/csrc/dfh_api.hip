@@ -3840,5 +3840,6 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 }  // extern "C"
 
 #include "dfh_shard.hip"
+#include "dfh_join.hip"
 #include "dfh_lbfgs.hip"
 #include "dfh_bcd.hip"

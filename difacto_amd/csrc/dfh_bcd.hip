@@ -10,6 +10,16 @@
 //                                                                              ascending, dw == 0 skipped
 //   progress                  bcd_learner.cc:295-314, bin_class_metric.h:35-91 k_bcd_prog (objv, accuracy) + the AUC path
 //
+// Warm start (dfh_bcd_set_model; the reference declares model_in, bcd_param.h:44, and never reads it): the input keys are
+// joined onto the model's ascending keys on the device (dfh_join.hip), matched keys take the input's w, every other key
+// keeps w = 0, delta = 1 and delta w = 0 stay as dfh_bcd_build leaves them.  The predictions of every training and
+// validation chunk are then rebuilt from w.  Definition, per row r:
+//   pred[r] = 0.f; for every surviving entry of the row whose key lies in a block, in ascending model position
+//   (ascending block, then ascending column inside the block): if (w != 0) pred[r] = pred[r] + w * x   (x = 1 in a
+//   chunk without values), in float, without contraction
+// which is what k_bcd_pred computes from pred = 0 with delta w := w, block after block in ascending block order: that
+// is how it is done, so the bits are those of an epoch's own prediction updates.  No float atomics.
+//
 // Layouts of a chunk (built once, dfh_bcd_build), both cut into contiguous per-block slices:
 //   column-major: the Localizer's key-ordered view (col_ptr, s_row, s_val) plus s_gk, the model position of every entry
 //                 (-1: a filtered key); block b's entries are [nz[b].x, nz[b].y)
@@ -302,6 +312,15 @@ __global__ void k_bcd_prog_finish(const double* __restrict__ part, int nparts, d
   out[1] = c;
 }
 
+// warm start: the matched input keys' w into the model (pos from the key join; input keys are unique: one writer per w)
+__global__ void __launch_bounds__(THREADS) k_bcd_set_w(const int32_t* __restrict__ pos, const float* __restrict__ win, uint64_t n,
+                                                       float* __restrict__ w) {
+  const uint64_t i = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int32_t p = pos[i];
+  if (p >= 0) w[p] = win[i];
+}
+
 // ---- layout build (once per chunk)
 // per entry of the key-ordered view: its column (binary search in col_ptr), its model position and the sort key
 // (block << 32 | row) of the row-major layout (~0: a filtered key or a key in no block, sorted behind everything)
@@ -392,6 +411,7 @@ struct dfh_bcd {
   };
   std::vector<Chunk> chunks[2];   // [0] training, [1] validation
   bool built = false;
+  bool stepped = false;           // a block step has run: the model can no longer be replaced
   int nblk = 0;
   float l1 = 1, lr = .9f;
   std::vector<uint64_t> keys;     // the model's keys (filtered, ascending)
@@ -860,6 +880,7 @@ int dfh_bcd_epoch(dfh_bcd* o, const int* order, int n, float* progress) {
   for (int i = 0; i < n; ++i) DFH_ARG(order[i] >= 0 && order[i] < o->nblk, "dfh_bcd_epoch: a block id out of range");
   DFH_HIP(hipSetDevice(o->ctx->device));
   hipStream_t s = o->ctx->stream;
+  o->stepped = true;
   o->h_order.assign(order, order + n);
   DFH_HIP(hipMemcpyAsync(o->d_order, o->h_order.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
   for (int i = 0; i < n; ++i) {
@@ -877,6 +898,7 @@ int dfh_bcd_step(dfh_bcd* o, int blk, double* g, double* h, float* progress) {
   DFH_ARG(o && o->built && blk >= 0 && blk < o->nblk, "dfh_bcd_step: bad argument");
   DFH_HIP(hipSetDevice(o->ctx->device));
   hipStream_t s = o->ctx->stream;
+  o->stepped = true;
   o->h_order.assign(1, blk);
   DFH_HIP(hipMemcpyAsync(o->d_order, o->h_order.data(), sizeof(int), hipMemcpyHostToDevice, s));
   const bool keep = g || h;
@@ -891,6 +913,75 @@ int dfh_bcd_step(dfh_bcd* o, int blk, double* g, double* h, float* progress) {
   }
   if (progress) return bcd_progress(o, progress);
   DFH_HIP(hipStreamSynchronize(s));
+  return DFH_OK;
+}
+
+int dfh_bcd_set_model(dfh_bcd* o, uint64_t n, const uint64_t* keys, const float* w, uint64_t* n_matched) {
+  DFH_ARG(o && (n == 0 || (keys && w)), "dfh_bcd_set_model: NULL argument");
+  if (!o->built) {
+    set_error("dfh_bcd_set_model: the layouts are not built (call dfh_bcd_build first)");
+    return DFH_ERR_STATE;
+  }
+  if (o->stepped) {
+    set_error("dfh_bcd_set_model: a block step has run: the model is set before the first dfh_bcd_epoch / dfh_bcd_step");
+    return DFH_ERR_STATE;
+  }
+  for (uint64_t i = 0; i < n; ++i) DFH_ARG(std::isfinite(w[i]), "dfh_bcd_set_model: w holds a non-finite value");
+  DFH_HIP(hipSetDevice(o->ctx->device));
+  hipStream_t s = o->ctx->stream;
+  // from the state dfh_bcd_build leaves: w = 0, pred = 0 (delta and delta w are untouched before the first step)
+  const size_t K = o->keys.size();
+  DFH_HIP(hipMemsetAsync(o->d_w, 0, std::max<size_t>(K, 1) * sizeof(float), s));
+  for (auto& cs : o->chunks)
+    for (auto& ch : cs) DFH_HIP(hipMemsetAsync(ch.b->d_pred, 0, ch.nrows * sizeof(float), s));
+  if (n_matched) *n_matched = 0;
+  if (n == 0 || K == 0) {
+    DFH_HIP(hipStreamSynchronize(s));
+    return DFH_OK;
+  }
+  join::Result j;
+  int rc = join::run(o->ctx, o->keys.data(), K, keys, n, n * sizeof(float), &j);
+  if (rc) return rc;
+  if (j.dups) {
+    (void)hipFree(j.mem);
+    set_error("dfh_bcd_set_model: the input keys are not unique");
+    return DFH_ERR_ARG;
+  }
+  rc = DFH_OK;
+  do {
+    if (!j.matched) break;
+    float* d_win = reinterpret_cast<float*>(j.extra);
+    if (hipMemcpyAsync(d_win, w, n * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) {
+      rc = DFH_ERR_HIP;
+      break;
+    }
+    hipLaunchKernelGGL(bcd::k_bcd_set_w, dim3(bcd::grid_of(n, bcd::THREADS)), dim3(bcd::THREADS), 0, s, j.pos, d_win, (uint64_t)n,
+                       o->d_w);
+    // the predictions: k_bcd_pred from pred = 0 with delta w := w, the blocks in ascending order
+    o->h_order.resize(o->nblk);
+    for (int b = 0; b < o->nblk; ++b) o->h_order[b] = b;
+    if (o->nblk && hipMemcpyAsync(o->d_order, o->h_order.data(), o->nblk * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess) {
+      rc = DFH_ERR_HIP;
+      break;
+    }
+    for (int b = 0; b < o->nblk; ++b) {
+      if (o->pend[b] == o->pbeg[b]) continue;   // a block without keys touches no row
+      for (auto& cs : o->chunks)
+        for (auto& ch : cs) {
+          if (!ch.max_rec) continue;
+          bcd::PredArgs p{o->d_order, b, ch.rec, ch.rec_row, ch.rec_lo, ch.r_key, ch.r_val, o->d_w, ch.b->d_pred};
+          hipLaunchKernelGGL(bcd::k_bcd_pred, dim3(bcd::grid_of(ch.max_rec, bcd::THREADS)), dim3(bcd::THREADS), 0, s, p);
+        }
+    }
+    if (hipGetLastError() != hipSuccess) rc = DFH_ERR_HIP;
+  } while (0);
+  if (hipStreamSynchronize(s) != hipSuccess) rc = DFH_ERR_HIP;
+  (void)hipFree(j.mem);
+  if (rc) {
+    set_error("dfh_bcd_set_model: setting the model on the device failed");
+    return rc;
+  }
+  if (n_matched) *n_matched = j.matched;
   return DFH_OK;
 }
 

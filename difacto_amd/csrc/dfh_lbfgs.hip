@@ -12,6 +12,10 @@
 //   CalcGrad                  lbfgs_learner.cc:246-305 per chunk: k_lb_gather -> forward -> backward -> k_lb_scatter
 //   InitWeight                lbfgs_updater.h:33-76    tail filter, lens, V from the rand_r(seed = 0) chain in key order
 //
+// Warm start (dfh_lbfgs_set_model; the reference declares model_in, lbfgs_param.h:58, and never reads it): the input keys
+// are joined onto the object's ascending keys on the device (dfh_join.hip); k_lb_set_model copies a matched key's w, and
+// its V where both sides carry one, into the ragged model.  Every other float keeps what InitWeight gave it.
+//
 // Every reduction is deterministic: per-thread fp64 sums, a fixed-order block reduction into one partial per block
 // (the grid depends on n only), then one ordered pass over the partials.  No float atomics.
 #include <cmath>
@@ -370,6 +374,25 @@ __global__ void __launch_bounds__(THREADS) k_lb_scatter(const float* __restrict_
   }
 }
 
+// warm start: input key u (model position jpos[u], -1 = not in the model) brings ilen = ipos[u + 1] - ipos[u] floats
+// (w [, V]); the model's entry holds mlen.  Both are 1 or 1 + V_dim: the first min(mlen, ilen) floats are copied, so V
+// only where both sides have one.  Input keys are unique: one writer per float.  Lanes as k_lb_gather's.
+__global__ void __launch_bounds__(THREADS) k_lb_set_model(const int32_t* __restrict__ jpos, const uint64_t* __restrict__ ipos,
+                                                          const float* __restrict__ vals, const int64_t* __restrict__ pos, RowLanes r,
+                                                          float* __restrict__ w) {
+  uint32_t u, c0, ustep;
+  row_lanes(r, &u, &c0, &ustep);
+  for (; u < r.U; u += ustep) {
+    const int32_t i = jpos[u];
+    if (i < 0) continue;
+    const int64_t p0 = pos[i], mlen = pos[i + 1] - p0;
+    const uint64_t q0 = ipos[u];
+    const int64_t ilen = (int64_t)(ipos[u + 1] - q0);
+    const int64_t len = mlen < ilen ? mlen : ilen;
+    for (int64_t c = c0; c < len; c += 1u << r.shift) w[p0 + c] = vals[q0 + c];
+  }
+}
+
 // CalcGrad's closing transform when gamma != 1 (lbfgs_learner.cc:300-302): pow of the float arguments evaluated in double
 // (C++'s pow on the float gamma and fabs), the signed result rounded to float on assignment
 __global__ void __launch_bounds__(THREADS) k_lb_gamma(float* __restrict__ g, uint64_t n, float gamma) {
@@ -510,6 +533,7 @@ struct dfh_lbfgs {
   std::vector<float*> s, y;        // m slots each
   int s_first = 0, s_count = 0, y_first = 0, y_count = 0;
   bool have_g = false;
+  bool grad_run = false;           // a gradient pass has run: the model can no longer be replaced by key
   float alpha = 0;                 // alpha_ of LBFGSUpdater / LBFGSLearner: the last line-search step taken
   float* d_rows = nullptr;         // [max_U x stride] packed rows / gradient rows of the current chunk
   float* d_grows = nullptr;
@@ -533,6 +557,7 @@ struct dfh_lbfgs {
   uint64_t nx = 0;
   std::vector<size_t> own_b, loc_b;   // bytes per peer: owner side (pull send = push receive), worker side (the reverse)
   bool pulled = false;             // d_lw holds the current w
+  std::vector<uint64_t> splits;    // [world - 1] first keys of shards 1..: the owner of a key is the number of them <= it
 };
 
 namespace {
@@ -631,6 +656,7 @@ int lb_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n) {
   auto& tr = o->chunks[0];
   hipStream_t s = o->ctx->stream;
   int rc = DFH_OK;
+  o->grad_run = true;
   if (o->comm) {
     rc = lb_pull(o);
     if (rc) return rc;
@@ -918,6 +944,7 @@ int lb_shard_model(dfh_lbfgs* o, float filter, int V_threshold, const std::vecto
   std::vector<uint64_t> splits(std::max(W - 1, 1), 0);
   int rc = dfh_shard_balanced_splits(o->comm, tk.data(), tk.size(), splits.data());
   if (rc) return rc;
+  o->splits.assign(splits.begin(), splits.begin() + (W - 1));
   // the owner of a key: the number of split keys at or below it
   std::vector<int> owner(req.size());
   std::vector<uint64_t> nreq(W, 0), nrecv(W, 0);
@@ -1226,6 +1253,101 @@ int dfh_lbfgs_set_weights(dfh_lbfgs* o, const float* w) {
   DFH_HIP(hipSetDevice(o->ctx->device));
   DFH_HIP(hipMemcpyAsync(o->d_w, w, o->n * sizeof(float), hipMemcpyHostToDevice, o->ctx->stream));
   DFH_HIP(hipStreamSynchronize(o->ctx->stream));
+  return DFH_OK;
+}
+
+int dfh_lbfgs_owned_range(dfh_lbfgs* o, uint64_t* key_lo, uint64_t* key_hi) {
+  DFH_ARG(o && o->inited, "dfh_lbfgs_owned_range: the model is not initialised");
+  uint64_t lo = 0, hi = 0;
+  if (o->comm) {
+    const int r = o->comm->rank, W = o->comm->world;
+    if (r > 0) lo = o->splits[r - 1];
+    if (r + 1 < W) hi = o->splits[r];
+  }
+  if (key_lo) *key_lo = lo;
+  if (key_hi) *key_hi = hi;
+  return DFH_OK;
+}
+
+int dfh_lbfgs_set_model(dfh_lbfgs* o, uint64_t n, const uint64_t* keys, const int* lens, const float* vals, uint64_t* n_matched) {
+  DFH_ARG(o && o->inited, "dfh_lbfgs_set_model: the model is not initialised");
+  DFH_ARG(n == 0 || (keys && lens && vals), "dfh_lbfgs_set_model: NULL argument");
+  if (o->grad_run || o->have_g) {
+    set_error("dfh_lbfgs_set_model: a gradient pass has run: the model is set before the first dfh_lbfgs_calc_grad");
+    return DFH_ERR_STATE;
+  }
+  DFH_HIP(hipSetDevice(o->ctx->device));
+  hipStream_t s = o->ctx->stream;
+  const int k = o->V_dim;
+  // on a sharded object a rank that refuses its input still meets the others in the one all-reduce
+  int rc = DFH_OK;
+  std::string why;
+  std::vector<uint64_t> ipos(n + 1, 0);
+  for (uint64_t i = 0; i < n && !rc; ++i) {
+    if (lens[i] != 1 && !(k > 0 && lens[i] == 1 + k)) {
+      rc = DFH_ERR_ARG;
+      why = "dfh_lbfgs_set_model: lens must be 1 or 1 + V_dim";
+    }
+    ipos[i + 1] = ipos[i] + (uint64_t)std::max(lens[i], 0);
+    if (!rc && o->comm) {
+      const int owner = (int)(std::upper_bound(o->splits.begin(), o->splits.end(), keys[i]) - o->splits.begin());
+      if (owner != o->comm->rank) {
+        rc = DFH_ERR_ARG;
+        why = "dfh_lbfgs_set_model: an entry outside this rank's key range (dfh_lbfgs_owned_range)";
+      }
+    }
+  }
+  if (!rc && n >= (uint64_t(1) << 31)) {
+    rc = DFH_ERR_ARG;
+    why = "dfh_lbfgs_set_model: fewer than 2^31 input keys";
+  }
+  uint64_t matched = 0;
+  const size_t K = o->keys.size();
+  if (!rc && n && K) {
+    join::Result j;
+    const size_t pos_b = ((n + 1) * sizeof(uint64_t) + 255) / 256 * 256;
+    rc = join::run(o->ctx, o->keys.data(), K, keys, n, pos_b + ipos[n] * sizeof(float), &j);
+    if (!rc && j.dups) {
+      rc = DFH_ERR_ARG;
+      why = "dfh_lbfgs_set_model: the input keys are not unique";
+    }
+    if (!rc && j.matched) {
+      uint64_t* d_ipos = reinterpret_cast<uint64_t*>(j.extra);
+      float* d_vals = reinterpret_cast<float*>(j.extra + pos_b);
+      const uint32_t st = (uint32_t)(1 + k);
+      uint32_t shift = 0;
+      while ((1u << shift) < st && shift < 6) ++shift;
+      const lb::RowLanes rl{(uint32_t)n, st, shift};
+      const uint64_t waves = (n + (64u >> shift) - 1) / (64u >> shift);
+      const int gb = (int)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, 8192));
+      if (hipMemcpyAsync(d_ipos, ipos.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+          hipMemcpyAsync(d_vals, vals, ipos[n] * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) {
+        rc = DFH_ERR_HIP;
+      } else {
+        hipLaunchKernelGGL(lb::k_lb_set_model, dim3(gb), dim3(lb::THREADS), 0, s, j.pos, d_ipos, d_vals, o->d_pos, rl, o->d_w);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = DFH_ERR_HIP;
+      }
+      if (rc) why = "dfh_lbfgs_set_model: setting the model on the device failed";
+      o->pulled = false;
+    }
+    if (j.mem) (void)hipFree(j.mem);
+    if (!rc) matched = j.matched;
+  }
+  if (o->comm) {   // the one exchange of this call: the matched count, and whether every rank accepted its entries
+    double t[2] = {(double)matched, rc ? 1.0 : 0.0};
+    const int rc2 = dfh_comm_allreduce_sum(o->comm, t, 2);
+    if (rc2 && !rc) return rc2;
+    if (!rc && t[1] > 0) {
+      rc = DFH_ERR_ARG;
+      why = "dfh_lbfgs_set_model: another rank refused its entries";
+    }
+    matched = (uint64_t)t[0];
+  }
+  if (rc) {
+    if (!why.empty()) set_error(why);
+    return rc;
+  }
+  if (n_matched) *n_matched = matched;
   return DFH_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <mutex>
 #include "./batch_reader.h"
 #include "./device_context.h"
+#include "./model_parts.h"
 
 namespace difacto {
 
@@ -130,6 +131,7 @@ void BCDLearner::RunScheduler() {
   uint64_t nkeys = 0;
   DFH_CALL(dfh_bcd_build(obj_, static_cast<float>(updater_param_.tail_feature_filter), static_cast<int>(ranges.size()), beg.data(),
                          end.data(), updater_param_.l1, updater_param_.lr, &nkeys));
+  if (param_.model_in.size()) LoadModel(nkeys);
 
   // iterate over data: the block order is std::random_shuffle on the process-wide rand() stream (bcd_learner.cc:79)
   std::vector<int> feablks(ranges.size());
@@ -148,6 +150,17 @@ void BCDLearner::RunScheduler() {
        << ", acc: " << progress[3] / cnt;
   }
   if (param_.model_out.size()) SaveModel();
+}
+
+// model_in: the file's w joined onto the model's keys on the device, the predictions of every chunk rebuilt from it
+// (dfh_bcd_set_model).  V in the file is ignored; keys the model does not hold (filtered, or not in this data) are dropped.
+void BCDLearner::LoadModel(uint64_t nkeys) {
+  ModelEntries m;
+  LoadModelEntries(param_.model_in, 0, 0, &m);
+  uint64_t matched = 0;
+  DFH_CALL(dfh_bcd_set_model(obj_, m.keys.size(), m.keys.data(), m.w.data(), &matched));
+  LOG(INFO) << "model loaded from " << param_.model_in << ": " << matched << " of " << m.keys.size() << " keys matched " << nkeys
+            << " model keys";
 }
 
 // the final w as learner = sgd's model file without optimiser state (dfh_table_save, save_aux = 0)

@@ -11,7 +11,11 @@
  *   - g and h are summed in fp64 (the reference adds floats in row order): the same objective to ~1e-6
  *   - model_out is written (the reference declares it and never writes it): the final w in the format of learner = sgd's
  *     model_out, without optimiser state, so that task = predict learner = sgd model_in = ... V_dim = 0 scores it
- *   - a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) and task = predict are refused with a message
+ *   - model_in is read (the reference declares it, bcd_param.h:44, and never reads it): a warm start from the w of a model
+ *     file of any learner (V and optimiser state in the file are ignored), e.g. the previous l1 of a regularisation
+ *     path; keys the feature map does not hold are dropped, delta starts at 1 as in a cold run
+ *   - a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is refused with a message; so is task = predict for a caller of
+ *     Learner::Create("bcd") (the command line scores a model through learner = sgd's prediction path itself)
  */
 #ifndef DIFACTO_HOST_BCD_LEARNER_H_
 #define DIFACTO_HOST_BCD_LEARNER_H_
@@ -79,6 +83,8 @@ class BCDLearner : public Learner {
  private:
   /*! \brief PrepareData (bcd_learner.cc:96-131): the chunks onto the device, the feature-group statistics */
   void PrepareData(std::vector<real_t>* fea_stats);
+  /*! \brief model_in: warm start from a model file (dfh_bcd_set_model), after the feature map is built */
+  void LoadModel(uint64_t nkeys);
   void SaveModel();
 
   BCDLearnerParam param_;

@@ -105,6 +105,7 @@ void LBFGSLearner::InitServer(std::vector<real_t>* rets) {
     updater_.weight_initializer()(lens, &w);
     DFH_CALL(dfh_lbfgs_set_weights(obj_, w.data()));
   }
+  if (param_.model_in.size()) LoadModel(nkeys);
   float nnz = 0, r = 0;
   DFH_CALL(dfh_lbfgs_evaluate(obj_, nullptr, &nnz, &r));
   double total = static_cast<double>(n);   // this rank's slice; the log shows the model's size
@@ -210,6 +211,34 @@ void LBFGSLearner::RunScheduler() {
   }
   LOG(INFO) << "Training is done";
   if (param_.model_out.size()) SaveModel();
+}
+
+// model_in: the file's entries of this rank's key range (the whole model in one process) joined onto the model's keys on
+// the device (dfh_lbfgs_set_model): w, and V where both the file and the model carry one
+void LBFGSLearner::LoadModel(uint64_t nkeys) {
+  const int k = param_.loss == "logit" ? 0 : updater_.param().V_dim;
+  uint64_t lo = 0, hi = 0;
+  DFH_CALL(dfh_lbfgs_owned_range(obj_, &lo, &hi));
+  ModelEntries m;
+  LoadModelEntries(param_.model_in, lo, hi, &m);
+  CHECK(k == 0 || m.V_dim == k) << "model_in " << param_.model_in << " has V_dim = " << m.V_dim << ", this job has V_dim = " << k;
+  const size_t n = m.keys.size();
+  std::vector<int> lens(n, 1);
+  std::vector<real_t> vals;
+  vals.reserve(n * (1 + static_cast<size_t>(k)));
+  for (size_t i = 0; i < n; ++i) {
+    vals.push_back(m.w[i]);
+    if (k && m.has_V[i]) {
+      lens[i] = 1 + k;
+      vals.insert(vals.end(), m.V.begin() + static_cast<size_t>(k) * i, m.V.begin() + static_cast<size_t>(k) * (i + 1));
+    }
+  }
+  uint64_t matched = 0;
+  DFH_CALL(dfh_lbfgs_set_model(obj_, n, m.keys.data(), lens.data(), vals.data(), &matched));   // collective; matched: over ranks
+  double tot[2] = {static_cast<double>(n), static_cast<double>(nkeys)};
+  if (comm_) DFH_CALL(dfh_comm_allreduce_sum(comm_, tot, 2));   // the log line shows the job's counts on every rank
+  LOG(INFO) << "model loaded from " << param_.model_in << ": " << matched << " of " << static_cast<uint64_t>(tot[0])
+            << " keys matched " << static_cast<uint64_t>(tot[1]) << " model keys";
 }
 
 // the final weights as learner = sgd's model file without optimiser state (dfh_table_save, save_aux = 0)

@@ -15,7 +15,12 @@
  *   - model_out is written (the reference declares it and never writes it): the final weights in the format of
  *     learner = sgd's model_out, without optimiser state, so that task = predict learner = sgd model_in = ... scores them
  *   - model_out of a sharded run is <model_out>.part-<rank> plus the <model_out>.parts manifest, as learner = sgd writes it
- *   - task = predict, and a multi-process environment that is not complete (see above), are refused with a message
+ *   - model_in is read (the reference declares it, lbfgs_param.h:58, and never reads it): a warm start from the w and V
+ *     of a model file of any learner (optimiser state in the file is ignored; with V_dim > 0 the file's V_dim must be
+ *     the job's), a file or the parts of a sharded save; a sharded rank reads its own key range.  The s / y history is
+ *     not restored and load_epoch keeps its meaning: the first epoch of the loop
+ *   - a multi-process environment that is not complete (see above) is refused with a message; so is task = predict for
+ *     a caller of Learner::Create("lbfgs") (the command line scores a model through learner = sgd's prediction path itself)
  */
 #ifndef DIFACTO_HOST_LBFGS_LEARNER_H_
 #define DIFACTO_HOST_LBFGS_LEARNER_H_
@@ -84,6 +89,8 @@ class LBFGSLearner : public Learner {
   /*! \brief the Wolfe line search from objective objv along p (<p, g> = pg), starting at step; returns the accepted
    * objective, *auc = AUC x n of the last gradient pass */
   real_t LineSearch(real_t step, real_t objv, float pg, float* auc);
+  /*! \brief model_in: warm start from a model file (dfh_lbfgs_set_model), after InitWeight and the weight initializer */
+  void LoadModel(uint64_t nkeys);
   void SaveModel();
 
   LBFGSLearnerParam param_;

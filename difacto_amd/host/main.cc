@@ -95,7 +95,26 @@ int main(int argc, char* argv[]) {
   } else if (param.task == "predict") {
     // the reference stops at a TODO here (main.cc:61-62); its SGDLearnerParam already names model_in as the model of
     // "a prediction task" (sgd_param.h:24-28).  The learner runs one forward pass over the data and writes pred_out.
-    Learner* learner = Learner::Create(param.learner);
+    // A prediction needs no training data and no learner state: a model_in of learner = lbfgs or bcd is scored by the SGD
+    // learner's prediction path with the same remaining arguments (for bcd: V_dim = 0, its models carry no V).  Without
+    // a model_in there is nothing to score: the learner's own Init refuses and says how a model is written and scored.
+    std::string type = param.learner;
+    bool has_model = false;
+    for (const auto& kw : kwargs_remain) has_model = has_model || (kw.first == "model_in" && kw.second.size());
+    if (has_model && (type == "lbfgs" || type == "bcd")) {
+      if (type == "bcd") {
+        bool given = false;
+        for (const auto& kw : kwargs_remain) {
+          if (kw.first != "V_dim") continue;
+          CHECK_EQ(atoi(kw.second.c_str()), 0) << "task = predict learner = bcd scores a linear model: V_dim = " << kw.second
+                                               << " is not 0";
+          given = true;
+        }
+        if (!given) kwargs_remain.push_back(std::make_pair("V_dim", "0"));
+      }
+      type = "sgd";
+    }
+    Learner* learner = Learner::Create(type);
     kwargs_remain.push_back(std::make_pair("task", "predict"));
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));
     learner->Run();

@@ -568,6 +568,22 @@ int dfh_lbfgs_shape(dfh_lbfgs* o, uint64_t* nkeys, uint64_t* nparams, int* ntrai
 int dfh_lbfgs_get_model(dfh_lbfgs* o, uint64_t* keys, int* lens, float* feacnt, float* w);
 /* SetWeightInitializer: replace w [nparams] before training starts */
 int dfh_lbfgs_set_weights(dfh_lbfgs* o, const float* w);
+/* [key_lo, key_hi) of the keys this rank owns on a dfh_lbfgs_create_sharded object (key_hi = 0: no upper bound; a plain
+ * object owns everything: 0, 0), known after dfh_lbfgs_init_model — the range to hand dfh_table_load */
+int dfh_lbfgs_owned_range(dfh_lbfgs* o, uint64_t* key_lo, uint64_t* key_hi);
+/* after dfh_lbfgs_init_model, before the first dfh_lbfgs_calc_grad: start from a model given by key.
+ * keys [n] unique, any order; lens [n] in {1, 1 + V_dim}; vals ragged [sum lens] = w then V, the layout of dfh_pull.
+ * The keys are matched against the object's ascending keys on the device (one lane per input key, a binary search; no
+ * host-side map).  A matched key takes the input's w, and the input's V only where BOTH the model's lens and the input's
+ * are 1 + V_dim; otherwise the model's V keeps its rand_r initial value (or the model has none).  An input key the model
+ * does not hold (filtered, or never seen in the training data) is dropped; a model key that is not in the input keeps
+ * what init_model gave it, bit for bit.  Given the whole model, the object equals one that took the same floats through
+ * dfh_lbfgs_set_weights.  *n_matched (may be NULL): input keys that are keys of the model.
+ * On a dfh_lbfgs_create_sharded object COLLECTIVE: every rank passes the entries of ITS OWN key range
+ * (dfh_lbfgs_owned_range; an entry outside it is an error) and *n_matched is the sum over ranks; nothing crosses the
+ * wire but one dfh_comm_allreduce_sum of that count (and of whether every rank accepted its entries: they fail together).
+ * Errors: DFH_ERR_STATE after a gradient pass; DFH_ERR_ARG for repeated keys, a bad lens or a foreign key. */
+int dfh_lbfgs_set_model(dfh_lbfgs* o, uint64_t n, const uint64_t* keys, const int* lens, const float* vals, uint64_t* n_matched);
 /* CalcGrad (lbfgs_learner.cc:246-305) into g_new: loss and AUC x n summed per chunk as the reference sums them */
 int dfh_lbfgs_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n);
 /* PrepareCalcDirection: *mcur = history pairs in use (0 at epoch 0: nothing is returned), incr_B [6 mcur + 1] */
@@ -606,6 +622,22 @@ int dfh_bcd_epoch(dfh_bcd* o, const int* order, int n, float* progress);
 /* one block, synchronised: g, h (NULL: not returned) = the block's summed gradient and diagonal Hessian [pos_end -
  * pos_begin] in fp64 before the update; progress as dfh_bcd_epoch (NULL: not computed) */
 int dfh_bcd_step(dfh_bcd* o, int blk, double* g, double* h, float* progress);
+/* after dfh_bcd_build, before the first dfh_bcd_epoch / dfh_bcd_step: start from a model.
+ * keys [n] (ReverseBytes keys as dfh_bcd_get_model returns them, unique, any order), w [n]: host arrays.
+ * *n_matched (may be NULL): input keys that are keys of the model.
+ * The keys are matched against the model's ascending keys on the device (one lane per input key, a binary search; no
+ * host-side map).  An input key that is not in the model (filtered by tail_feature_filter, or never seen in the training
+ * data) is dropped; a model key that is not in the input keeps w = 0; delta stays 1 and the last delta w stays 0, as
+ * dfh_bcd_build leaves them.  Every call starts from the built state, so n = 0 leaves the object as built.
+ * The predictions of EVERY training and validation chunk are rebuilt from the new w.  Definition, per row r:
+ *     pred[r] = 0; for each surviving entry of the row whose key lies in a block, in ascending model position (ascending
+ *     block, then ascending column inside the block): if (w != 0) pred[r] = pred[r] + w * x
+ * in float, without contraction, x = 1 in a chunk without values — exactly what the block steps' own prediction update
+ * computes from pred = 0 with delta w := w, block after block in ascending block order.  No float atomics: two calls
+ * give the same bits.
+ * Errors: DFH_ERR_STATE before dfh_bcd_build or after a step has run; DFH_ERR_ARG when the input keys are not unique
+ * or w holds a non-finite value. */
+int dfh_bcd_set_model(dfh_bcd* o, uint64_t n, const uint64_t* keys, const float* w, uint64_t* n_matched);
 /* the model (any pointer may be NULL): keys [nkeys], merged counts, w, delta, the last delta w */
 int dfh_bcd_get_model(dfh_bcd* o, uint64_t* keys, float* feacnt, float* w, float* delta, float* dw);
 /* the predictions of a chunk (pred NULL: only *nrows) */

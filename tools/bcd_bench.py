@@ -10,6 +10,8 @@ With --stats FILE (rocprofv3 --kernel-trace --stats output of this tool's run): 
 achieved TB/s (its bytes over k_bcd_grad + k_bcd_fixup time) against 5 TB/s.
 
   python tools/bcd_bench.py [--rows 4000000] [--chunk-rows 1000000] [--block-ratio 1] [--epochs 3] [--out FILE]
+  python tools/bcd_bench.py --set-model ...   also: ms of dfh_bcd_set_model (model_in's warm start) with a value for every
+                                              key of the model, keys shuffled, next to the epoch; the epochs still start cold
   rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/bcd_bench.py ...
   python tools/bcd_bench.py --stats DIR/.../run_kernel_stats.csv --model FILE
 """
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--block-ratio", type=float, default=1.0)
     ap.add_argument("--tail-feature-filter", type=int, default=4)
     ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--set-model", action="store_true")
     ap.add_argument("--out")
     ap.add_argument("--stats")
     ap.add_argument("--model")
@@ -97,6 +100,18 @@ def main():
     res["bytes_pred"] = tr_nnz * (4 + 4) + touched * (8 + 8)
     res["bytes_state"] = nkeys * (16 + 24)
     res["bytes_per_epoch"] = res["bytes_grad"] + res["bytes_pred"] + res["bytes_state"]
+    if args.set_model:   # before the first step: every key of the model, shuffled; then n = 0 puts the built state back
+        rng = np.random.default_rng(11)
+        keys = rng.permutation(obj.get_model()["keys"])
+        w = (rng.normal(size=len(keys)) * .01).astype(np.float32)
+        ts = []
+        for _ in range(3):
+            t = time.perf_counter()
+            matched = obj.set_model(keys, w)
+            ts.append(1e3 * (time.perf_counter() - t))
+        assert matched == nkeys
+        obj.set_model(keys[:0], w[:0])
+        res.update(set_model_keys=len(keys), set_model_ms=ts, set_model_ms_best=min(ts))
     stream = R.RefRand()
     order = list(range(len(ranges)))
     stream.shuffle(order)
