@@ -201,7 +201,8 @@ struct dfh_batch {
   uint32_t *d_urow = nullptr, *d_need = nullptr, *d_rank = nullptr, *d_total = nullptr;
   float *d_pred = nullptr, *d_slope = nullptr, *d_xv = nullptr;
   size_t xv_floats = 0;
-  double* d_prog = nullptr;
+  static constexpr size_t kProgDoubles = 2 * PROG_SLOTS + 64;   // [2][PROG_SLOTS] partials, then the AUC accumulator
+  double* d_prog = nullptr;        // [kProgDoubles]
   float nrows_seen = 0;
   // pipelining: prep-stream work -> ev_ready -> main-stream step -> ev_free -> next prep
   hipEvent_t ev_ready = nullptr, ev_free = nullptr;
@@ -231,6 +232,12 @@ struct dfh_batch {
   bool loc_big = false;
   int pend_stage = RID_STAGES;
 };
+
+namespace dfh {
+namespace chunks {
+inline hipError_t reset_prog(dfh_batch* b, hipStream_t s);   // dfh_chunks.hip: d_prog back to zero
+}
+}  // namespace dfh
 
 namespace {
 int flush_pending(dfh_batch* b);  // single-queue step: queue what is left of the batch's noted Localizer as plain launches
@@ -2278,7 +2285,7 @@ static int batch_create_impl(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_ba
   DFH_ALLOC(b->d_rank, N, uint32_t);
   DFH_ALLOC(b->d_pred, B, float);
   DFH_ALLOC(b->d_slope, B, float);
-  DFH_ALLOC(b->d_prog, 2 * PROG_SLOTS + 64, double);
+  DFH_ALLOC(b->d_prog, dfh_batch::kProgDoubles, double);
   DFH_ALLOC(b->d_auc_keys, B, uint32_t);
   DFH_ALLOC(b->d_auc_skeys, B, uint32_t);
   DFH_ALLOC(b->d_auc_lab, B, uint32_t);
@@ -2293,7 +2300,7 @@ static int batch_create_impl(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_ba
   // (a failure from here on gives the object — and its reference on a shared arena — back: ADVICE r5)
   hipError_t e2 = hipEventCreateWithFlags(&b->ev_ready, evf);
   if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&b->ev_free, evf);
-  if (e2 == hipSuccess) e2 = hipMemsetAsync(b->d_prog, 0, (2 * PROG_SLOTS + 64) * sizeof(double), c->stream);
+  if (e2 == hipSuccess) e2 = chunks::reset_prog(b, c->stream);
   if (e2 == hipSuccess) e2 = hipMemsetAsync(b->d_U, 0, 64 * sizeof(uint32_t), c->stream);
   // a key's ticket is back at zero when its last part has been applied (upd_split_role)
   if (e2 == hipSuccess) e2 = hipMemsetAsync(b->d_split_ticket, 0, b->split_cap * sizeof(uint32_t), c->stream);
@@ -3780,7 +3787,7 @@ int dfh_batch_progress(dfh_batch* b, dfh_progress* out, int reset) {
   out->nnz_w = 0;
   out->nrows = b->nrows_seen;
   if (reset) {
-    DFH_HIP(hipMemsetAsync(b->d_prog, 0, (2 * PROG_SLOTS + 64) * sizeof(double), s));
+    DFH_HIP(chunks::reset_prog(b, s));
     b->nrows_seen = 0;
   }
   return DFH_OK;
@@ -3841,5 +3848,6 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 
 #include "dfh_shard.hip"
 #include "dfh_join.hip"
+#include "dfh_chunks.hip"
 #include "dfh_lbfgs.hip"
 #include "dfh_bcd.hip"

@@ -393,11 +393,7 @@ inline int grid_of(uint64_t n, int per_block) { return (int)std::max<uint64_t>(1
 
 struct dfh_bcd {
   dfh_ctx* ctx = nullptr;
-  struct Chunk {
-    dfh_batch* b = nullptr;
-    size_t nrows = 0, nnz = 0, U = 0;
-    std::vector<uint64_t> keys;
-    std::vector<float> cnt;
+  struct Chunk : chunks::Resident {
     // device layout
     int* s_gk = nullptr;          // [nnz]
     uint2* nz = nullptr;          // [nblk]
@@ -433,22 +429,8 @@ struct dfh_bcd {
 
 namespace {
 
-std::string bcd_bytes_msg(const char* what, size_t need, size_t free_b) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), "dfh_bcd: %s needs %zu bytes of HBM, %zu are free (out-of-core BCD is not supported)", what, need,
-           free_b);
-  return buf;
-}
-
-int bcd_check_free(const char* what, size_t need) {
-  size_t free_b = 0, total_b = 0;
-  DFH_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (need > free_b) {
-    set_error(bcd_bytes_msg(what, need, free_b));
-    return DFH_ERR_CAPACITY;
-  }
-  return DFH_OK;
-}
+constexpr const char* kBcdWho = "dfh_bcd";
+constexpr const char* kBcdTail = "out-of-core BCD is not supported";
 
 // device bytes a chunk's layouts keep (m <= nnz entries, records <= nnz) and the transient build buffers
 inline size_t bcd_layout_bytes(size_t nnz, int nblk, bool val) {
@@ -510,7 +492,7 @@ int bcd_progress(dfh_bcd* o, float* prog) {
       int rc = launch_auc(ch.b);
       if (rc) return rc;
       DFH_HIP(hipMemcpyAsync(res + 2, ch.b->d_prog + PROG_AUC * PROG_SLOTS, sizeof(double), hipMemcpyDeviceToDevice, s));
-      DFH_HIP(hipMemsetAsync(ch.b->d_prog, 0, (2 * PROG_SLOTS + 64) * sizeof(double), s));
+      DFH_HIP(chunks::reset_prog(ch.b, s));
     }
   std::vector<double> r(4 * i);
   if (i) DFH_HIP(hipMemcpyAsync(r.data(), o->d_res, r.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -532,7 +514,7 @@ int bcd_progress(dfh_bcd* o, float* prog) {
 }
 
 void bcd_free_chunk(dfh_bcd::Chunk& ch) {
-  if (ch.b) dfh_batch_destroy(ch.b);
+  chunks::release(ch);
   for (void* p : {(void*)ch.s_gk, (void*)ch.nz, (void*)ch.r_key, (void*)ch.r_val, (void*)ch.rec, (void*)ch.rec_row, (void*)ch.rec_lo})
     if (p) (void)hipFree(p);
 }
@@ -577,7 +559,7 @@ int bcd_build_chunk(dfh_bcd* o, dfh_bcd::Chunk& ch, const std::vector<int>& gmap
   DFH_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, std::max<size_t>(m, 1),
                                   rocprim::plus<uint32_t>(), s));
   const size_t tmp = std::max(sort_tmp, scan_tmp);
-  int rc = bcd_check_free("the layouts of a data chunk", bcd_layout_bytes(nnz, nblk, ch.b->has_value) + bcd_build_bytes(nnz, tmp));
+  int rc = chunks::check_free(kBcdWho, "the layouts of a data chunk", kBcdTail, bcd_layout_bytes(nnz, nblk, ch.b->has_value) + bcd_build_bytes(nnz, tmp));
   if (rc) return rc;
   const bool val = ch.b->has_value;
   DFH_HIP(hipMalloc(&ch.s_gk, std::max<size_t>(nnz, 1) * sizeof(int)));
@@ -591,21 +573,16 @@ int bcd_build_chunk(dfh_bcd* o, dfh_bcd::Chunk& ch, const std::vector<int>& gmap
   const size_t n1 = std::max<size_t>(nnz, 1), u1 = std::max<size_t>(U, 1);
   const size_t tb = u1 * 8 + n1 * (8 + 8 + 4 + 4 + 4 + 4) + tmp + 8 * 256;
   DFH_HIP(hipMalloc(&t, tb));
-  char* p = t;
-  auto take = [&](size_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  int* d_gmap = reinterpret_cast<int*>(take(u1 * 4));
-  int* d_cblk = reinterpret_cast<int*>(take(u1 * 4));
-  uint64_t* k_in = reinterpret_cast<uint64_t*>(take(n1 * 8));
-  uint64_t* k_out = reinterpret_cast<uint64_t*>(take(n1 * 8));
-  uint32_t* v_in = reinterpret_cast<uint32_t*>(take(n1 * 4));
-  uint32_t* v_out = reinterpret_cast<uint32_t*>(take(n1 * 4));
-  uint32_t* head = reinterpret_cast<uint32_t*>(take(n1 * 4));
-  uint32_t* idx = reinterpret_cast<uint32_t*>(take(n1 * 4));
-  void* d_tmp = take(tmp);
+  Carver cv(t);   // nine pieces, each begun on 256 bytes: at most 8 x 255 bytes of padding
+  int* d_gmap = cv.take<int>(u1);
+  int* d_cblk = cv.take<int>(u1);
+  uint64_t* k_in = cv.take<uint64_t>(n1);
+  uint64_t* k_out = cv.take<uint64_t>(n1);
+  uint32_t* v_in = cv.take<uint32_t>(n1);
+  uint32_t* v_out = cv.take<uint32_t>(n1);
+  uint32_t* head = cv.take<uint32_t>(n1);
+  uint32_t* idx = cv.take<uint32_t>(n1);
+  void* d_tmp = cv.take<char>(tmp);
   rc = DFH_OK;
   do {
     if (U) {
@@ -660,7 +637,7 @@ int bcd_build_chunk(dfh_bcd* o, dfh_bcd::Chunk& ch, const std::vector<int>& gmap
     std::vector<uint32_t> rec(nblk + 1);
     if (hipMemcpyAsync(rec.data(), ch.rec, rec.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemsetAsync(ch.b->d_pred, 0, ch.nrows * sizeof(float), s) != hipSuccess ||
-        hipMemsetAsync(ch.b->d_prog, 0, (2 * PROG_SLOTS + 64) * sizeof(double), s) != hipSuccess ||
+        chunks::reset_prog(ch.b, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
       rc = DFH_ERR_HIP;
       break;
@@ -693,43 +670,11 @@ int dfh_bcd_add_chunk(dfh_bcd* o, int is_val, size_t nrows, const size_t* offset
   DFH_ARG(!o->built, "dfh_bcd_add_chunk: the layouts are already built");
   const size_t nnz = offset[nrows] - offset[0];
   DFH_ARG(nnz < (size_t(1) << 31) && nrows < (size_t(1) << 31), "dfh_bcd_add_chunk: a chunk holds fewer than 2^31 rows and entries");
-  DFH_HIP(hipSetDevice(o->ctx->device));
-  size_t need = 0;
-  int rc = batch_create_impl(o->ctx, nrows, std::max<size_t>(nnz, 1), nullptr, nullptr, 0, &need, false);
-  if (rc) return rc;
-  rc = bcd_check_free("a data chunk", need + bcd_layout_bytes(nnz, 0, value != nullptr));
-  if (rc) return rc;
   dfh_bcd::Chunk ch;
-  ch.nrows = nrows;
-  ch.nnz = nnz;
-  rc = dfh_batch_create(o->ctx, nrows, std::max<size_t>(nnz, 1), &ch.b);
+  // + the layouts dfh_bcd_build adds to the chunk
+  const int rc = chunks::add(o->ctx, kBcdWho, kBcdTail, bcd_layout_bytes(nnz, 0, value != nullptr), nrows, offset, index, value,
+                             label, &ch);
   if (rc) return rc;
-  rc = dfh_batch_load_host(ch.b, nrows, offset, index, value, label);
-  if (!rc) rc = dfh_localize(ch.b, ~0ULL);   // Localizer(-1): TileBuilder::Add, src/data/tile_builder.h:139-147
-  size_t U = 0;
-  if (!rc) rc = dfh_batch_get_localized(ch.b, &U, nullptr, nullptr, nullptr);
-  if (!rc) {
-    ch.U = U;
-    ch.keys.resize(U);
-    ch.cnt.resize(U);
-    if (U) rc = dfh_batch_get_localized(ch.b, &U, ch.keys.data(), ch.cnt.data(), nullptr);
-  }
-  // the chunk is never loaded again: its page-locked staging copy goes back to the host
-  if (!rc && ch.b->h_stage) {
-    if (ch.b->staged_pending) {
-      if (hipEventSynchronize(ch.b->ev_staged) != hipSuccess) rc = DFH_ERR_HIP;
-      ch.b->staged_pending = false;
-    }
-    if (!rc && hipHostFree(ch.b->h_stage) != hipSuccess) rc = DFH_ERR_HIP;
-    ch.b->h_stage = nullptr;
-    ch.b->stage_bytes = 0;
-    ch.b->d_stage_view = nullptr;
-    if (rc) set_error("dfh_bcd_add_chunk: releasing the staging buffer failed");
-  }
-  if (rc) {
-    dfh_batch_destroy(ch.b);
-    return rc;
-  }
   o->chunks[is_val ? 1 : 0].push_back(std::move(ch));
   return DFH_OK;
 }
@@ -751,25 +696,16 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
   // merged feature counts (KVUnion in chunk order, tile_builder.h:171-176), keys with count > filter kept
   // (BuildFeatureMap, bcd_learner.cc:127-146)
   {
-    size_t tot = 0;
-    for (auto& ch : o->chunks[0]) tot += ch.U;
-    std::vector<std::pair<uint64_t, float>> kc;
-    kc.reserve(tot);
-    for (auto& ch : o->chunks[0])
-      for (size_t u = 0; u < ch.U; ++u) kc.emplace_back(ch.keys[u], ch.cnt[u]);
-    std::stable_sort(kc.begin(), kc.end(), [](const std::pair<uint64_t, float>& a, const std::pair<uint64_t, float>& b) {
-      return a.first < b.first;
-    });
-    for (size_t i = 0; i < kc.size();) {
-      size_t j = i;
-      float cnt = 0;
-      for (; j < kc.size() && kc[j].first == kc[i].first; ++j) cnt += kc[j].second;
-      if (cnt > tail_feature_filter) {
-        o->keys.push_back(kc[i].first);
-        o->cnts.push_back(cnt);
+    std::vector<const chunks::Resident*> train(o->chunks[0].size());
+    for (size_t i = 0; i < train.size(); ++i) train[i] = &o->chunks[0][i];
+    std::vector<uint64_t> tk;
+    std::vector<float> tc;
+    chunks::merged_counts(train, &tk, &tc);
+    for (size_t i = 0; i < tk.size(); ++i)
+      if (tc[i] > tail_feature_filter) {
+        o->keys.push_back(tk[i]);
+        o->cnts.push_back(tc[i]);
       }
-      i = j;
-    }
   }
   const size_t K = o->keys.size();
   DFH_ARG(K < (size_t(1) << 31), "dfh_bcd_build: more than 2^31 - 1 keys");
@@ -788,7 +724,7 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
   for (auto& ch : o->chunks[0]) max_shares = std::max<size_t>(max_shares, (ch.nnz + bcd::SHARE - 1) / bcd::SHARE + bcd::WAVES);
   o->res_cap = 4 * (o->chunks[0].size() + o->chunks[1].size());
   const size_t state = K1 * 12 + mk * 16 + max_shares * 40 + B1 * 12 + bcd::PROG_BLOCKS * 16 + o->res_cap * 8 + 4096;
-  int rc = bcd_check_free("the model and the block state", state);
+  int rc = chunks::check_free(kBcdWho, "the model and the block state", kBcdTail, state);
   if (rc) return rc;
   DFH_HIP(hipMalloc(&o->d_pbeg, B1 * sizeof(int)));
   DFH_HIP(hipMalloc(&o->d_pend, B1 * sizeof(int)));
@@ -825,13 +761,11 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
   // every chunk: colmap (TileBuilder::BuildColmap, tile_builder.h:62-76: -1 = filtered) and each key's block, then the layouts
   for (auto& cs : o->chunks)
     for (auto& ch : cs) {
-      std::vector<int> gmap(std::max<size_t>(ch.U, 1), -1), cblk(std::max<size_t>(ch.U, 1), -1);
-      size_t j = 0;
+      std::vector<int> gmap, cblk(std::max<size_t>(ch.U, 1), -1);
+      chunks::colmap(ch, o->keys, &gmap);
       int b = 0;
       for (size_t u = 0; u < ch.U; ++u) {
         const uint64_t key = ch.keys[u];
-        while (j < K && o->keys[j] < key) ++j;
-        if (j < K && o->keys[j] == key) gmap[u] = (int)j;
         while (b < nblk && blk_end[b] <= key) ++b;
         if (gmap[u] >= 0 && b < nblk && blk_begin[b] <= key) cblk[u] = b;
       }

@@ -63,19 +63,14 @@ inline int run(dfh_ctx* c, const uint64_t* mkeys, size_t K, const uint64_t* keys
     return DFH_ERR_CAPACITY;
   }
   DFH_HIP(hipMalloc(reinterpret_cast<void**>(&out->mem), bytes));
-  char* p = out->mem;
-  auto take = [&](size_t b) {
-    char* r = p;
-    p += pad(b);
-    return r;
-  };
-  uint64_t* d_mkeys = reinterpret_cast<uint64_t*>(take(K * 8));
-  uint64_t* d_in = reinterpret_cast<uint64_t*>(take(n * 8));
-  uint64_t* d_sorted = reinterpret_cast<uint64_t*>(take(n * 8));
-  out->pos = reinterpret_cast<int32_t*>(take(n * 4));
-  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(take(16));
-  void* d_tmp = take(sort_tmp);
-  out->extra = take(extra_bytes);
+  Carver cv(out->mem);   // an empty piece still gets 256 bytes of its own, as bytes counts it (pad)
+  uint64_t* d_mkeys = cv.take<uint64_t>(std::max<size_t>(K, 1));
+  uint64_t* d_in = cv.take<uint64_t>(n);
+  uint64_t* d_sorted = cv.take<uint64_t>(n);
+  out->pos = cv.take<int32_t>(n);
+  unsigned long long* d_cnt = cv.take<unsigned long long>(2);
+  void* d_tmp = cv.take<char>(std::max<size_t>(sort_tmp, 1));
+  out->extra = cv.take<char>(extra_bytes);
   unsigned long long h_cnt[2] = {0, 0};
   const int grid = (int)((n + THREADS - 1) / THREADS);
   int rc = DFH_OK;

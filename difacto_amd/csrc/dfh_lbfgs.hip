@@ -510,11 +510,7 @@ struct dfh_lbfgs {
   dfh_ctx* ctx = nullptr;
   int V_dim = 0, m = 0;
   size_t stride = 4;
-  struct Chunk {
-    dfh_batch* b = nullptr;
-    size_t nrows = 0, U = 0;
-    std::vector<uint64_t> keys;
-    std::vector<float> cnt;
+  struct Chunk : chunks::Resident {
     int32_t* d_map = nullptr;
   };
   std::vector<Chunk> chunks[2];   // [0] training, [1] validation
@@ -577,12 +573,8 @@ int lb_fetch(dfh_lbfgs* o, const double* d, size_t cnt, std::vector<double>* out
   return DFH_OK;
 }
 
-std::string lb_bytes_msg(const char* what, size_t need, size_t free_b) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), "dfh_lbfgs: %s needs %zu bytes of HBM, %zu are free (out-of-core L-BFGS is not supported)", what, need,
-           free_b);
-  return buf;
-}
+constexpr const char* kLbWho = "dfh_lbfgs";
+constexpr const char* kLbTail = "out-of-core L-BFGS is not supported";
 
 // forward (+ AUC) over a chunk's rows, its loss / AUC into res[0..1]; with grad, the backward and the scatter into g
 int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
@@ -607,7 +599,7 @@ int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
   }
   hipLaunchKernelGGL(lb::k_lb_take_prog, dim3(1), dim3(lb::THREADS), 0, s, ch.b->d_prog, res);
   DFH_HIP(hipGetLastError());
-  DFH_HIP(hipMemsetAsync(ch.b->d_prog, 0, (2 * PROG_SLOTS + 64) * sizeof(double), s));
+  DFH_HIP(chunks::reset_prog(ch.b, s));
   ch.b->nrows_seen = 0;
   return DFH_OK;
 }
@@ -714,7 +706,7 @@ int lb_free(dfh_lbfgs* o) {
   if (o->ctx) (void)hipSetDevice(o->ctx->device);
   for (auto& cs : o->chunks)
     for (auto& ch : cs) {
-      if (ch.b) dfh_batch_destroy(ch.b);
+      chunks::release(ch);
       if (ch.d_map) (void)hipFree(ch.d_map);
     }
   if (o->arena) (void)hipFree(o->arena);
@@ -835,49 +827,12 @@ int dfh_lbfgs_add_chunk(dfh_lbfgs* o, int is_val, size_t nrows, const size_t* of
   DFH_ARG(o && offset && label && nrows >= 1, "dfh_lbfgs_add_chunk: bad argument");
   DFH_ARG(!o->inited, "dfh_lbfgs_add_chunk: the model is already initialised");
   const size_t nnz = offset[nrows] - offset[0];
-  DFH_HIP(hipSetDevice(o->ctx->device));
-  size_t need = 0;
-  int rc = batch_create_impl(o->ctx, nrows, std::max<size_t>(nnz, 1), nullptr, nullptr, 0, &need, false);
-  if (rc) return rc;
   // + the key map and the X V buffer the first forward allocates (ensure_xv)
-  need += (nnz + 1) * sizeof(int32_t) + nrows * (size_t)std::max((o->V_dim + 3) / 4 * 4, 4) * sizeof(float);
-  size_t free_b = 0, total_b = 0;
-  DFH_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (need > free_b) {
-    set_error(lb_bytes_msg("a data chunk", need, free_b));
-    return DFH_ERR_CAPACITY;
-  }
+  const size_t extra = (nnz + 1) * sizeof(int32_t) + nrows * (size_t)std::max((o->V_dim + 3) / 4 * 4, 4) * sizeof(float);
   dfh_lbfgs::Chunk ch;
-  ch.nrows = nrows;
-  rc = dfh_batch_create(o->ctx, nrows, std::max<size_t>(nnz, 1), &ch.b);
+  const int rc = chunks::add(o->ctx, kLbWho, kLbTail, extra, nrows, offset, index, value, label, &ch);
   if (rc) return rc;
-  rc = dfh_batch_load_host(ch.b, nrows, offset, index, value, label);
-  if (!rc) rc = dfh_localize(ch.b, ~0ULL);  // Localizer(-1): TileBuilder::Add, src/data/tile_builder.h:139-147
-  size_t U = 0;
-  if (!rc) rc = dfh_batch_get_localized(ch.b, &U, nullptr, nullptr, nullptr);
-  if (!rc) {
-    ch.U = U;
-    ch.keys.resize(U);
-    ch.cnt.resize(U);
-    if (U) rc = dfh_batch_get_localized(ch.b, &U, ch.keys.data(), ch.cnt.data(), nullptr);
-  }
-  // the chunk is never loaded again: its page-locked staging copy of the rows (12 B per nnz) goes back to the host
-  if (!rc && ch.b->h_stage) {
-    if (ch.b->staged_pending) {
-      if (hipEventSynchronize(ch.b->ev_staged) != hipSuccess) rc = DFH_ERR_HIP;
-      ch.b->staged_pending = false;
-    }
-    if (!rc && hipHostFree(ch.b->h_stage) != hipSuccess) rc = DFH_ERR_HIP;
-    ch.b->h_stage = nullptr;
-    ch.b->stage_bytes = 0;
-    ch.b->d_stage_view = nullptr;
-    if (rc) set_error("dfh_lbfgs_add_chunk: releasing the staging buffer failed");
-  }
-  if (rc) {
-    dfh_batch_destroy(ch.b);
-    return rc;
-  }
-  o->max_U = std::max(o->max_U, U);
+  o->max_U = std::max(o->max_U, ch.U);
   o->chunks[is_val ? 1 : 0].push_back(std::move(ch));
   return DFH_OK;
 }
@@ -1047,23 +1002,9 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   std::vector<uint64_t> tk;
   std::vector<float> tc;
   {
-    size_t tot = 0;
-    for (auto& ch : o->chunks[0]) tot += ch.U;
-    std::vector<std::pair<uint64_t, float>> kc;
-    kc.reserve(tot);
-    for (auto& ch : o->chunks[0])
-      for (size_t u = 0; u < ch.U; ++u) kc.emplace_back(ch.keys[u], ch.cnt[u]);
-    std::stable_sort(kc.begin(), kc.end(), [](const std::pair<uint64_t, float>& a, const std::pair<uint64_t, float>& b) {
-      return a.first < b.first;
-    });
-    for (size_t i = 0; i < kc.size();) {
-      size_t j = i;
-      float cnt = 0;
-      for (; j < kc.size() && kc[j].first == kc[i].first; ++j) cnt += kc[j].second;
-      tk.push_back(kc[i].first);
-      tc.push_back(cnt);
-      i = j;
-    }
+    std::vector<const chunks::Resident*> train(o->chunks[0].size());
+    for (size_t i = 0; i < train.size(); ++i) train[i] = &o->chunks[0][i];
+    chunks::merged_counts(train, &tk, &tc);
   }
   std::vector<uint64_t> lkeys;   // sharded: the worker's local model
   std::vector<int> llens;
@@ -1101,7 +1042,7 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
     for (int q = 0; q < o->comm->rank; ++q) skip += draws[q];
   }
   // every model-sized vector in one allocation: w, g_new, g, m s slots, m y slots (each padded to 64 floats), pos, V mask
-  const size_t vec = ((n + 63) / 64) * 64 * sizeof(float);
+  const size_t vecf = ((n + 63) / 64) * 64, vec = vecf * sizeof(float);
   const size_t mask_words = k ? (n + 31) / 32 + 1 : 0;
   const size_t arena = (size_t)(3 + 2 * o->m) * vec + ((K + 1) * sizeof(int64_t) + 255) / 256 * 256 + mask_words * 4 + 256;
   const size_t rows = std::max<size_t>(o->max_U, 1) * o->stride * sizeof(float);
@@ -1114,11 +1055,9 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   const size_t sh_arena = o->comm ? 2 * pad(nl * sizeof(float)) + pad((lkeys.size() + 1) * sizeof(int64_t)) +
                                         3 * pad(nx * sizeof(uint32_t)) + pad((n + 1) * sizeof(uint32_t))
                                   : 0;
-  size_t free_b = 0, total_b = 0;
-  DFH_HIP(hipMemGetInfo(&free_b, &total_b));
-  if (arena + 2 * rows + part + sh_arena > free_b) {
-    set_error(lb_bytes_msg("the model and the optimiser state", arena + 2 * rows + part + sh_arena, free_b));
-    return DFH_ERR_CAPACITY;
+  {
+    const int rc = chunks::check_free(kLbWho, "the model and the optimiser state", kLbTail, arena + 2 * rows + part + sh_arena);
+    if (rc) return rc;
   }
   DFH_HIP(hipMalloc(&o->arena, arena));
   DFH_HIP(hipMalloc(&o->d_rows, rows));
@@ -1126,21 +1065,16 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   DFH_HIP(hipMalloc(&o->d_part, part));
   o->res_cap = 2 * std::max(o->chunks[0].size(), o->chunks[1].size()) + kTail;
   DFH_HIP(hipMalloc(&o->d_res, o->res_cap * sizeof(double)));
-  char* p = static_cast<char*>(o->arena);
-  auto take = [&](size_t bytes) {
-    char* r = p;
-    p += (bytes + 255) / 256 * 256;
-    return r;
-  };
-  o->d_w = reinterpret_cast<float*>(take(vec));
-  o->d_gnew = reinterpret_cast<float*>(take(vec));
-  o->d_g = reinterpret_cast<float*>(take(vec));
+  Carver cv(o->arena);
+  o->d_w = cv.take<float>(vecf);
+  o->d_gnew = cv.take<float>(vecf);
+  o->d_g = cv.take<float>(vecf);
   o->s.resize(o->m);
   o->y.resize(o->m);
-  for (int i = 0; i < o->m; ++i) o->s[i] = reinterpret_cast<float*>(take(vec));
-  for (int i = 0; i < o->m; ++i) o->y[i] = reinterpret_cast<float*>(take(vec));
-  o->d_pos = reinterpret_cast<int64_t*>(take((K + 1) * sizeof(int64_t)));
-  o->d_vmask = k ? reinterpret_cast<uint32_t*>(take(mask_words * 4)) : nullptr;
+  for (int i = 0; i < o->m; ++i) o->s[i] = cv.take<float>(vecf);
+  for (int i = 0; i < o->m; ++i) o->y[i] = cv.take<float>(vecf);
+  o->d_pos = cv.take<int64_t>(K + 1);
+  o->d_vmask = k ? cv.take<uint32_t>(mask_words) : nullptr;
   // w = 0, V from the rand_r(seed = 0) chain in key order (InitWeight, lbfgs_updater.h:58-69)
   std::vector<float> w(n, 0.f);
   std::vector<uint32_t> mask(mask_words, 0u);
@@ -1168,19 +1102,16 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   std::vector<uint32_t> rptr, ridx;
   if (o->comm) {
     DFH_HIP(hipMalloc(&o->sh_arena, sh_arena));
-    p = static_cast<char*>(o->sh_arena);
-    auto take_p = [&](size_t bytes) {
-      char* r = p;
-      p += pad(bytes);
-      return r;
-    };
-    o->d_lw = reinterpret_cast<float*>(take_p(nl * sizeof(float)));
-    o->d_lg = reinterpret_cast<float*>(take_p(nl * sizeof(float)));
-    o->d_lpos = reinterpret_cast<int64_t*>(take_p((lkeys.size() + 1) * sizeof(int64_t)));
-    o->d_xbuf = reinterpret_cast<float*>(take_p(nx * sizeof(float)));
-    o->d_src = reinterpret_cast<uint32_t*>(take_p(nx * sizeof(uint32_t)));
-    o->d_ridx = reinterpret_cast<uint32_t*>(take_p(nx * sizeof(uint32_t)));
-    o->d_rptr = reinterpret_cast<uint32_t*>(take_p((n + 1) * sizeof(uint32_t)));
+    // an empty vector still gets a piece of its own, as sh_arena counts it (pad)
+    const uint64_t nl1 = std::max<uint64_t>(nl, 1), nx1 = std::max<uint64_t>(nx, 1);
+    Carver cs(o->sh_arena);
+    o->d_lw = cs.take<float>(nl1);
+    o->d_lg = cs.take<float>(nl1);
+    o->d_lpos = cs.take<int64_t>(lkeys.size() + 1);
+    o->d_xbuf = cs.take<float>(nx1);
+    o->d_src = cs.take<uint32_t>(nx1);
+    o->d_ridx = cs.take<uint32_t>(nx1);
+    o->d_rptr = cs.take<uint32_t>(n + 1);
     o->nx = nx;
     lpos.assign(lkeys.size() + 1, 0);
     for (size_t i = 0; i < lkeys.size(); ++i) lpos[i + 1] = lpos[i] + llens[i];
@@ -1203,15 +1134,10 @@ int dfh_lbfgs_init_model(dfh_lbfgs* o, float tail_feature_filter, int V_threshol
   // each chunk's key -> model key map (TileBuilder::BuildColmap, tile_builder.h:59-76: -1 = not in the model); on a
   // sharded object into the local model
   const std::vector<uint64_t>& mkeys = o->comm ? lkeys : o->keys;
-  const size_t MK = mkeys.size();
   for (auto& cs : o->chunks)
     for (auto& ch : cs) {
-      std::vector<int32_t> map(std::max<size_t>(ch.U, 1), -1);
-      size_t j = 0;
-      for (size_t u = 0; u < ch.U; ++u) {
-        while (j < MK && mkeys[j] < ch.keys[u]) ++j;
-        if (j < MK && mkeys[j] == ch.keys[u]) map[u] = (int32_t)j;
-      }
+      std::vector<int32_t> map;
+      chunks::colmap(ch, mkeys, &map);
       DFH_HIP(hipMalloc(&ch.d_map, map.size() * sizeof(int32_t)));
       DFH_HIP(hipMemcpyAsync(ch.d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
       DFH_HIP(hipStreamSynchronize(s));

@@ -10,6 +10,7 @@
 #include "./batch_reader.h"
 #include "./device_context.h"
 #include "./model_parts.h"
+#include "./resident_data.h"
 
 namespace difacto {
 
@@ -83,23 +84,16 @@ void BCDLearner::PrepareData(std::vector<real_t>* fea_stats) {
   // Reader blocks of data_chunk_size bytes (bcd_learner.cc:98-108); a block beyond the batch object's 32-bit positions is
   // cut by rows
   const size_t chunk_bytes = std::max<size_t>(64, static_cast<size_t>(param_.data_chunk_size));
-  const size_t kMaxNnz = size_t(1) << 31;
   bcd::FeaGroupStats stats(param_.num_feature_group_bits);
   auto read = [&](const std::string& uri, int is_val) {
     Reader reader(uri, param_.data_format, 0, 1, chunk_bytes);
-    while (reader.Next()) {
-      const auto& blk = reader.Value();
-      for (size_t r0 = 0; r0 < blk.size;) {
-        size_t r1 = r0 + 1;
-        while (r1 < blk.size && blk.offset[r1 + 1] - blk.offset[r0] <= kMaxNnz) ++r1;
-        if (!is_val) {
-          stats.Add(r1 - r0, blk.offset + r0, blk.index);   // bcd_learner.cc:107
-          chunk_rows_.push_back(r1 - r0);
-        }
-        DFH_CALL(dfh_bcd_add_chunk(obj_, is_val, r1 - r0, blk.offset + r0, blk.index, blk.value, blk.label + r0));
-        r0 = r1;
+    ForEachChunk(&reader, kMaxChunkNnz, [&](size_t r0, size_t r1, const dmlc::RowBlock<feaid_t>& blk) {
+      if (!is_val) {
+        stats.Add(r1 - r0, blk.offset + r0, blk.index);   // bcd_learner.cc:107
+        chunk_rows_.push_back(r1 - r0);
       }
-    }
+      DFH_CALL(dfh_bcd_add_chunk(obj_, is_val, r1 - r0, blk.offset + r0, blk.index, blk.value, blk.label + r0));
+    });
   };
   read(param_.data_in, 0);
   stats.Get(fea_stats);
@@ -176,14 +170,7 @@ void BCDLearner::SaveModel() {
     scal[4 * i] = cnt[i];   // {fea_cnt, w, sqrt_g, z}
     scal[4 * i + 1] = w[i];
   }
-  dfh_updater_param up;
-  dfh_updater_param_default(&up, 0);
-  dfh_table* t = nullptr;
-  DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
-  DFH_CALL(dfh_table_import(t, nkeys, keys.data(), scal.data(), has.data(), nullptr));
-  uint64_t saved = 0;
-  DFH_CALL(dfh_table_save(t, param_.model_out.c_str(), 0, &saved));
-  DFH_CALL(dfh_table_destroy(t));
+  SaveDenseModel(param_.model_out, 0, nkeys, keys.data(), scal.data(), has.data(), nullptr);
   LOG(INFO) << "model saved to " << param_.model_out;
 }
 

@@ -5,6 +5,7 @@
  *   Localizer.Base / BaseHash       tests/cpp/localizer_test.cc:12-49
  *   SGDLearner.Basic                tests/cpp/sgd_learner_test.cc:9-49  (fused and literal worker loops)
  *   BatchReader.Read / RandRead / PartRead   tests/cpp/batch_reader_test.cc:9-57
+ *   ForEachChunk                    resident_data.h: a reader block cut by rows at a bound on its entries
  *   LBFGSLearner.Basic / WithV      tests/cpp/lbfgs_learner_test.cc:8-146 (objective trajectories of an
  *                                   L-BFGS loop over Loss::Predict / CalcGrad / Evaluate — lbfgs_mini.h)
  * plus Store Pull/Push and Updater Save/Load round trips.  Needs a GPU, except the reader cases.
@@ -18,6 +19,7 @@
 #include "./host_localizer.h"
 #include "./lbfgs_mini.h"
 #include "./libsvm_reader.h"
+#include "./resident_data.h"
 #include "./sgd_learner.h"
 #include "dmlc/memory_io.h"
 
@@ -134,6 +136,44 @@ static void TestBatchReader() {
   int ttl = 0;
   while (part.Next()) ttl += static_cast<int>(part.Value().size);
   EXPECT(ttl >= 40 && ttl <= 60);
+}
+
+// ForEachChunk on hand-made blocks and a bound of 10 entries: the cuts of the loop both PrepareData's held
+// (r1 = r0 + 1; while (r1 < size && offset[r1 + 1] - offset[r0] <= bound) ++r1)
+struct FakeBlock {
+  size_t size;
+  const size_t* offset;
+};
+struct FakeReader {
+  std::vector<FakeBlock> blocks;
+  size_t at = 0;
+  bool Next() { return at++ < blocks.size(); }
+  const FakeBlock& Value() const { return blocks[at - 1]; }
+};
+
+static void TestForEachChunk() {
+  // rows of 4, 4, 4, 0, 12, 3, 7, 1 entries, offsets from 3: 4 + 4 fits and the third 4 does not; the empty row joins the
+  // chunk before it; the row of 12 is beyond the bound on its own and is passed on alone; 3 + 7 is the bound exactly
+  const size_t a[] = {3, 7, 11, 15, 15, 27, 30, 37, 38};
+  const size_t b[] = {0, 5};    // a block of one row
+  const size_t c[] = {9};       // a block without rows
+  const size_t d[] = {0, 10, 20, 21};   // every row at the bound
+  FakeReader reader;
+  reader.blocks = {{8, a}, {1, b}, {0, c}, {3, d}};
+  std::vector<std::vector<size_t>> got;
+  ForEachChunk(&reader, 10, [&](size_t r0, size_t r1, const FakeBlock& blk) {
+    got.push_back({static_cast<size_t>(blk.offset == a ? 0 : blk.offset == b ? 1 : blk.offset == d ? 3 : 2), r0, r1});
+  });
+  const std::vector<std::vector<size_t>> want = {{0, 0, 2}, {0, 2, 4}, {0, 4, 5}, {0, 5, 7}, {0, 7, 8}, {1, 0, 1},
+                                                 {3, 0, 1}, {3, 1, 2}, {3, 2, 3}};
+  EXPECT(got == want);
+  // the bound production passes: nothing is cut
+  reader.at = 0;
+  got.clear();
+  ForEachChunk(&reader, kMaxChunkNnz, [&](size_t r0, size_t r1, const FakeBlock&) { got.push_back({r0, r1}); });
+  const std::vector<std::vector<size_t>> whole = {{0, 8}, {0, 1}, {0, 3}};
+  EXPECT(got == whole);
+  EXPECT(kMaxChunkNnz == size_t(1) << 31);
 }
 
 static void TestFMLossNoV() {
@@ -315,12 +355,16 @@ int main(int argc, char** argv) {
     printf("[%s] %s\n", g_fail ? "FAILED" : "  OK  ", "RefRand = glibc rand() / std::random_shuffle");
     TestBatchReader();
     printf("[%s] %s\n", g_fail ? "FAILED" : "  OK  ", "BatchReader.Read+RandRead+PartRead");
+    const int before = g_fail;
+    TestForEachChunk();
+    printf("[%s] %s\n", g_fail == before ? "  OK  " : "FAILED", "ForEachChunk cuts a block at the entry bound");
     printf("%s\n", g_fail ? "SOME TESTS FAILED" : "ALL HOST TESTS PASSED");
     return g_fail ? 1 : 0;
   }
   struct { const char* name; std::function<void()> fn; } tests[] = {
       {"RefRand = glibc rand() / std::random_shuffle", TestRefRand},
       {"BatchReader.Read+RandRead+PartRead", TestBatchReader},
+      {"ForEachChunk cuts a block at the entry bound", TestForEachChunk},
       {"Localizer.Base+BaseHash", TestLocalizer},
       {"FMLoss.NoV", TestFMLossNoV},
       {"FMLoss.HasV", TestFMLossHasV},

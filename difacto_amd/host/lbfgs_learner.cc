@@ -11,6 +11,7 @@
 #include "./comm_setup.h"
 #include "./device_context.h"
 #include "./model_parts.h"
+#include "./resident_data.h"
 
 namespace difacto {
 
@@ -60,23 +61,16 @@ void LBFGSLearner::PrepareData(std::vector<real_t>* rets) {
   // Reader blocks of data_chunk_size MB (lbfgs_learner.cc:167-171); a block beyond the batch object's 32-bit positions
   // is cut by rows
   const size_t chunk_bytes = std::max<size_t>(64, static_cast<size_t>(param_.data_chunk_size * 1024 * 1024));
-  const size_t kMaxNnz = size_t(1) << 31;
   double cnt[6] = {0, 0, 0, 0, 0, 0};
   auto read = [&](const std::string& uri, int is_val, double* out) {
     Reader reader(uri, param_.data_format, rank_, world_, chunk_bytes);   // part rank_ of world_
     size_t nrows = 0, nnz = 0, nchunks = 0;
-    while (reader.Next()) {
-      const auto& blk = reader.Value();
-      for (size_t r0 = 0; r0 < blk.size;) {
-        size_t r1 = r0 + 1;
-        while (r1 < blk.size && blk.offset[r1 + 1] - blk.offset[r0] <= kMaxNnz) ++r1;
-        DFH_CALL(dfh_lbfgs_add_chunk(obj_, is_val, r1 - r0, blk.offset + r0, blk.index, blk.value, blk.label + r0));
-        ++nchunks;
-        r0 = r1;
-      }
-      nrows += blk.size;
-      nnz += blk.offset[blk.size] - blk.offset[0];
-    }
+    ForEachChunk(&reader, kMaxChunkNnz, [&](size_t r0, size_t r1, const dmlc::RowBlock<feaid_t>& blk) {
+      DFH_CALL(dfh_lbfgs_add_chunk(obj_, is_val, r1 - r0, blk.offset + r0, blk.index, blk.value, blk.label + r0));
+      ++nchunks;
+      nrows += r1 - r0;
+      nnz += blk.offset[r1] - blk.offset[r0];
+    });
     out[0] = nrows;
     out[1] = nchunks;
     out[2] = nnz;
@@ -260,16 +254,9 @@ void LBFGSLearner::SaveModel() {
     for (int j = 1; j < lens[i]; ++j) V[2 * k * i + j - 1] = w[p + j];
     p += lens[i];
   }
-  dfh_updater_param up;
-  dfh_updater_param_default(&up, k);
   // a sharded run: this rank's key range into <model_out>.part-<rank>, committed with the manifest (model_parts.h)
   SaveModelParts(comm_, rank_, world_, param_.model_out, [&](const std::string& tmp) {
-    dfh_table* t = nullptr;
-    DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
-    if (nkeys) DFH_CALL(dfh_table_import(t, nkeys, keys.data(), scal.data(), has.data(), V.data()));
-    uint64_t saved = 0;
-    DFH_CALL(dfh_table_save(t, tmp.c_str(), 0, &saved));
-    DFH_CALL(dfh_table_destroy(t));
+    SaveDenseModel(tmp, k, nkeys, keys.data(), scal.data(), has.data(), V.data());
   });
 }
 

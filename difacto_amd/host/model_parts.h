@@ -7,7 +7,7 @@
  *
  * LoadModelEntries is the way back for learner = lbfgs and learner = bcd (model_in): the entries of a key range out of
  * the file, or out of the parts its manifest names, through a scratch dfh_table (dfh_table_load + dfh_table_export) —
- * SaveModel of those learners goes the other way through the same calls.
+ * SaveDenseModel, the end of both learners' SaveModel, goes the other way through the same calls.
  */
 #ifndef DIFACTO_HOST_MODEL_PARTS_H_
 #define DIFACTO_HOST_MODEL_PARTS_H_
@@ -145,6 +145,20 @@ inline void LoadModelEntries(const std::string& model_in, uint64_t key_lo, uint6
     if (out->has_V[i])
       for (int j = 0; j < k; ++j) out->V[static_cast<size_t>(k) * i + j] = V2[static_cast<size_t>(2) * k * i + j];
   }
+}
+
+/*! \brief SaveModel of those learners: nkeys entries as learner = sgd's model file without optimiser state, through a
+ * scratch table.  scal [nkeys x 4] {fea_cnt, w, sqrt_g, z}, has [nkeys], V [nkeys x 2 V_dim] (NULL with V_dim = 0) */
+inline void SaveDenseModel(const std::string& path, int V_dim, uint64_t nkeys, const uint64_t* keys, const float* scal,
+                           const int* has, const float* V) {
+  dfh_updater_param up;
+  dfh_updater_param_default(&up, V_dim);
+  dfh_table* t = nullptr;
+  DFH_CALL(dfh_table_create(DeviceContext::Get(), &up, std::max<uint64_t>(nkeys + nkeys / 2 + 1024, 1024), &t));
+  if (nkeys) DFH_CALL(dfh_table_import(t, nkeys, keys, scal, has, V));
+  uint64_t saved = 0;
+  DFH_CALL(dfh_table_save(t, path.c_str(), 0, &saved));
+  DFH_CALL(dfh_table_destroy(t));
 }
 
 }  // namespace difacto

@@ -77,16 +77,19 @@ def main():
     obj = capi.Bcd(ctx)
     gen = CriteoSynth(total_ids=args.ids, seed=7)
     t0 = time.perf_counter()
-    nnz, sampled, entries = 0, 0, 0
+    nnz, sampled, entries, add_s = 0, 0, 0, 0.0
     for r0 in range(0, args.rows, args.chunk_rows):
         b = gen.batch(min(args.chunk_rows, args.rows - r0))
         n = len(b["label"])
+        t1 = time.perf_counter()
         obj.add_chunk(b["offset"], b["index"], None, b["label"])
+        add_s += time.perf_counter() - t1
         nnz += len(b["index"])
         s = len(range(0, n, 10))   # FeaGroupStats: every 10th row of a chunk, 39 entries each
         sampled += s
         entries += 39 * s
     res["load_s"] = time.perf_counter() - t0
+    res["add_chunks_s"] = add_s   # dfh_*_add_chunk alone; load_s also generates the rows
     st = np.array([entries, sampled, args.rows], np.float32)
     ranges = R.partition_feature(0, R.block_counts(st, args.block_ratio))
     t0 = time.perf_counter()

@@ -174,13 +174,18 @@ def main():
     obj = capi.Lbfgs(ctx, args.V_dim, args.m)
     gen = CriteoSynth(total_ids=args.ids, seed=7)
     t0 = time.perf_counter()
-    nnz = 0
+    nnz, add_s = 0, 0.0
     for r0 in range(0, args.rows, args.chunk_rows):
         b = gen.batch(min(args.chunk_rows, args.rows - r0))
+        t1 = time.perf_counter()
         obj.add_chunk(b["offset"], b["index"], None, b["label"])
+        add_s += time.perf_counter() - t1
         nnz += len(b["index"])
     res["load_s"] = time.perf_counter() - t0
+    res["add_chunks_s"] = add_s   # dfh_*_add_chunk alone; load_s also generates the rows
+    t0 = time.perf_counter()
     nkeys, n = obj.init_model(tail_feature_filter=4, V_threshold=args.V_threshold, V_init_scale=0.01, l2=100, V_l2=10)
+    res["init_s"] = time.perf_counter() - t0
     res.update(nkeys=nkeys, nparams=n, nnz=nnz)
     res["grad_eval_s"] = timed(lambda: obj.calc_grad(), args.reps)
     loss, _ = obj.calc_grad()
