@@ -156,6 +156,7 @@ def lib():
     L.dfh_rowbuf_create.argtypes = [vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.dfh_rowbuf_destroy.argtypes = [vp]
     L.dfh_rowbuf_load_host.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    L.dfh_rowbuf_load_host_slices.argtypes = [vp, C.c_size_t, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
     L.dfh_rowbuf_set_labels.argtypes = [vp, C.c_size_t, vp]
@@ -533,6 +534,17 @@ class RowBuf:
         index = np.ascontiguousarray(index, np.uint64)
         value = None if value is None else np.ascontiguousarray(value, np.float32)
         _ck(lib().dfh_rowbuf_load_host(self.h, len(offset) - 1, _p(offset), _p(index), _p(value)))
+
+    def load_host_slices(self, offset, slices):
+        """dfh_rowbuf_load_host_slices: the ids / values as consecutive pieces [(index, value or None), ...]"""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        idx = [np.ascontiguousarray(i, np.uint64) for i, _ in slices]
+        val = [None if v is None else np.ascontiguousarray(v, np.float32) for _, v in slices]
+        n = len(slices)
+        ip = (C.c_void_p * n)(*[i.ctypes.data for i in idx])
+        vp = (C.c_void_p * n)(*[None if v is None else v.ctypes.data for v in val])
+        cnt = (C.c_size_t * n)(*[len(i) for i in idx])
+        _ck(lib().dfh_rowbuf_load_host_slices(self.h, len(offset) - 1, _p(offset), n, ip, vp, cnt))
 
     def set_labels(self, label):
         """dfh_rowbuf_set_labels: the labels of the loaded rows (a buffer that stays: Batch.prepare_cached)"""

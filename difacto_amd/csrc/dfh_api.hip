@@ -155,7 +155,8 @@ struct dfh_batch {
   uint32_t* o_offset = nullptr;
   float* o_value = nullptr;
   float* o_label = nullptr;
-  // pinned staging of dfh_batch_load_host (one block: offsets | labels | ids | values), allocated on first use
+  // pinned staging of dfh_batch_load_host and of the device feed (one block, laid out by `stage`), allocated on first use
+  StageLayout stage;
   char* h_stage = nullptr;
   size_t stage_bytes = 0;          // allocated size of h_stage (ensure_stage: the row-description paths need ~160 KB, load_host the whole batch)
   hipEvent_t ev_staged = nullptr;  // the copies out of h_stage (or the kernels that read it in place) have completed
@@ -2248,6 +2249,7 @@ static int batch_create_impl(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_ba
   DFH_ALLOC(b->d_uid, N, uint32_t);
   DFH_ALLOC(b->d_temp, b->temp_bytes, char);
   b->max_tiles = (N + LOC_TILE - 1) / LOC_TILE;
+  b->stage = StageLayout(max_rows, max_nnz, b->max_tiles);
   DFH_ALLOC(b->d_spl_key, LOC_BIG_BUCKETS, uint64_t);
   DFH_ALLOC(b->d_spl_pos, LOC_BIG_BUCKETS, uint32_t);
   DFH_ALLOC(b->d_smp_key, LOC_BIG_BUCKETS * LOC_OVERSAMPLE, uint64_t);
@@ -2383,23 +2385,11 @@ int dfh_batch_destroy(dfh_batch* b) {
   return DFH_OK;
 }
 
-// page-locked staging of a batch object, sized for what the calling path puts there: a minibatch DESCRIBED by row numbers
-// needs offsets + labels + row numbers (~160 KB), dfh_batch_load_host the ids and values too (9 MB at C3's sizes — 2.4 ms
-// of hipHostMalloc each, which the worker loop's twelve batch objects paid on their first minibatch before round 4)
-static int ensure_stage(dfh_batch* b, size_t need) {
-  if (b->h_stage && b->stage_bytes >= need) return DFH_OK;
-  if (b->h_stage) {
-    if (b->staged_pending) DFH_HIP(hipEventSynchronize(b->ev_staged));
-    b->staged_pending = false;
-    DFH_HIP(hipHostFree(b->h_stage));
-    b->h_stage = nullptr;
-    b->d_stage_view = nullptr;
-  }
-  DFH_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->h_stage), need, hipHostMallocDefault));
-  b->stage_bytes = need;
-  if (!b->ev_staged) DFH_HIP(hipEventCreateWithFlags(&b->ev_staged, hipEventDisableTiming));
-  return DFH_OK;
-}
+}  // extern "C"
+
+#include "dfh_feed.hip"   // the device feed, and the staging helpers the load calls below share with it
+
+extern "C" {
 
 int dfh_batch_load_host(dfh_batch* b, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,
                         const float* label) {
@@ -2412,40 +2402,28 @@ int dfh_batch_load_host(dfh_batch* b, size_t nrows, const size_t* offset, const 
   DFH_ARG(nnz <= b->max_nnz, "dfh_batch_load_host: nnz exceeds max_nnz");
   DFH_ARG(nnz == 0 || index, "index is NULL");
   DFH_HIP(hipSetDevice(b->ctx->device));
-  phase_begin(b);
-  rc = prep_begin(b);
+  rc = phase_own_arrays(b);
   if (rc) return rc;
   hipStream_t s = prep_of(b);
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
   // Pinned staging: the caller's (pageable) arrays are copied into page-locked memory owned by the
   // batch object and sent with asynchronous copies on the preparation stream — the call returns as
   // soon as the bytes are staged, the caller may reuse its arrays, and with two batch objects used
   // alternately the transfer of minibatch t+1 overlaps the training of minibatch t.
-  const size_t o_off = 0, o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255),
-               o_val = o_idx + b->max_nnz * 8, total = o_val + b->max_nnz * 4;
-  rc = ensure_stage(b, total);
+  const StageLayout& L = b->stage;
+  rc = ensure_stage(b, L.load_host_bytes, false);
+  if (!rc) rc = stage_wait(b);
   if (rc) return rc;
-  if (b->staged_pending) {  // the previous minibatch staged here has long left; this wait is a formality
-    // (a query first: hipEventSynchronize costs ~100 us of host time even on an event that completed long ago)
-    if (hipEventQuery(b->ev_staged) != hipSuccess) DFH_HIP(hipEventSynchronize(b->ev_staged));
-    b->staged_pending = false;
-  }
-  memcpy(b->h_stage + o_off, off32.data(), (nrows + 1) * 4);
-  memcpy(b->h_stage + o_lab, label, nrows * 4);
-  if (nnz) memcpy(b->h_stage + o_idx, index + base, nnz * 8);
-  if (nnz && value) memcpy(b->h_stage + o_val, value + base, nnz * 4);
-  DFH_HIP(hipMemcpyAsync(b->d_offset, b->h_stage + o_off, (nrows + 1) * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipMemcpyAsync(b->d_label, b->h_stage + o_lab, nrows * 4, hipMemcpyHostToDevice, s));
-  if (nnz) DFH_HIP(hipMemcpyAsync(b->d_raw, b->h_stage + o_idx, nnz * 8, hipMemcpyHostToDevice, s));
-  if (nnz && value) DFH_HIP(hipMemcpyAsync(b->d_value, b->h_stage + o_val, nnz * 4, hipMemcpyHostToDevice, s));
+  memcpy(b->h_stage + L.o_off, off32.data(), (nrows + 1) * 4);
+  memcpy(b->h_stage + L.o_lab, label, nrows * 4);
+  if (nnz) memcpy(b->h_stage + L.o_idx, index + base, nnz * 8);
+  if (nnz && value) memcpy(b->h_stage + L.o_val, value + base, nnz * 4);
+  DFH_HIP(hipMemcpyAsync(b->d_offset, b->h_stage + L.o_off, (nrows + 1) * 4, hipMemcpyHostToDevice, s));
+  DFH_HIP(hipMemcpyAsync(b->d_label, b->h_stage + L.o_lab, nrows * 4, hipMemcpyHostToDevice, s));
+  if (nnz) DFH_HIP(hipMemcpyAsync(b->d_raw, b->h_stage + L.o_idx, nnz * 8, hipMemcpyHostToDevice, s));
+  if (nnz && value) DFH_HIP(hipMemcpyAsync(b->d_value, b->h_stage + L.o_val, nnz * 4, hipMemcpyHostToDevice, s));
   DFH_HIP(hipEventRecord(b->ev_staged, s));
   b->staged_pending = true;
-  b->nrows = nrows;
-  b->nnz = nnz;
-  b->has_value = value != nullptr;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
+  batch_loaded(b, nrows, nnz, value != nullptr);
   return DFH_OK;
 }
 
@@ -2453,23 +2431,14 @@ int dfh_batch_load_device(dfh_batch* b, size_t nrows, size_t nnz, const uint32_t
                           const float* d_value, const float* d_label) {
   DFH_ARG(b && d_offset && d_label && (nnz == 0 || d_index), "dfh_batch_load_device: NULL argument");
   DFH_ARG(nrows >= 1 && nrows <= b->max_rows && nnz <= b->max_nnz, "dfh_batch_load_device: shape out of range");
-  phase_begin(b);
-  {
-    int rc = prep_begin(b);
-    if (rc) return rc;
-  }
+  int rc = phase_own_arrays(b);
+  if (rc) return rc;
   hipStream_t s = prep_of(b);
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
   DFH_HIP(hipMemcpyAsync(b->d_offset, d_offset, (nrows + 1) * 4, hipMemcpyDeviceToDevice, s));
   if (nnz) DFH_HIP(hipMemcpyAsync(b->d_raw, d_index, nnz * 8, hipMemcpyDeviceToDevice, s));
   if (nnz && d_value) DFH_HIP(hipMemcpyAsync(b->d_value, d_value, nnz * 4, hipMemcpyDeviceToDevice, s));
   DFH_HIP(hipMemcpyAsync(b->d_label, d_label, nrows * 4, hipMemcpyDeviceToDevice, s));
-  b->nrows = nrows;
-  b->nnz = nnz;
-  b->has_value = d_value != nullptr;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
+  batch_loaded(b, nrows, nnz, d_value != nullptr);
   return DFH_OK;
 }
 
@@ -2486,399 +2455,9 @@ int dfh_batch_attach_device(dfh_batch* b, size_t nrows, size_t nnz, const uint32
   b->d_raw = const_cast<uint64_t*>(d_index);
   b->d_value = d_value ? const_cast<float*>(d_value) : b->o_value;
   b->d_label = const_cast<float*>(d_label);
-  b->nrows = nrows;
-  b->nnz = nnz;
-  b->has_value = d_value != nullptr;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
+  batch_loaded(b, nrows, nnz, d_value != nullptr);
   return DFH_OK;
 }
-
-
-// ---------------------------------------------------------------------------------------
-// Device feed: the shuffle buffer of BatchReader (src/reader/batch_reader.cc:38-52) lives in HBM; a minibatch is gathered
-// out of it by row number on the device (the host sends 4 B per row instead of copying ~300 B per row twice).
-// ---------------------------------------------------------------------------------------
-struct dfh_rowbuf {
-  dfh_ctx* ctx = nullptr;
-  size_t max_rows = 0, max_nnz = 0, nrows = 0, nnz = 0;
-  uint32_t* d_off = nullptr;   // [max_rows + 1]
-  uint64_t* d_idx = nullptr;   // [max_nnz]
-  float* d_val = nullptr;      // [max_nnz]
-  float* d_lab = nullptr;      // [max_rows] the rows' labels (dfh_rowbuf_set_labels: allocated by the first call)
-  bool has_value = false, has_labels = false;
-  hipStream_t up = nullptr;    // uploads: the feed thread's own stream
-  hipEvent_t ev_loaded = nullptr;
-  // one "gathered" event per stream that has gathered out of this buffer (the two batch objects of a worker loop gather on
-  // different preparation streams: one shared event would only remember the LAST gather); `pending` marks the ones
-  // recorded since the last upload.  Set by the thread that gathers, read by the thread that uploads.
-  struct Used { hipStream_t stream; hipEvent_t ev; bool pending; };
-  std::mutex mu;
-  std::vector<Used> used;
-  std::vector<hipStream_t> seen_loaded;  // streams ordered behind the current upload already (one wait per stream and upload)
-  double t_prof[3] = {0, 0, 0};          // DFH_PROFILE_PREP: host seconds of dfh_rowbuf_load_host (offsets, queue, wait)
-  uint64_t n_prof = 0, bytes_prof = 0;
-  std::vector<uint32_t> off32;
-};
-
-namespace {
-// one wave per row of the minibatch: row rows[q] of the buffer -> positions dst_off[q] .. of the minibatch's arrays
-__global__ void __launch_bounds__(256) k_gather_rows(const uint32_t* __restrict__ src_off, const uint64_t* __restrict__ src_idx,
-                                                     const float* __restrict__ src_val, const uint32_t* __restrict__ rows, uint32_t n,
-                                                     const uint32_t* __restrict__ dst_off, uint64_t* __restrict__ dst_idx,
-                                                     float* __restrict__ dst_val) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; q < n; q += nw) {
-    const uint32_t r = rows[q];
-    const uint32_t lo = src_off[r], len = src_off[r + 1] - lo, d0 = dst_off[q];
-    for (uint32_t j = lane; j < len; j += 64u) {
-      dst_idx[d0 + j] = src_idx[lo + j];
-      if (dst_val) dst_val[d0 + j] = src_val ? src_val[lo + j] : 1.0f;   // a buffer without values holds ones
-    }
-  }
-}
-}  // namespace
-
-int dfh_rowbuf_create(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_rowbuf** out) {
-  DFH_ARG(c && out && max_rows >= 1 && max_nnz >= 1, "dfh_rowbuf_create: bad argument");
-  DFH_ARG(max_nnz < 0xFFFFFFF0ULL && max_rows < 0xFFFFFFF0ULL, "dfh_rowbuf_create: a row buffer holds fewer than 2^32 rows / nonzeros");
-  DFH_HIP(hipSetDevice(c->device));
-  dfh_rowbuf* rb = new (std::nothrow) dfh_rowbuf();
-  if (!rb) {
-    set_error("dfh_rowbuf_create: out of host memory");
-    return DFH_ERR_HIP;
-  }
-  rb->ctx = c;
-  rb->max_rows = max_rows;
-  rb->max_nnz = max_nnz;
-  hipError_t e;
-  if ((e = hipMalloc(reinterpret_cast<void**>(&rb->d_off), (max_rows + 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&rb->d_idx), max_nnz * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipMalloc(reinterpret_cast<void**>(&rb->d_val), max_nnz * sizeof(float))) != hipSuccess ||
-      (e = hipStreamCreateWithFlags(&rb->up, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&rb->ev_loaded, hipEventDisableTiming)) != hipSuccess) {
-    set_error(std::string("dfh_rowbuf_create: ") + hipGetErrorString(e));
-    dfh_rowbuf_destroy(rb);
-    return DFH_ERR_HIP;
-  }
-  *out = rb;
-  return DFH_OK;
-}
-
-int dfh_rowbuf_destroy(dfh_rowbuf* rb) {
-  if (!rb) return DFH_OK;
-  if (rb->n_prof)
-    fprintf(stderr, "dfh_rowbuf_load_host x %llu (%.1f MB): offsets %.4f s, queue copies %.4f, wait %.4f\n", (unsigned long long)rb->n_prof,
-            rb->bytes_prof / 1e6, rb->t_prof[0], rb->t_prof[1], rb->t_prof[2]);
-  hipSetDevice(rb->ctx->device);
-  // the gathers out of this buffer, wherever they were queued (NOT sync_all: this may run beside the thread that drives
-  // the context, and only this buffer's own consumers matter)
-  for (auto& u : rb->used) {
-    if (u.pending) hipEventSynchronize(u.ev);
-    hipEventDestroy(u.ev);
-  }
-  if (rb->up) {
-    hipStreamSynchronize(rb->up);
-    hipStreamDestroy(rb->up);
-  }
-  if (rb->ev_loaded) hipEventDestroy(rb->ev_loaded);
-  for (void* p : {(void*)rb->d_off, (void*)rb->d_idx, (void*)rb->d_val, (void*)rb->d_lab})
-    if (p) hipFree(p);
-  delete rb;
-  return DFH_OK;
-}
-
-int dfh_rowbuf_load_host(dfh_rowbuf* rb, size_t nrows, const size_t* offset, const uint64_t* index, const float* value) {
-  DFH_ARG(rb && offset && nrows >= 1 && nrows <= rb->max_rows, "dfh_rowbuf_load_host: bad argument / more rows than the buffer holds");
-  const size_t base = offset[0], nnz = offset[nrows] - base;
-  DFH_ARG(nnz <= rb->max_nnz, "dfh_rowbuf_load_host: more nonzeros than the buffer holds");
-  DFH_ARG(nnz == 0 || index, "dfh_rowbuf_load_host: index is NULL");
-  DFH_HIP(hipSetDevice(rb->ctx->device));
-  {
-    // every gather out of the previous contents, on whichever stream it was queued, precedes the copies below
-    std::lock_guard<std::mutex> lk(rb->mu);
-    for (auto& u : rb->used) {
-      if (!u.pending) continue;
-      DFH_HIP(hipStreamWaitEvent(rb->up, u.ev, 0));
-      u.pending = false;
-    }
-    rb->seen_loaded.clear();
-  }
-  static const bool prof = getenv("DFH_PROFILE_PREP") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tp = prof ? now() : 0;
-  rb->off32.resize(nrows + 1);
-  for (size_t i = 0; i <= nrows; ++i) {
-    DFH_ARG(offset[i] >= base && (i == 0 || offset[i] >= offset[i - 1]), "dfh_rowbuf_load_host: offsets must not decrease");
-    rb->off32[i] = (uint32_t)(offset[i] - base);
-  }
-  if (prof) { const double x = now(); rb->t_prof[0] += x - tp; tp = x; }
-  DFH_HIP(hipMemcpyAsync(rb->d_off, rb->off32.data(), (nrows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, rb->up));
-  if (nnz) DFH_HIP(hipMemcpyAsync(rb->d_idx, index + base, nnz * sizeof(uint64_t), hipMemcpyHostToDevice, rb->up));
-  if (nnz && value) DFH_HIP(hipMemcpyAsync(rb->d_val, value + base, nnz * sizeof(float), hipMemcpyHostToDevice, rb->up));
-  DFH_HIP(hipEventRecord(rb->ev_loaded, rb->up));
-  if (prof) { const double x = now(); rb->t_prof[1] += x - tp; tp = x; }
-  DFH_HIP(hipStreamSynchronize(rb->up));   // the caller's arrays are free again
-  if (prof) { rb->t_prof[2] += now() - tp; ++rb->n_prof; rb->bytes_prof += nnz * (value ? 12 : 8) + nrows * 4; }
-  rb->nrows = nrows;
-  rb->nnz = nnz;
-  rb->has_value = value != nullptr;
-  rb->has_labels = false;   // (they were the previous contents')
-  return DFH_OK;
-}
-
-namespace {
-__global__ void k_fill_f32(float* __restrict__ p, size_t n, float v) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-}  // namespace
-
-// dfh_rowbuf_load_host for a buffer that was never assembled on the host: `offset` [nrows + 1] are the buffer's own
-// (cumulative) offsets, the ids / values arrive as `nslices` pieces that follow one another (slice g: nnz[g] ids at
-// index[g], values at value[g] or NULL = all ones).  One copy per piece, straight out of the caller's arrays.
-int dfh_rowbuf_load_host_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const uint64_t* const* index,
-                                const float* const* value, const size_t* nnz_of) {
-  DFH_ARG(rb && offset && nrows >= 1 && nrows <= rb->max_rows, "dfh_rowbuf_load_host_slices: bad argument / more rows than the buffer holds");
-  DFH_ARG(nslices >= 0 && (nslices == 0 || (index && value && nnz_of)), "dfh_rowbuf_load_host_slices: NULL slice arrays");
-  const size_t base = offset[0], nnz = offset[nrows] - base;
-  DFH_ARG(nnz <= rb->max_nnz, "dfh_rowbuf_load_host_slices: more nonzeros than the buffer holds");
-  size_t total = 0;
-  bool any_value = false;
-  for (int g = 0; g < nslices; ++g) {
-    DFH_ARG(nnz_of[g] == 0 || index[g], "dfh_rowbuf_load_host_slices: a slice without ids");
-    total += nnz_of[g];
-    any_value = any_value || (nnz_of[g] && value[g]);
-  }
-  DFH_ARG(total == nnz, "dfh_rowbuf_load_host_slices: the slices must hold the buffer's nonzeros");
-  DFH_HIP(hipSetDevice(rb->ctx->device));
-  {
-    std::lock_guard<std::mutex> lk(rb->mu);
-    for (auto& u : rb->used) {
-      if (!u.pending) continue;
-      DFH_HIP(hipStreamWaitEvent(rb->up, u.ev, 0));
-      u.pending = false;
-    }
-    rb->seen_loaded.clear();
-  }
-  static const bool prof = getenv("DFH_PROFILE_PREP") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tp = prof ? now() : 0;
-  rb->off32.resize(nrows + 1);
-  for (size_t i = 0; i <= nrows; ++i) {
-    DFH_ARG(offset[i] >= base && (i == 0 || offset[i] >= offset[i - 1]), "dfh_rowbuf_load_host_slices: offsets must not decrease");
-    rb->off32[i] = (uint32_t)(offset[i] - base);
-  }
-  if (prof) { const double x = now(); rb->t_prof[0] += x - tp; tp = x; }
-  DFH_HIP(hipMemcpyAsync(rb->d_off, rb->off32.data(), (nrows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, rb->up));
-  size_t at = 0;
-  for (int g = 0; g < nslices; ++g) {
-    const size_t n = nnz_of[g];
-    if (!n) continue;
-    DFH_HIP(hipMemcpyAsync(rb->d_idx + at, index[g], n * sizeof(uint64_t), hipMemcpyHostToDevice, rb->up));
-    if (any_value) {
-      if (value[g]) {
-        DFH_HIP(hipMemcpyAsync(rb->d_val + at, value[g], n * sizeof(float), hipMemcpyHostToDevice, rb->up));
-      } else {  // a block without a value array beside blocks with one: ones (compressed_row_block.h:36-44)
-        hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, rb->up, rb->d_val + at, n, 1.0f);
-      }
-    }
-    at += n;
-  }
-  DFH_HIP(hipGetLastError());
-  DFH_HIP(hipEventRecord(rb->ev_loaded, rb->up));
-  if (prof) { const double x = now(); rb->t_prof[1] += x - tp; tp = x; }
-  DFH_HIP(hipStreamSynchronize(rb->up));   // the caller's arrays are free again
-  if (prof) { rb->t_prof[2] += now() - tp; ++rb->n_prof; rb->bytes_prof += nnz * (any_value ? 12 : 8) + nrows * 4; }
-  rb->nrows = nrows;
-  rb->nnz = nnz;
-  rb->has_value = any_value;
-  rb->has_labels = false;   // (they were the previous contents')
-  return DFH_OK;
-}
-
-// The labels of the rows a row buffer holds (after dfh_rowbuf_load_host / _slices, same thread): with them — and its own
-// offsets, which the buffer keeps on the device and, 4 B per row, on the host — a minibatch out of this buffer is described by
-// its row numbers alone (dfh_batch_prepare_cached).  A reload drops them.
-int dfh_rowbuf_set_labels(dfh_rowbuf* rb, size_t nrows, const float* label) {
-  DFH_ARG(rb && label && nrows >= 1 && nrows == rb->nrows, "dfh_rowbuf_set_labels: one label per row of the loaded buffer");
-  DFH_HIP(hipSetDevice(rb->ctx->device));
-  if (!rb->d_lab) DFH_HIP(hipMalloc(reinterpret_cast<void**>(&rb->d_lab), rb->max_rows * sizeof(float)));
-  DFH_HIP(hipMemcpyAsync(rb->d_lab, label, nrows * sizeof(float), hipMemcpyHostToDevice, rb->up));
-  DFH_HIP(hipEventRecord(rb->ev_loaded, rb->up));   // whoever waits for the upload waits for the labels too
-  DFH_HIP(hipStreamSynchronize(rb->up));            // the caller's array is free again
-  {
-    std::lock_guard<std::mutex> lk(rb->mu);
-    rb->seen_loaded.clear();
-  }
-  rb->has_labels = true;
-  return DFH_OK;
-}
-
-int dfh_batch_gather_rows(dfh_batch* b, size_t nrows, const size_t* offset, const float* label, int nseg, dfh_rowbuf* const* bufs,
-                          const uint32_t* const* rows, const size_t* seg_rows) {
-  DFH_ARG(b && offset && label && nseg >= 1 && bufs && rows && seg_rows, "dfh_batch_gather_rows: NULL argument");
-  DFH_ARG(nrows >= 1 && nrows <= b->max_rows, "dfh_batch_gather_rows: nrows out of range");
-  std::vector<uint32_t> off32;
-  int rc = to_u32_offsets(offset, nrows, &off32);
-  if (rc) return rc;
-  const size_t nnz = off32[nrows];
-  DFH_ARG(nnz <= b->max_nnz, "dfh_batch_gather_rows: nnz exceeds max_nnz");
-  size_t total = 0;
-  bool any_value = false;
-  for (int g = 0; g < nseg; ++g) {
-    DFH_ARG(bufs[g] && bufs[g]->ctx == b->ctx && (seg_rows[g] == 0 || rows[g]), "dfh_batch_gather_rows: bad segment");
-    total += seg_rows[g];
-    any_value = any_value || bufs[g]->has_value;
-  }
-  DFH_ARG(total == nrows, "dfh_batch_gather_rows: the segments must hold nrows rows");
-  DFH_HIP(hipSetDevice(b->ctx->device));
-  phase_begin(b);
-  rc = prep_begin(b);
-  if (rc) return rc;
-  hipStream_t s = prep_of(b);
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
-  // offsets, labels and row numbers through the batch's pinned staging (the row numbers where load_host puts the ids)
-  const size_t o_off = 0, o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255),
-               o_val = o_idx + b->max_nnz * 8, stage_total = o_val + b->max_nnz * 4;
-  (void)stage_total;   // (the layout of dfh_batch_load_host; only the head of it is used here)
-  rc = ensure_stage(b, o_idx + (b->max_rows + 1) * 4);
-  if (rc) return rc;
-  if (b->staged_pending) {
-    // (a query first: hipEventSynchronize costs ~100 us of host time even on an event that completed long ago)
-    if (hipEventQuery(b->ev_staged) != hipSuccess) DFH_HIP(hipEventSynchronize(b->ev_staged));
-    b->staged_pending = false;
-  }
-  memcpy(b->h_stage + o_off, off32.data(), (nrows + 1) * 4);
-  memcpy(b->h_stage + o_lab, label, nrows * 4);
-  uint32_t* h_rows = reinterpret_cast<uint32_t*>(b->h_stage + o_idx);
-  size_t at = 0;
-  for (int g = 0; g < nseg; ++g) {
-    for (size_t i = 0; i < seg_rows[g]; ++i) {
-      DFH_ARG(rows[g][i] < bufs[g]->nrows, "dfh_batch_gather_rows: row number beyond the buffer");
-      h_rows[at + i] = rows[g][i];
-    }
-    at += seg_rows[g];
-  }
-  uint32_t* d_rows = b->d_pos;   // scratch until the Localizer writes its row ids there (same stream, later)
-  DFH_HIP(hipMemcpyAsync(b->d_offset, b->h_stage + o_off, (nrows + 1) * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipMemcpyAsync(b->d_label, b->h_stage + o_lab, nrows * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipMemcpyAsync(d_rows, h_rows, nrows * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipEventRecord(b->ev_staged, s));
-  b->staged_pending = true;
-  at = 0;
-  for (int g = 0; g < nseg; ++g) {
-    dfh_rowbuf* rb = bufs[g];
-    if (seg_rows[g] == 0) continue;
-    DFH_HIP(hipStreamWaitEvent(s, rb->ev_loaded, 0));
-    const unsigned blocks = (unsigned)std::min<size_t>((seg_rows[g] + 3) / 4, 4096);
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks), dim3(256), 0, s, rb->d_off, rb->d_idx, rb->has_value ? rb->d_val : (const float*)nullptr,
-                       d_rows + at, (uint32_t)seg_rows[g], b->d_offset + at, b->d_raw, any_value ? b->d_value : (float*)nullptr);
-    {
-      std::lock_guard<std::mutex> lk(rb->mu);
-      dfh_rowbuf::Used* u = nullptr;
-      for (auto& x : rb->used)
-        if (x.stream == s) u = &x;
-      if (!u) {
-        hipEvent_t ev = nullptr;
-        DFH_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        rb->used.push_back({s, ev, false});
-        u = &rb->used.back();
-      }
-      DFH_HIP(hipEventRecord(u->ev, s));
-      u->pending = true;
-    }
-    at += seg_rows[g];
-  }
-  DFH_HIP(hipGetLastError());
-  b->nrows = nrows;
-  b->nnz = nnz;
-  b->has_value = any_value;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
-  return DFH_OK;
-}
-
-namespace {
-// dfh_batch_prepare_rows: the description of the minibatch (row numbers, offsets, labels) is read where the host wrote it —
-// page-locked host memory mapped into the device's address space — 256 rows per block, coalesced, and passed on: the
-// minibatch's own offsets / labels land in HBM by the same kernel that gathers its rows, no copy is queued.
-__global__ void __launch_bounds__(256) k_gather_rows_staged(const uint32_t* __restrict__ src_off, const uint64_t* __restrict__ src_idx,
-                                                            const float* __restrict__ src_val, const uint32_t* __restrict__ h_rows,
-                                                            const uint32_t* __restrict__ h_off, const float* __restrict__ h_lab, uint32_t n,
-                                                            uint32_t* __restrict__ dst_off, float* __restrict__ dst_lab,
-                                                            uint64_t* __restrict__ dst_idx, float* __restrict__ dst_val, int write_end) {
-  // GR rows per block and pass: few enough that a minibatch spreads over the whole chip (10 000 rows = 313 blocks; 256
-  // rows per block left 216 of the 256 CUs idle and took 92 us), enough that the description is read in 128 B pieces
-  constexpr uint32_t GR = 32;
-  __shared__ uint32_t s_lo[GR], s_len[GR], s_d0[GR];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  for (uint32_t q0 = blockIdx.x * GR; q0 < n; q0 += gridDim.x * GR) {
-    const uint32_t m = min(GR, n - q0);
-    __syncthreads();
-    if (threadIdx.x < m) {
-      const uint32_t q = q0 + threadIdx.x;
-      const uint32_t r = h_rows[q], o = h_off[q];
-      const uint32_t lo = src_off[r];
-      s_lo[threadIdx.x] = lo;
-      s_len[threadIdx.x] = src_off[r + 1] - lo;
-      s_d0[threadIdx.x] = o;
-      dst_off[q] = o;
-      dst_lab[q] = h_lab[q];
-    }
-    if (threadIdx.x == 255 && write_end && q0 + m == n) dst_off[n] = h_off[n];
-    __syncthreads();
-    for (uint32_t t = w; t < m; t += 4u) {   // 8 rows per wave, independent addresses: the copies overlap
-      const uint32_t lo = s_lo[t], len = s_len[t], d0 = s_d0[t];
-      for (uint32_t j = lane; j < len; j += 64u) {
-        dst_idx[d0 + j] = src_idx[lo + j];
-        if (dst_val) dst_val[d0 + j] = src_val ? src_val[lo + j] : 1.0f;   // a buffer without values holds ones
-      }
-    }
-  }
-}
-}  // namespace
-
-namespace {
-// after the launch(es) that read a described minibatch's rows out of their buffers have been queued on s: the buffers may be
-// refilled, the page-locked description rewritten, once those launches are through
-int gather_queued(dfh_batch* b, hipStream_t s) {
-  for (const auto& g : b->gsegs) {
-    dfh_rowbuf* rb = g.rb;
-    std::lock_guard<std::mutex> lk(rb->mu);
-    dfh_rowbuf::Used* u = nullptr;
-    for (auto& x : rb->used)
-      if (x.stream == s) u = &x;
-    if (!u) {
-      hipEvent_t ev = nullptr;
-      DFH_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      rb->used.push_back({s, ev, false});
-      u = &rb->used.back();
-    }
-    DFH_HIP(hipEventRecord(u->ev, s));
-    u->pending = true;
-  }
-  DFH_HIP(hipEventRecord(b->ev_staged, s));   // the page-locked block may be rewritten once the launches have read it
-  b->staged_pending = true;
-  b->gather_pending = false;
-  return DFH_OK;
-}
-// the rows of a described minibatch by launches of their own (k_gather_rows_staged): where the count pass cannot gather
-int gather_alone(dfh_batch* b, hipStream_t s) {
-  for (const auto& g : b->gsegs) {
-    dfh_rowbuf* rb = g.rb;
-    const unsigned blocks = (unsigned)std::min<size_t>((g.n + 31) / 32, 2048);
-    hipLaunchKernelGGL(k_gather_rows_staged, dim3(blocks), dim3(256), 0, s, rb->d_off, rb->d_idx,
-                       rb->has_value ? rb->d_val : (const float*)nullptr, b->g_rows + g.at, b->g_off + g.at, b->g_lab + g.at, (uint32_t)g.n,
-                       b->d_offset + g.at, b->d_label + g.at, b->d_raw, b->gather_any_value ? b->d_value : (float*)nullptr,
-                       g.at + g.n == b->nrows ? 1 : 0);
-  }
-  DFH_HIP(hipGetLastError());
-  return gather_queued(b, s);
-}
-}  // namespace
 
 namespace {
 // one stage (RiderKind) of the noted sample sort of b's minibatch as a launch of its own on stream s
@@ -3152,298 +2731,6 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
 }  // namespace
 
 
-namespace {
-// A described minibatch (dfh_batch_prepare_rows, dfh_batch_prepare_cached) whose description lies in the batch's page-locked
-// block: the gather is noted — the rows stay where they are, the Localizer's count pass gathers them as it reads them
-// (k_loc_count_gather), or localize_impl queues k_gather_rows_staged first where that pass cannot (see dfh_batch::gsegs) —
-// then Localizer::Compact + the key-index probe in the same phase, ONE ev_ready at the end.  `h_base` (cached only): the
-// minibatch's offsets and labels are not part of the description; k_loc_describe derives them first, into the minibatch's own
-// arrays, and the gather reads them there (v_off / v_lab are NULL).
-struct DescribedIn {
-  size_t nrows, nnz;
-  int nseg;
-  dfh_rowbuf* const* bufs;
-  const size_t* seg_rows;
-  bool any_value;
-  const uint32_t *v_rows, *v_off;
-  const float* v_lab;
-  const uint32_t* v_tile;
-  bool fusable;
-  const uint32_t* v_base;
-};
-int queue_described(dfh_table* t, dfh_batch* b, const DescribedIn& in, uint64_t max_index, bool prof, double tp) {
-  dfh_ctx* c = b->ctx;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  auto lap = [&](int k) { if (prof) { const double x = now(); b->t_prof[k] += x - tp; tp = x; } };
-  hipStream_t s = prep_of(b);
-  const size_t nrows = in.nrows;
-  const bool cached = in.v_base != nullptr;
-  b->gsegs.clear();
-  size_t at = 0, blk0 = 0;
-  for (int g = 0; g < in.nseg; ++g) {
-    dfh_rowbuf* rb = in.bufs[g];
-    const size_t n = in.seg_rows[g];
-    if (n == 0) continue;
-    bool waited;
-    {
-      std::lock_guard<std::mutex> lk(rb->mu);
-      waited = std::find(rb->seen_loaded.begin(), rb->seen_loaded.end(), s) != rb->seen_loaded.end();
-      if (!waited) rb->seen_loaded.push_back(s);
-    }
-    if (!waited) DFH_HIP(hipStreamWaitEvent(s, rb->ev_loaded, 0));
-    if (cached) {
-      const unsigned blocks = (unsigned)((n + LOC_DESC_ROWS - 1) / LOC_DESC_ROWS);
-      hipLaunchKernelGGL(k_loc_describe, dim3(blocks), dim3(LOC_DESC_ROWS), 0, s, rb->d_off, rb->d_lab, in.v_rows + at, in.v_base + blk0,
-                         (uint32_t)n, b->d_offset + at, b->d_label + at, at + n == nrows ? 1 : 0);
-      blk0 += blocks;
-    }
-    b->gsegs.push_back({rb, at, n});
-    at += n;
-  }
-  if (cached) DFH_HIP(hipGetLastError());
-  const uint32_t* v_off = cached ? b->d_offset : in.v_off;
-  const float* v_lab = cached ? b->d_label : in.v_lab;
-  b->g_rows = in.v_rows;
-  b->g_off = v_off;
-  b->g_lab = v_lab;
-  b->gather_any_value = in.any_value;
-  b->gather_pending = true;
-  {
-    GatherSrc& gs = b->gsrc;
-    const bool ok = in.fusable;
-    b->gather_fusable = ok;
-    gs.nseg = (int)b->gsegs.size();
-    for (int g = 0; g <= LOC_GATHER_SEGS; ++g) gs.seg_row0[g] = (uint32_t)nrows;
-    for (int g = 0; g < LOC_GATHER_SEGS; ++g) {
-      const bool have = g < gs.nseg && ok;
-      gs.seg_row0[g] = have ? (uint32_t)b->gsegs[g].at : (uint32_t)nrows;
-      gs.src_off[g] = have ? b->gsegs[g].rb->d_off : nullptr;
-      gs.src_idx[g] = have ? b->gsegs[g].rb->d_idx : nullptr;
-      gs.src_val[g] = (have && b->gsegs[g].rb->has_value) ? b->gsegs[g].rb->d_val : nullptr;
-    }
-    gs.h_rows = in.v_rows;
-    gs.h_off = v_off;
-    gs.h_lab = v_lab;
-    gs.h_tile_row = in.v_tile;
-    gs.dst_raw = b->d_raw;
-    gs.dst_val = in.any_value ? b->d_value : nullptr;
-    gs.dst_off = b->d_offset;
-    gs.dst_lab = b->d_label;
-  }
-  b->nrows = nrows;
-  b->nnz = in.nnz;
-  b->has_value = in.any_value;
-  b->has_cnt = false;
-  b->localized = false;
-  b->looked_up = nullptr;
-  lap(3);  // gather queued
-  // Localizer::Compact + the key-index probe, same phase: ONE ev_ready at the end
-  b->defer_ready = true;
-  int rc = localize_impl(b, max_index, nullptr);
-  lap(4);  // Localizer queued
-  if (!rc && in.nnz > kSmallBatchPairs && !c->single_queue) {   // (a small minibatch: the step's own pass probes, see dfh_batch_lookup)
-    hipLaunchKernelGGL(k_lookup, dim3(grid_for_threads(b->nnz, c)), dim3(256), 0, s, t->v, b->d_feaids, b->d_U, 0u, b->d_urow,
-                       (const float*)nullptr, b->d_col_ptr, 0, (uint32_t*)nullptr, 0, (uint2*)nullptr, AucFin{nullptr, 0u, nullptr});
-    if (hipGetLastError() != hipSuccess) rc = DFH_ERR_HIP;
-    b->looked_up = t;
-  }
-  b->defer_ready = false;
-  if (rc) return rc;
-  rc = prep_end(b);
-  lap(5);  // lookup queued, ev_ready recorded
-  if (prof) ++b->n_prof;
-  return rc;
-}
-}  // namespace
-
-int dfh_batch_prepare_rows(dfh_table* t, dfh_batch* b, size_t nrows, const size_t* offset, const float* label, int nseg,
-                           dfh_rowbuf* const* bufs, const uint32_t* const* rows, const size_t* seg_rows, uint64_t max_index) {
-  DFH_ARG(t && b && t->ctx == b->ctx && offset && label && nseg >= 1 && bufs && rows && seg_rows, "dfh_batch_prepare_rows: NULL argument");
-  DFH_ARG(nrows >= 1 && nrows <= b->max_rows, "dfh_batch_prepare_rows: nrows out of range");
-  DFH_ARG(max_index != 0, "max_index must be nonzero");
-  const size_t base = offset[0], nnz = offset[nrows] - base;
-  DFH_ARG(nnz <= b->max_nnz && nnz < 0xFFFFFFFFULL, "dfh_batch_prepare_rows: nnz exceeds max_nnz");
-  size_t total = 0;
-  bool any_value = false;
-  for (int g = 0; g < nseg; ++g) {
-    DFH_ARG(bufs[g] && bufs[g]->ctx == b->ctx && (seg_rows[g] == 0 || rows[g]), "dfh_batch_prepare_rows: bad segment");
-    total += seg_rows[g];
-    any_value = any_value || bufs[g]->has_value;
-  }
-  DFH_ARG(total == nrows, "dfh_batch_prepare_rows: the segments must hold nrows rows");
-  dfh_ctx* c = b->ctx;
-  static const bool prof = getenv("DFH_PROFILE_PREP") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tp = prof ? now() : 0;
-  auto lap = [&](int k) { if (prof) { const double x = now(); b->t_prof[k] += x - tp; tp = x; } };
-  DFH_HIP(hipSetDevice(c->device));
-  if (nnz) {
-    int rcr = table_reserve(t, nnz);  // U <= nnz keys may be new; before anything of this phase is queued
-    if (rcr) return rcr;
-  }
-  phase_begin(b);
-  int rc = prep_begin(b);
-  if (rc) return rc;
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
-  // the same page-locked block as dfh_batch_load_host / dfh_batch_gather_rows: offsets | labels | (ids ->) row numbers
-  const size_t o_off = 0, o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255),
-               o_val = o_idx + b->max_nnz * 8, stage_total = o_val + b->max_nnz * 4;
-  (void)stage_total;   // (the layout of dfh_batch_load_host; only the head of it is used here)
-  const size_t o_tile = o_idx + (b->max_rows + 1) * 4;   // the tiles' first rows (k_loc_count_gather), behind the row numbers
-  rc = ensure_stage(b, o_tile + (b->max_tiles + 2) * 4);
-  if (rc) return rc;
-  if (!b->d_stage_view) DFH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_stage_view), b->h_stage, 0));
-  lap(0);  // set-up, prep_begin (wait for the batch object's previous step)
-  if (b->staged_pending) {
-    // (a query first: hipEventSynchronize costs ~100 us of host time even on an event that completed long ago)
-    if (hipEventQuery(b->ev_staged) != hipSuccess) DFH_HIP(hipEventSynchronize(b->ev_staged));
-    b->staged_pending = false;
-  }
-  lap(1);  // the previous description has been read
-  uint32_t* h_off = reinterpret_cast<uint32_t*>(b->h_stage + o_off);
-  for (size_t i = 0; i <= nrows; ++i) {
-    DFH_ARG(offset[i] >= base && (i == 0 || offset[i] >= offset[i - 1]), "dfh_batch_prepare_rows: offsets must not decrease");
-    h_off[i] = (uint32_t)(offset[i] - base);
-  }
-  memcpy(b->h_stage + o_lab, label, nrows * 4);
-  uint32_t* h_rows = reinterpret_cast<uint32_t*>(b->h_stage + o_idx);
-  size_t at = 0;
-  for (int g = 0; g < nseg; ++g) {
-    const uint32_t lim = (uint32_t)bufs[g]->nrows;
-    const uint32_t* src = rows[g];
-    uint32_t worst = 0;
-    for (size_t i = 0; i < seg_rows[g]; ++i) {
-      h_rows[at + i] = src[i];
-      worst = std::max(worst, src[i]);
-    }
-    DFH_ARG(seg_rows[g] == 0 || worst < lim, "dfh_batch_prepare_rows: row number beyond the buffer");
-    at += seg_rows[g];
-  }
-  lap(2);  // description written
-  const uint32_t* v_off = reinterpret_cast<const uint32_t*>(b->d_stage_view + o_off);
-  const float* v_lab = reinterpret_cast<const float*>(b->d_stage_view + o_lab);
-  const uint32_t* v_rows = reinterpret_cast<const uint32_t*>(b->d_stage_view + o_idx);
-  // what the count pass needs on top: the first row of every tile of LOC_TILE positions (the last row that starts at or before
-  // the tile), behind the row numbers in the same page-locked block; a tile may span LOC_GATHER_ROWS rows, a minibatch
-  // LOC_GATHER_SEGS buffers
-  size_t nsegs_used = 0;
-  for (int g = 0; g < nseg; ++g) nsegs_used += seg_rows[g] != 0;
-  const size_t ntiles = (nnz + LOC_TILE - 1) / LOC_TILE;
-  uint32_t* h_tile = reinterpret_cast<uint32_t*>(b->h_stage + o_tile);
-  bool ok = nnz > 0 && nsegs_used <= (size_t)LOC_GATHER_SEGS;
-  size_t r = 0;
-  for (size_t t = 0; t < ntiles && ok; ++t) {
-    const uint32_t p = (uint32_t)(t * LOC_TILE);
-    while (r + 1 < nrows && h_off[r + 1] <= p) ++r;   // the last row with off[r] <= p
-    h_tile[t] = (uint32_t)r;
-    if (t > 0 && r - h_tile[t - 1] + 1 > (size_t)LOC_GATHER_ROWS) ok = false;
-  }
-  if (ok) {
-    h_tile[ntiles] = (uint32_t)nrows;
-    if (nrows - h_tile[ntiles - 1] > (size_t)LOC_GATHER_ROWS) ok = false;   // (the last tile's rows, trailing empty ones included)
-  }
-  DescribedIn in{nrows, nnz, nseg, bufs, seg_rows, any_value, v_rows, v_off, v_lab,
-                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_tile), ok, nullptr};
-  return queue_described(t, b, in, max_index, prof, tp);
-}
-
-// dfh_batch_prepare_rows for a minibatch out of buffers that carry their own labels (dfh_rowbuf_set_labels): the caller names
-// the rows, nothing else.  The host's share: the row numbers into the page-locked block (4 B per row), and — read off the
-// buffers' host-side offsets while it copies them — the minibatch's nnz (the launches that follow are sized by it), the running
-// total at every 256th row of a segment (k_loc_describe's block bases) and the first row of every tile (the count pass's
-// gather, as in dfh_batch_prepare_rows).  Offsets and labels are derived on the device (k_loc_describe, dfh_localize.hip).
-int dfh_batch_prepare_cached(dfh_table* t, dfh_batch* b, size_t nrows, int nseg, dfh_rowbuf* const* bufs, const uint32_t* const* rows,
-                             const size_t* seg_rows, uint64_t max_index) {
-  DFH_ARG(t && b && t->ctx == b->ctx && nseg >= 1 && bufs && rows && seg_rows, "dfh_batch_prepare_cached: NULL argument");
-  DFH_ARG(nrows >= 1 && nrows <= b->max_rows, "dfh_batch_prepare_cached: nrows out of range");
-  DFH_ARG(max_index != 0, "max_index must be nonzero");
-  size_t total = 0, nblk = 0, nsegs_used = 0;
-  bool any_value = false;
-  for (int g = 0; g < nseg; ++g) {
-    DFH_ARG(bufs[g] && bufs[g]->ctx == b->ctx && (seg_rows[g] == 0 || rows[g]), "dfh_batch_prepare_cached: bad segment");
-    DFH_ARG(bufs[g]->has_labels && bufs[g]->off32.size() == bufs[g]->nrows + 1,
-            "dfh_batch_prepare_cached: a row buffer without labels (dfh_rowbuf_set_labels)");
-    total += seg_rows[g];
-    nblk += (seg_rows[g] + LOC_DESC_ROWS - 1) / LOC_DESC_ROWS;
-    nsegs_used += seg_rows[g] != 0;
-    any_value = any_value || bufs[g]->has_value;
-  }
-  DFH_ARG(total == nrows, "dfh_batch_prepare_cached: the segments must hold nrows rows");
-  dfh_ctx* c = b->ctx;
-  static const bool prof = getenv("DFH_PROFILE_PREP") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tp = prof ? now() : 0;
-  auto lap = [&](int k) { if (prof) { const double x = now(); b->t_prof[k] += x - tp; tp = x; } };
-  DFH_HIP(hipSetDevice(c->device));
-  // the page-locked block of dfh_batch_prepare_rows: | (offsets) | (labels) | row numbers | tile rows | block bases
-  const size_t o_lab = (b->max_rows + 1) * 4, o_idx = ((o_lab + b->max_rows * 4 + 255) & ~(size_t)255);
-  const size_t o_tile = o_idx + (b->max_rows + 1) * 4, o_base = o_tile + (b->max_tiles + 2) * 4;
-  int rc = ensure_stage(b, o_base + (nblk + 1) * 4);
-  if (rc) return rc;
-  if (!b->d_stage_view) DFH_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_stage_view), b->h_stage, 0));
-  if (b->staged_pending) {
-    if (hipEventQuery(b->ev_staged) != hipSuccess) DFH_HIP(hipEventSynchronize(b->ev_staged));
-    b->staged_pending = false;
-  }
-  lap(1);  // the previous description has been read
-  uint32_t* h_rows = reinterpret_cast<uint32_t*>(b->h_stage + o_idx);
-  uint32_t* h_tile = reinterpret_cast<uint32_t*>(b->h_stage + o_tile);
-  uint32_t* h_base = reinterpret_cast<uint32_t*>(b->h_stage + o_base);
-  // h_tile[t] = the last row that starts at or before position t * LOC_TILE: when row q starts beyond it, that row is q - 1
-  size_t at = 0, nnz = 0, nt = 0, nb = 0;
-  const size_t tile_cap = b->max_tiles + 1;   // (a minibatch beyond max_nnz is refused below; its surplus tiles are not written)
-  for (int g = 0; g < nseg; ++g) {
-    const uint32_t lim = (uint32_t)bufs[g]->nrows;
-    const uint32_t* src = rows[g];
-    const uint32_t* off = bufs[g]->off32.data();
-    for (size_t i = 0; i < seg_rows[g]; ++i) {
-      const uint32_t r = src[i];
-      DFH_ARG(r < lim, "dfh_batch_prepare_cached: row number beyond the buffer");
-      h_rows[at + i] = r;
-      if (i % LOC_DESC_ROWS == 0) h_base[nb++] = (uint32_t)nnz;
-      while (nt * (size_t)LOC_TILE < nnz && nt < tile_cap) h_tile[nt++] = (uint32_t)(at + i - 1);
-      nnz += off[r + 1] - off[r];
-    }
-    at += seg_rows[g];
-  }
-  DFH_ARG(nnz <= b->max_nnz && nnz < 0xFFFFFFFFULL, "dfh_batch_prepare_cached: nnz exceeds max_nnz");
-  const size_t ntiles = (nnz + LOC_TILE - 1) / LOC_TILE;
-  while (nt < ntiles) h_tile[nt++] = (uint32_t)(nrows - 1);
-  bool ok = nnz > 0 && nsegs_used <= (size_t)LOC_GATHER_SEGS;
-  for (size_t q = 1; q < ntiles && ok; ++q)
-    if ((size_t)h_tile[q] - h_tile[q - 1] + 1 > (size_t)LOC_GATHER_ROWS) ok = false;
-  if (ok) {
-    h_tile[ntiles] = (uint32_t)nrows;
-    if (nrows - h_tile[ntiles - 1] > (size_t)LOC_GATHER_ROWS) ok = false;   // (the last tile's rows, trailing empty ones included)
-  }
-  lap(2);  // description written
-  if (nnz) {
-    int rcr = table_reserve(t, nnz);  // U <= nnz keys may be new; before anything of this phase is queued
-    if (rcr) return rcr;
-  }
-  phase_begin(b);
-  rc = prep_begin(b);
-  if (rc) return rc;
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
-  lap(0);  // prep_begin (wait for the batch object's previous step)
-  DescribedIn in{nrows, nnz, nseg, bufs, seg_rows, any_value, reinterpret_cast<const uint32_t*>(b->d_stage_view + o_idx), nullptr, nullptr,
-                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_tile), ok,
-                 reinterpret_cast<const uint32_t*>(b->d_stage_view + o_base)};
-  return queue_described(t, b, in, max_index, prof, tp);
-}
-
-// the loaded minibatch's own offsets [nrows + 1] and labels [nrows] as the device holds them (tests: a described minibatch's
-// are written by the gather, a cached one's derived by k_loc_describe).  Synchronises.
-int dfh_batch_get_rows(dfh_batch* b, uint32_t* offset, float* label) {
-  DFH_ARG(b && b->nrows > 0 && offset && label, "dfh_batch_get_rows: no batch loaded / NULL argument");
-  DFH_HIP(hipSetDevice(b->ctx->device));
-  int rc = sync_all(b->ctx);
-  if (rc) return rc;
-  DFH_HIP(hipMemcpy(offset, b->d_offset, (b->nrows + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  DFH_HIP(hipMemcpy(label, b->d_label, b->nrows * sizeof(float), hipMemcpyDeviceToHost));
-  return DFH_OK;
-}
-
 int dfh_localize(dfh_batch* b, uint64_t max_index) {
   DFH_ARG(b && b->nrows > 0, "dfh_localize: no batch loaded");
   DFH_ARG(max_index != 0, "max_index must be nonzero");
@@ -3540,11 +2827,9 @@ int dfh_batch_load_localized_host(dfh_batch* b, size_t nrows, const size_t* offs
       }
   }
   DFH_HIP(hipSetDevice(b->ctx->device));
-  phase_begin(b);
-  rc = prep_begin(b);
+  rc = phase_own_arrays(b);
   if (rc) return rc;
   hipStream_t s = prep_of(b);
-  b->d_raw = b->o_raw; b->d_offset = b->o_offset; b->d_value = b->o_value; b->d_label = b->o_label;
   b->looked_up = nullptr;
   uint32_t U32 = (uint32_t)U;
   DFH_HIP(hipMemcpyAsync(b->d_offset, off32.data(), (nrows + 1) * 4, hipMemcpyHostToDevice, s));

@@ -56,6 +56,7 @@
 #ifndef DFH_LOCALIZE_HIP_
 #define DFH_LOCALIZE_HIP_
 #include "dfh_internal.h"
+#include "dfh_feed_layout.h"   // LOC_TILE, LOC_GATHER_ROWS, LOC_GATHER_SEGS, LOC_DESC_ROWS: shared with the host side
 
 namespace dfh {
 
@@ -69,13 +70,9 @@ constexpr int LOC_MAX_AVG = 700;
 // (tests/test_loc_sort_runs.py shapes its minibatches by these two, by DFH_LOC_SMALL_AVG of dfh_api.hip and by emit's splitters so
 // that n = 1 .. 1 024 pairs land in ONE bucket; no getter shows the bucket count, so a change here must revisit its primers)
 constexpr int LOC_LDS_CAP = 1024;      // pairs a bucket may hold to be sorted in LDS
-#ifndef DFH_LOC_TILE
-#define DFH_LOC_TILE 2048
-#endif
 #ifndef DFH_LOC_TILE_THREADS
 #define DFH_LOC_TILE_THREADS 1024
 #endif
-constexpr int LOC_TILE = DFH_LOC_TILE;         // pairs per block in count / scatter
 constexpr int LOC_TILE_THREADS = DFH_LOC_TILE_THREADS;
 constexpr int LOC_PER_THREAD = LOC_TILE / LOC_TILE_THREADS;
 constexpr int LOC_SORT_THREADS = 256;
@@ -269,8 +266,6 @@ __global__ void __launch_bounds__(256) k_loc_splitters(LocView v) {
 // (the host, which wrote the offsets, also wrote the first row of every tile), stages their {offset, source position} in
 // LDS, reads every pair's raw id straight out of the row buffer and leaves it in the minibatch's own array for
 // k_loc_scatter.  Until round 6 a launch of its own (k_gather_rows_staged, 16 us at C3 size) opened the preparation chain.
-constexpr int LOC_GATHER_ROWS = 1024;   // rows a tile may span (the host checks; beyond: the gather runs as its own launch)
-constexpr int LOC_GATHER_SEGS = 4;      // row buffers one minibatch may draw from
 struct GatherSrc {
   int nseg;                                // 0: no gather (v.raw holds the minibatch already)
   uint32_t seg_row0[LOC_GATHER_SEGS + 1];  // rows [seg_row0[g], seg_row0[g + 1]) of the minibatch come from buffer g
@@ -454,7 +449,6 @@ __global__ void __launch_bounds__(LOC_TILE_THREADS) k_loc_count_gather(LocView v
 // are gathered as ones.  Nothing of that depends on this kernel.
 // Registers: 13 VGPRs, 26 SGPRs, no scratch, 16 B of LDS (the count pass: 18 VGPRs, 20 when it gathers).
 // ---------------------------------------------------------------------------------------
-constexpr int LOC_DESC_ROWS = 256;
 __global__ void __launch_bounds__(LOC_DESC_ROWS) k_loc_describe(const uint32_t* __restrict__ src_off, const float* __restrict__ src_lab,
                                                                 const uint32_t* __restrict__ h_rows, const uint32_t* __restrict__ h_base,
                                                                 uint32_t n, uint32_t* __restrict__ dst_off, float* __restrict__ dst_lab,

@@ -8,6 +8,7 @@
  *   ForEachChunk                    resident_data.h: a reader block cut by rows at a bound on its entries
  *   LBFGSLearner.Basic / WithV      tests/cpp/lbfgs_learner_test.cc:8-146 (objective trajectories of an
  *                                   L-BFGS loop over Loss::Predict / CalcGrad / Evaluate — lbfgs_mini.h)
+ *   StageLayout / tile rows         csrc/dfh_feed_layout.h: the device feed's page-locked block and its tile-row table
  * plus Store Pull/Push and Updater Save/Load round trips.  Needs a GPU, except the reader cases.
  * usage: difacto_host_tests <path to rcv1_100.libsvm> [reader]     ("reader": only the host-only cases)
  */
@@ -22,6 +23,7 @@
 #include "./resident_data.h"
 #include "./sgd_learner.h"
 #include "dmlc/memory_io.h"
+#include "dfh_feed_layout.h"
 
 using namespace difacto;
 
@@ -344,6 +346,84 @@ static void TestStoreAndModelIO() {
   for (size_t i = 0; i < vals.size() && i < vals2.size(); ++i) EXPECT(vals[i] == vals2[i]);
 }
 
+// the staging block every feed path writes and the device reads in place: offsets as the entry points computed them by hand
+// before StageLayout, for a one-row batch, a small one and the benchmark's
+static void TestStageLayout() {
+  const size_t shapes[3][3] = {{1, 1, 1}, {400, 16000, 8}, {10000, 480000, 235}};
+  for (auto& sh : shapes) {
+    const size_t max_rows = sh[0], max_nnz = sh[1], max_tiles = sh[2];
+    const dfh::StageLayout L(max_rows, max_nnz, max_tiles);
+    const size_t o_off = 0, o_lab = (max_rows + 1) * 4, o_idx = ((o_lab + max_rows * 4 + 255) & ~(size_t)255),
+                 o_val = o_idx + max_nnz * 8, total = o_val + max_nnz * 4;
+    const size_t o_tile = o_idx + (max_rows + 1) * 4, o_base = o_tile + (max_tiles + 2) * 4;
+    EXPECT(L.o_off == o_off && L.o_lab == o_lab && L.o_idx == o_idx && L.o_val == o_val && L.o_tile == o_tile && L.o_base == o_base);
+    EXPECT(L.o_idx % 256 == 0);
+    EXPECT(L.load_host_bytes == total && L.load_host_bytes >= L.o_val + 4 * max_nnz);
+    EXPECT(L.rows_bytes() == o_tile + (max_tiles + 2) * 4 && L.rows_bytes() > 0);
+    for (size_t nblk : {(size_t)1, (max_rows + dfh::LOC_DESC_ROWS - 1) / dfh::LOC_DESC_ROWS + dfh::LOC_GATHER_SEGS}) {
+      EXPECT(L.cached_bytes(nblk) == o_base + (nblk + 1) * 4);
+      EXPECT(L.cached_bytes(nblk) > L.rows_bytes());
+    }
+  }
+}
+
+// one minibatch (its rows' lengths) through the two fills of the tile-row table: from offsets (dfh_batch_prepare_rows) and
+// streaming over the lengths (dfh_batch_prepare_cached); returns the shared verdict, the table in *tile
+static bool tile_rows_both(const std::vector<uint32_t>& len, size_t nsegs, std::vector<uint32_t>* tile) {
+  const size_t T = dfh::LOC_TILE, nrows = len.size();
+  std::vector<uint32_t> off(nrows + 1, 0);
+  for (size_t q = 0; q < nrows; ++q) off[q + 1] = off[q] + len[q];
+  const size_t nnz = off[nrows], ntiles = (nnz + T - 1) / T;
+  std::vector<uint32_t> a(ntiles + 2, 0xDEADu), b(ntiles + 2, 0xDEADu);
+  const size_t nt_a = dfh::tile_rows_fill(off.data(), nrows, a.data());
+  EXPECT(nt_a == ntiles);
+  const bool ok_a = dfh::tile_rows_finish(a.data(), nt_a, nrows, nnz, nsegs);
+  size_t run = 0, nt = 0;
+  for (size_t q = 0; q < nrows; ++q) {
+    while (nt * T < run && nt < ntiles + 1) b[nt++] = (uint32_t)(q - 1);
+    run += len[q];
+  }
+  while (nt < ntiles) b[nt++] = (uint32_t)(nrows - 1);
+  const bool ok_b = dfh::tile_rows_finish(b.data(), ntiles, nrows, nnz, nsegs);
+  EXPECT(ok_a == ok_b);
+  if (ok_a && ok_b)
+    for (size_t t = 0; t <= ntiles; ++t) EXPECT(a[t] == b[t]);   // the sentinel included
+  *tile = a;
+  return ok_a;
+}
+
+static void TestTileRows() {
+  const uint32_t T = dfh::LOC_TILE, R = dfh::LOC_GATHER_ROWS;
+  EXPECT(T >= R);   // (the cases below put R - 1 rows of one pair into a tile)
+  std::vector<uint32_t> tile;
+  // one row longer than two tiles: the tiles it covers all start in it
+  EXPECT(tile_rows_both({3, 2 * T + 5, 4}, 1, &tile));
+  EXPECT(tile.size() >= 4 && tile[0] == 0 && tile[1] == 1 && tile[2] == 1 && tile[3] == 3);
+  // the first tile spans exactly R rows (row R - 1 starts at the tile's end) ...
+  std::vector<uint32_t> len(R, 1);
+  len[0] = T - (R - 2);
+  len[R - 1] = 5;
+  EXPECT(tile_rows_both(len, 1, &tile));
+  EXPECT(tile[0] == 0 && tile[1] == R - 1 && tile[2] == R);
+  // ... and one row more
+  len.assign(R + 1, 1);
+  len[0] = T - (R - 1);
+  len[R] = 5;
+  EXPECT(!tile_rows_both(len, 1, &tile));
+  // trailing empty rows belong to the last tile: R rows in all, then R + 1
+  len.assign(R, 0);
+  len[0] = 5;
+  EXPECT(tile_rows_both(len, 1, &tile));
+  EXPECT(tile[0] == 0 && tile[1] == R);
+  len.push_back(0);
+  EXPECT(!tile_rows_both(len, 1, &tile));
+  // no pair at all: nothing for the count pass to gather
+  EXPECT(!tile_rows_both({0, 0, 0}, 1, &tile));
+  // as many buffers as the count pass has sources, and one more
+  EXPECT(tile_rows_both({3, 4, 5}, dfh::LOC_GATHER_SEGS, &tile));
+  EXPECT(!tile_rows_both({3, 4, 5}, dfh::LOC_GATHER_SEGS + 1, &tile));
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: %s <rcv1_100.libsvm>\n", argv[0]);
@@ -358,6 +438,10 @@ int main(int argc, char** argv) {
     const int before = g_fail;
     TestForEachChunk();
     printf("[%s] %s\n", g_fail == before ? "  OK  " : "FAILED", "ForEachChunk cuts a block at the entry bound");
+    const int before2 = g_fail;
+    TestStageLayout();
+    TestTileRows();
+    printf("[%s] %s\n", g_fail == before2 ? "  OK  " : "FAILED", "StageLayout + tile rows of the device feed");
     printf("%s\n", g_fail ? "SOME TESTS FAILED" : "ALL HOST TESTS PASSED");
     return g_fail ? 1 : 0;
   }
@@ -365,6 +449,7 @@ int main(int argc, char** argv) {
       {"RefRand = glibc rand() / std::random_shuffle", TestRefRand},
       {"BatchReader.Read+RandRead+PartRead", TestBatchReader},
       {"ForEachChunk cuts a block at the entry bound", TestForEachChunk},
+      {"StageLayout + tile rows of the device feed", [] { TestStageLayout(); TestTileRows(); }},
       {"Localizer.Base+BaseHash", TestLocalizer},
       {"FMLoss.NoV", TestFMLossNoV},
       {"FMLoss.HasV", TestFMLossHasV},

@@ -255,7 +255,8 @@ int dfh_localize_lookup(dfh_table* t, dfh_batch* b, uint64_t max_index);
  * stream of its own and returns when the caller's arrays are free) and a minibatch is gathered out of at most a few buffers
  * by row number on the device (dfh_batch_gather_rows, in place of dfh_batch_load_host): `offset` [nrows + 1] and `label`
  * [nrows] are the minibatch's own (the host knows the row lengths), segment g takes rows[g][0 .. seg_rows[g]) of bufs[g], in
- * order.  A buffer without values counts as all ones.  The same minibatch as the host-side gather, byte for byte. */
+ * order.  A buffer without values counts as all ones.  The same minibatch as the host-side gather, byte for byte.  The gather
+ * kernel reads the description in place, in the batch object's page-locked staging block, as dfh_batch_prepare_rows' does. */
 typedef struct dfh_rowbuf dfh_rowbuf;
 int dfh_rowbuf_create(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_rowbuf** out);
 int dfh_rowbuf_destroy(dfh_rowbuf* rb);
