@@ -40,6 +40,7 @@ SYMBOLS = [
     "dfh_lbfgs_owned_range", "dfh_lbfgs_set_model", "dfh_bcd_set_model",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
+    "dfh_bcd_create_sharded",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -236,6 +237,7 @@ def lib():
     L.dfh_lbfgs_line_search.argtypes = [vp, f32, f32, PP(f32), PP(f32), PP(f32)]
     L.dfh_lbfgs_evaluate.argtypes = [vp, PP(f32), PP(f32), PP(f32)]
     L.dfh_bcd_create.argtypes = [vp, PP(vp)]
+    L.dfh_bcd_create_sharded.argtypes = [vp, vp, PP(vp)]
     L.dfh_bcd_destroy.argtypes = [vp]
     L.dfh_bcd_add_chunk.argtypes = [vp, i32, sz, vp, vp, vp, vp]
     L.dfh_bcd_build.argtypes = [vp, f32, i32, vp, vp, f32, f32, PP(u64)]
@@ -882,11 +884,16 @@ class Bcd:
     """the block coordinate descent state resident in HBM (dfh_bcd): data chunks with their per-block layouts,
     predictions, and the model w / delta / delta w"""
 
-    def __init__(self, ctx):
-        self.ctx = ctx
+    def __init__(self, ctx, comm=None):
+        """comm (a Comm): the sharded object of dfh_bcd_create_sharded; every call is then collective, the chunks are this
+        rank's rows and the model is the whole, replicated model"""
+        self.ctx, self.comm = ctx, comm
         self.h = C.c_void_p()
         self.nkeys = 0
-        _ck(lib().dfh_bcd_create(ctx.h, C.byref(self.h)))
+        if comm is None:
+            _ck(lib().dfh_bcd_create(ctx.h, C.byref(self.h)))
+        else:
+            _ck(lib().dfh_bcd_create_sharded(ctx.h, comm.h, C.byref(self.h)))
 
     def add_chunk(self, offset, index, value, label, is_val=False):
         offset = np.ascontiguousarray(offset, np.uint64)

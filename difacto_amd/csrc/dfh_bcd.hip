@@ -29,6 +29,15 @@
 //                 records are [rec[b], rec[b + 1])
 // Neither pass needs atomics.  The block id of a launch is read from a device-side order array, so that an epoch's
 // launches are queued back to back on one stream; every launch of a chunk has the grid of its largest block.
+//
+// Over the ranks of a communicator (dfh_bcd_create_sharded; the reference's workers and servers, bcd_learner.cc:171-315):
+// every rank keeps its own rows and the whole model.  The positions of a block are cut into `world` slices, rank r the
+// "server" of slice r.  One block step: the rank's partial g, h over its own chunks (k_bcd_grad + k_bcd_fixup) -> every
+// slice's partials to its owner (all-to-all-v) -> k_bcd_reduce adds a key's partials in ascending source rank ->
+// k_bcd_update on the owned slice -> the slice's delta w to every peer (all-to-all-v) -> k_bcd_apply stores w, delta,
+// delta w of the other slices as k_bcd_update stored them -> k_bcd_pred over the rank's own chunks.  No float atomics: the
+// model has the same bits on every rank, run and transport.
+#include <climits>
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -204,14 +213,15 @@ struct UpdArgs {
   float* dw;
   float l1, lr;
   int zero;    // clear gacc / hacc for the next block
+  int lo, hi;  // the block-local positions [lo, hi) this launch updates (a plain object: the whole block)
 };
 
 // BCDUpdater::UpdateWeight (bcd_updater.h:138-162) on the block's summed g, h, then bcd::Delta::Update (bcd_utils.h:158-163)
 __global__ void __launch_bounds__(THREADS) k_bcd_update(UpdArgs A) {
   const int blk = A.order[A.at];
   const int pb = A.pbeg[blk], n = A.pend[blk] - pb;
-  const int k = blockIdx.x * THREADS + threadIdx.x;
-  if (k >= n) return;
+  const int k = A.lo + blockIdx.x * THREADS + threadIdx.x;
+  if (k >= n || k >= A.hi) return;
   const float g = (float)A.gacc[k];
   const float hh = (float)A.hacc[k];
   if (A.zero) {
@@ -236,6 +246,40 @@ __global__ void __launch_bounds__(THREADS) k_bcd_update(UpdArgs A) {
   A.delta[pb + k] = (nd < 5.f) ? nd : 5.f;   // std::min(max_val, .)
   A.w[pb + k] = w + d;
   A.dw[pb + k] = d;
+}
+
+// sharded: the owner of slice [lo, lo + own) of a block's n keys adds the W partials of each of its keys (xg / xh: [W][own],
+// source rank major) in ascending source rank, starting from rank 0's value, and writes gacc / hacc of the slice once;
+// the other slices are cleared for the next block's k_bcd_grad
+__global__ void __launch_bounds__(THREADS) k_bcd_reduce(const double* __restrict__ xg, const double* __restrict__ xh, int W, int n,
+                                                        int lo, int own, double* __restrict__ gacc, double* __restrict__ hacc) {
+  const int k = blockIdx.x * THREADS + threadIdx.x;
+  if (k >= n) return;
+  double g = 0.0, h = 0.0;
+  const int j = k - lo;
+  if (j >= 0 && j < own) {
+    g = xg[j];
+    h = xh[j];
+    for (int p = 1; p < W; ++p) {
+      g += xg[(size_t)p * own + j];
+      h += xh[(size_t)p * own + j];
+    }
+  }
+  gacc[k] = g;
+  hacc[k] = h;
+}
+
+// sharded: the keys of the slices this rank does not own take the step d their owners computed (xd: the block's n steps
+// in position order): exactly the three stores of k_bcd_update
+__global__ void __launch_bounds__(THREADS) k_bcd_apply(const float* __restrict__ xd, int n, int lo, int hi, int pb,
+                                                       float* __restrict__ w, float* __restrict__ delta, float* __restrict__ dw) {
+  const int k = blockIdx.x * THREADS + threadIdx.x;
+  if (k >= n || (k >= lo && k < hi)) return;
+  const float d = xd[k];
+  const float nd = (float)((double)fabsf(d) * 2.0 + .1);
+  delta[pb + k] = (nd < 5.f) ? nd : 5.f;
+  w[pb + k] = w[pb + k] + d;
+  dw[pb + k] = d;
 }
 
 struct PredArgs {
@@ -425,6 +469,14 @@ struct dfh_bcd {
   double* d_part = nullptr;       // [PROG_BLOCKS][2]
   double* d_res = nullptr;        // [chunks][4] {objv, correct, auc x n, -}
   size_t res_cap = 0;
+  // ---- sharded (dfh_bcd_create_sharded): a worker for its own chunks, the server of one slice of every block
+  dfh_comm* comm = nullptr;
+  int max_slice = 0;              // keys of the largest slice of any block
+  double *d_xg = nullptr, *d_xh = nullptr;   // [world][max_slice] the partials of the own slice, source rank major
+  float* d_xd = nullptr;          // [max_keys] the block's delta w as the owners sent it
+  std::vector<size_t> xsb, xso, xrb, xsb4, xrb4, xzero;   // bytes and offsets per peer of the block under way
+  // slice p of a block of n keys: block-local positions [slice(p, n), slice(p + 1, n))
+  int slice(int p, int n) const { return (int)((long long)p * n / comm->world); }
 };
 
 namespace {
@@ -437,6 +489,87 @@ inline size_t bcd_layout_bytes(size_t nnz, int nblk, bool val) {
   return nnz * (sizeof(int) + sizeof(int) + (val ? 4 : 0) + 2 * sizeof(uint32_t)) + (size_t)(nblk + 2) * 16 + 1024;
 }
 inline size_t bcd_build_bytes(size_t nnz, size_t sort_tmp) { return nnz * (8 + 8 + 4 + 4 + 4 + 4) + sort_tmp + 1024; }
+
+// sharded, between the gradient and the predictions of block h_order[at]: the slices' partials to their owners, the sums
+// in rank order, the update of the owned slice, its delta w to every peer, the peers' slices applied.  Byte counts come
+// from pbeg / pend on the host; with the RCCL transport everything is queued on the context's stream.  A block without
+// keys exchanges nothing (every rank knows it).
+int bcd_block_servers(dfh_bcd* o, int at, int zero) {
+  hipStream_t s = o->ctx->stream;
+  const int blk = o->h_order[at];
+  const int pb = o->pbeg[blk], n = o->pend[blk] - pb;
+  if (!n) return DFH_OK;
+  const int W = o->comm->world, r = o->comm->rank;
+  const int lo = o->slice(r, n), hi = o->slice(r + 1, n), own = hi - lo;
+  for (int p = 0; p < W; ++p) {
+    const size_t np = (size_t)(o->slice(p + 1, n) - o->slice(p, n));
+    o->xsb[p] = np * sizeof(double);                       // slice p's partials to rank p
+    o->xso[p] = (size_t)o->slice(p, n) * sizeof(double);
+    o->xrb[p] = (size_t)own * sizeof(double);              // every rank's partials of the own slice
+    o->xsb4[p] = (size_t)own * sizeof(float);              // the own slice's delta w to every rank
+    o->xrb4[p] = np * sizeof(float);                       // every slice's delta w, in position order
+  }
+  const XPart gh[2] = {{o->d_gacc, o->xsb.data(), o->xso.data(), o->d_xg, o->xrb.data(), nullptr},
+                       {o->d_hacc, o->xsb.data(), o->xso.data(), o->d_xh, o->xrb.data(), nullptr}};
+  int rc = comm_exchange(o->comm, gh, 2, nullptr, DFH_XCHG_GRADS);
+  if (rc) return rc;
+  const dim3 grid(bcd::grid_of(n, bcd::THREADS)), block(bcd::THREADS);
+  hipLaunchKernelGGL(bcd::k_bcd_reduce, grid, block, 0, s, o->d_xg, o->d_xh, W, n, lo, own, o->d_gacc, o->d_hacc);
+  if (own) {
+    bcd::UpdArgs u{o->d_order, at, o->d_pbeg, o->d_pend, o->d_gacc, o->d_hacc, o->d_w, o->d_delta, o->d_dw, o->l1, o->lr, zero, lo, hi};
+    hipLaunchKernelGGL(bcd::k_bcd_update, dim3(bcd::grid_of(own, bcd::THREADS)), block, 0, s, u);
+  }
+  DFH_HIP(hipGetLastError());
+  const XPart d{o->d_dw + pb + lo, o->xsb4.data(), o->xzero.data(), o->d_xd, o->xrb4.data(), nullptr};
+  rc = comm_exchange(o->comm, &d, 1, nullptr, DFH_XCHG_ROWS);
+  if (rc) return rc;
+  if (own < n) {
+    hipLaunchKernelGGL(bcd::k_bcd_apply, grid, block, 0, s, o->d_xd, n, lo, hi, pb, o->d_w, o->d_delta, o->d_dw);
+    DFH_HIP(hipGetLastError());
+  }
+  return DFH_OK;
+}
+
+// sharded, dfh_bcd_step's g and h: the owners' reduced slices of block blk gathered into d_xg / d_xh in position order
+int bcd_gather_gh(dfh_bcd* o, int blk) {
+  const int n = o->pend[blk] - o->pbeg[blk];
+  if (!n) return DFH_OK;
+  const int W = o->comm->world, r = o->comm->rank;
+  const int lo = o->slice(r, n), own = o->slice(r + 1, n) - lo;
+  for (int p = 0; p < W; ++p) {
+    o->xsb[p] = (size_t)own * sizeof(double);
+    o->xrb[p] = (size_t)(o->slice(p + 1, n) - o->slice(p, n)) * sizeof(double);
+  }
+  const XPart gh[2] = {{o->d_gacc + lo, o->xsb.data(), o->xzero.data(), o->d_xg, o->xrb.data(), nullptr},
+                       {o->d_hacc + lo, o->xsb.data(), o->xzero.data(), o->d_xh, o->xrb.data(), nullptr}};
+  return comm_exchange(o->comm, gh, 2, nullptr, DFH_XCHG_GRADS);
+}
+
+// sharded, set-up: every rank's n[p] elements of `elem` host bytes to every rank, in rank order; synchronous
+int bcd_allgatherv(dfh_bcd* o, const void* mine, size_t elem, const std::vector<uint64_t>& n, void* all) {
+  const int W = o->comm->world, r = o->comm->rank;
+  hipStream_t s = o->ctx->stream;
+  std::vector<size_t> sb(W, (size_t)n[r] * elem), so(W, 0), rb(W);
+  size_t rt = 0;
+  for (int p = 0; p < W; ++p) rt += rb[p] = (size_t)n[p] * elem;
+  char *d_s = nullptr, *d_r = nullptr;
+  DFH_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), std::max<size_t>(sb[r], 16)));
+  if (hipMalloc(reinterpret_cast<void**>(&d_r), std::max<size_t>(rt, 16)) != hipSuccess) {
+    (void)hipFree(d_s);
+    set_error("dfh_bcd_build: no device memory for the exchange of the ranks' keys");
+    return DFH_ERR_HIP;
+  }
+  int rc = DFH_OK;
+  if (sb[r] && hipMemcpyAsync(d_s, mine, sb[r], hipMemcpyHostToDevice, s) != hipSuccess) rc = DFH_ERR_HIP;
+  const XPart x{d_s, sb.data(), so.data(), d_r, rb.data(), nullptr};
+  if (!rc) rc = comm_exchange(o->comm, &x, 1, nullptr, DFH_XCHG_KEYS);
+  if (!rc && rt && hipMemcpyAsync(all, d_r, rt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = DFH_ERR_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = DFH_ERR_HIP;
+  (void)hipFree(d_s);
+  (void)hipFree(d_r);
+  if (rc == DFH_ERR_HIP) set_error("dfh_bcd_build: the exchange of the ranks' keys failed");
+  return rc;
+}
 
 // one block (order[at]) over every chunk: the gradient over the training chunks, the update, the predictions of every chunk
 int bcd_block(dfh_bcd* o, int at, int zero) {
@@ -462,8 +595,12 @@ int bcd_block(dfh_bcd* o, int at, int zero) {
     hipLaunchKernelGGL(bcd::k_bcd_fixup, dim3(grid), dim3(bcd::THREADS), 0, s, g);
   }
   DFH_HIP(hipGetLastError());
-  if (o->max_keys) {
-    bcd::UpdArgs u{o->d_order, at, o->d_pbeg, o->d_pend, o->d_gacc, o->d_hacc, o->d_w, o->d_delta, o->d_dw, o->l1, o->lr, zero};
+  if (o->comm) {
+    const int rc = bcd_block_servers(o, at, zero);
+    if (rc) return rc;
+  } else if (o->max_keys) {
+    bcd::UpdArgs u{o->d_order, at, o->d_pbeg, o->d_pend, o->d_gacc, o->d_hacc, o->d_w, o->d_delta, o->d_dw, o->l1, o->lr, zero,
+                   0, INT_MAX};
     hipLaunchKernelGGL(bcd::k_bcd_update, dim3(bcd::grid_of(o->max_keys, bcd::THREADS)), dim3(bcd::THREADS), 0, s, u);
   }
   for (auto& cs : o->chunks)
@@ -509,6 +646,12 @@ int bcd_progress(dfh_bcd* o, float* prog) {
       v[3] += correct > 0.5f * n ? correct : n - correct;
       ++i;
     }
+  if (o->comm) {   // the ranks' values added in rank order: the same bits on every rank, with one rank the plain object's
+    double t[4] = {v[0], v[1], v[2], v[3]};
+    const int rc = dfh_comm_allreduce_sum(o->comm, t, 4);
+    if (rc) return rc;
+    for (int k = 0; k < 4; ++k) v[k] = (float)t[k];
+  }
   for (int k = 0; k < 4; ++k) prog[k] = v[k];
   return DFH_OK;
 }
@@ -525,7 +668,8 @@ int bcd_free(dfh_bcd* o) {
   for (auto& cs : o->chunks)
     for (auto& ch : cs) bcd_free_chunk(ch);
   for (void* p : {(void*)o->d_pbeg, (void*)o->d_pend, (void*)o->d_w, (void*)o->d_delta, (void*)o->d_dw, (void*)o->d_gacc,
-                  (void*)o->d_hacc, o->slab_mem, (void*)o->d_order, (void*)o->d_part, (void*)o->d_res})
+                  (void*)o->d_hacc, o->slab_mem, (void*)o->d_order, (void*)o->d_part, (void*)o->d_res, (void*)o->d_xg,
+                  (void*)o->d_xh, (void*)o->d_xd})
     if (p) (void)hipFree(p);
   delete o;
   return DFH_OK;
@@ -662,6 +806,17 @@ int dfh_bcd_create(dfh_ctx* c, dfh_bcd** out) {
   return DFH_OK;
 }
 
+int dfh_bcd_create_sharded(dfh_ctx* c, dfh_comm* comm, dfh_bcd** out) {
+  DFH_ARG(c && comm && out && comm->ctx == c, "dfh_bcd_create_sharded: the context and the communicator must match");
+  DFH_ARG(!comm->loopback, "dfh_bcd_create_sharded: the loop-back transport is for dfh_shard_step measurements only");
+  const int rc = dfh_bcd_create(c, out);
+  if (rc) return rc;
+  (*out)->comm = comm;
+  const size_t W = (size_t)comm->world;
+  for (auto* v : {&(*out)->xsb, &(*out)->xso, &(*out)->xrb, &(*out)->xsb4, &(*out)->xrb4, &(*out)->xzero}) v->assign(W, 0);
+  return DFH_OK;
+}
+
 int dfh_bcd_destroy(dfh_bcd* o) { return bcd_free(o); }
 
 int dfh_bcd_add_chunk(dfh_bcd* o, int is_val, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,
@@ -682,7 +837,7 @@ int dfh_bcd_add_chunk(dfh_bcd* o, int is_val, size_t nrows, const size_t* offset
 int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_t* blk_begin, const uint64_t* blk_end, float l1,
                   float lr, uint64_t* nkeys) {
   DFH_ARG(o && !o->built, "dfh_bcd_build: bad argument or called twice");
-  DFH_ARG(!o->chunks[0].empty(), "dfh_bcd_build: no training chunk");
+  DFH_ARG(o->comm || !o->chunks[0].empty(), "dfh_bcd_build: no training chunk");
   DFH_ARG(nblk >= 0 && (nblk == 0 || (blk_begin && blk_end)), "dfh_bcd_build: bad block ranges");
   for (int b = 0; b < nblk; ++b) {
     DFH_ARG(blk_begin[b] < blk_end[b], "dfh_bcd_build: an empty block range");
@@ -701,6 +856,33 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
     std::vector<uint64_t> tk;
     std::vector<float> tc;
     chunks::merged_counts(train, &tk, &tc);
+    if (o->comm) {
+      // the ranks' (key, count) lists to every rank; a key's counts are added in ascending source rank, so every rank
+      // filters the same global counts and builds the same model
+      const int W = o->comm->world;
+      std::vector<uint64_t> n(W, 0);
+      const uint64_t mine = tk.size();
+      int rc = dfh_comm_allgather(o->comm, &mine, sizeof(mine), n.data());
+      if (rc) return rc;
+      size_t tot = 0;
+      for (int p = 0; p < W; ++p) tot += n[p];
+      std::vector<uint64_t> ak(std::max<size_t>(tot, 1));
+      std::vector<float> ac(std::max<size_t>(tot, 1));
+      rc = bcd_allgatherv(o, tk.data(), sizeof(uint64_t), n, ak.data());
+      if (!rc) rc = bcd_allgatherv(o, tc.data(), sizeof(float), n, ac.data());
+      if (rc) return rc;
+      std::vector<chunks::Resident> parts(W);
+      std::vector<const chunks::Resident*> ranks(W);
+      size_t at = 0;
+      for (int p = 0; p < W; ++p) {
+        parts[p].U = n[p];
+        parts[p].keys.assign(ak.begin() + at, ak.begin() + at + n[p]);
+        parts[p].cnt.assign(ac.begin() + at, ac.begin() + at + n[p]);
+        at += n[p];
+        ranks[p] = &parts[p];
+      }
+      chunks::merged_counts(ranks, &tk, &tc);
+    }
     for (size_t i = 0; i < tk.size(); ++i)
       if (tc[i] > tail_feature_filter) {
         o->keys.push_back(tk[i]);
@@ -723,7 +905,11 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
   // shares bound: the largest block slice of any training chunk is at most the chunk's nnz
   for (auto& ch : o->chunks[0]) max_shares = std::max<size_t>(max_shares, (ch.nnz + bcd::SHARE - 1) / bcd::SHARE + bcd::WAVES);
   o->res_cap = 4 * (o->chunks[0].size() + o->chunks[1].size());
-  const size_t state = K1 * 12 + mk * 16 + max_shares * 40 + B1 * 12 + bcd::PROG_BLOCKS * 16 + o->res_cap * 8 + 4096;
+  // sharded: the staging of the two exchanges, sized for the largest block
+  if (o->comm) o->max_slice = (o->max_keys + o->comm->world - 1) / o->comm->world;
+  const size_t xs = std::max<size_t>((o->comm ? (size_t)o->comm->world : 0) * o->max_slice, mk);
+  const size_t state = K1 * 12 + mk * 16 + max_shares * 40 + B1 * 12 + bcd::PROG_BLOCKS * 16 + o->res_cap * 8 + 4096 +
+                       (o->comm ? xs * 16 + mk * 4 : 0);
   int rc = chunks::check_free(kBcdWho, "the model and the block state", kBcdTail, state);
   if (rc) return rc;
   DFH_HIP(hipMalloc(&o->d_pbeg, B1 * sizeof(int)));
@@ -746,6 +932,11 @@ int dfh_bcd_build(dfh_bcd* o, float tail_feature_filter, int nblk, const uint64_
   DFH_HIP(hipMalloc(&o->d_order, B1 * sizeof(int)));
   DFH_HIP(hipMalloc(&o->d_part, bcd::PROG_BLOCKS * 2 * sizeof(double)));
   DFH_HIP(hipMalloc(&o->d_res, std::max<size_t>(o->res_cap, 4) * sizeof(double)));
+  if (o->comm) {
+    DFH_HIP(hipMalloc(&o->d_xg, xs * sizeof(double)));
+    DFH_HIP(hipMalloc(&o->d_xh, xs * sizeof(double)));
+    DFH_HIP(hipMalloc(&o->d_xd, mk * sizeof(float)));
+  }
   if (nblk) {
     DFH_HIP(hipMemcpyAsync(o->d_pbeg, o->pbeg.data(), nblk * sizeof(int), hipMemcpyHostToDevice, s));
     DFH_HIP(hipMemcpyAsync(o->d_pend, o->pend.data(), nblk * sizeof(int), hipMemcpyHostToDevice, s));
@@ -840,8 +1031,12 @@ int dfh_bcd_step(dfh_bcd* o, int blk, double* g, double* h, float* progress) {
   if (rc) return rc;
   if (keep) {
     const size_t nk = (size_t)(o->pend[blk] - o->pbeg[blk]);
-    if (g && nk) DFH_HIP(hipMemcpyAsync(g, o->d_gacc, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (h && nk) DFH_HIP(hipMemcpyAsync(h, o->d_hacc, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (o->comm) {   // the global sums: the owners' reduced slices, gathered
+      rc = bcd_gather_gh(o, blk);
+      if (rc) return rc;
+    }
+    if (g && nk) DFH_HIP(hipMemcpyAsync(g, o->comm ? o->d_xg : o->d_gacc, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (h && nk) DFH_HIP(hipMemcpyAsync(h, o->comm ? o->d_xh : o->d_hacc, nk * sizeof(double), hipMemcpyDeviceToHost, s));
     DFH_HIP(hipMemsetAsync(o->d_gacc, 0, std::max(o->max_keys, 1) * sizeof(double), s));
     DFH_HIP(hipMemsetAsync(o->d_hacc, 0, std::max(o->max_keys, 1) * sizeof(double), s));
   }

@@ -60,6 +60,7 @@ void FeaGroupStats::Add(size_t nrows, const size_t* offset, const feaid_t* index
 
 BCDLearner::~BCDLearner() {
   if (obj_) dfh_bcd_destroy(obj_);
+  if (comm_) dfh_comm_destroy(comm_);
 }
 
 KWArgs BCDLearner::Init(const KWArgs& kwargs) {
@@ -68,15 +69,40 @@ KWArgs BCDLearner::Init(const KWArgs& kwargs) {
         << "learner = bcd has no prediction task: train with model_out=<file>, then score with "
            "task=predict learner=sgd model_in=<file> V_dim=0 pred_out=<file>";
   const char* nw = getenv("DMLC_NUM_WORKER");
-  CHECK(!IsDistributed() && !(nw && atoi(nw) > 1))
-      << "learner = bcd runs in one process on one GPU: a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is not supported";
+  bool shard_rows = false;
+  for (const auto& kw : kwargs)
+    if (kw.first == "shard_rows") shard_rows = atoi(kw.second.c_str()) != 0;
+  if (shard_rows) {
+    // one process per GPU only with the whole environment of a rank; a scheduler or server role is refused as the
+    // sharded store of learner = sgd refuses it
+    const char* role = getenv("DMLC_ROLE");
+    if (role && std::string(role) != "worker") ReadRankEnv();
+    std::string missing;
+    for (const char* name : {"DMLC_ROLE", "DMLC_NUM_WORKER", "DIFACTO_RANK", "DIFACTO_RENDEZVOUS"})
+      if (!getenv(name)) missing += std::string(missing.size() ? ", " : "") + name;
+    CHECK(missing.empty()) << "learner = bcd shard_rows=1 needs the complete environment of a rank (DMLC_ROLE=worker, "
+                           << "DMLC_NUM_WORKER, DIFACTO_RANK, DIFACTO_RENDEZVOUS): " << missing << " is not set";
+  } else {
+    CHECK(!IsDistributed() && !(nw && atoi(nw) > 1))
+        << "learner = bcd runs in one process on one GPU: a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is not supported";
+  }
   // bcd_learner.cc:15-34: the learner's, then the updater's keys; the loss (logit_delta) and the tile store take none
   auto remain = Learner::Init(kwargs);
   remain = param_.InitAllowUnknown(remain);
   remain = updater_param_.InitAllowUnknown(remain);
   CHECK_EQ(param_.num_feature_group_bits % 4, 0) << "num_feature_group_bits should be 0, 4, 8, ...";
   CHECK(param_.num_feature_group_bits >= 0 && param_.num_feature_group_bits <= 16) << "num_feature_group_bits <= 16";
-  DFH_CALL(dfh_bcd_create(DeviceContext::Get(), &obj_));
+  if (shard_rows) {
+    const RankEnv env = ReadRankEnv();   // before the device context: the rank's device
+    rank_ = env.rank;
+    world_ = env.world;
+    comm_ = ConnectRanks(rank_, world_, &files_, 120.0);
+    LOG(INFO) << "bcd: rank " << rank_ << " of " << world_ << " connected (" << (files_ ? "file transport" : "RCCL")
+              << "): a worker for part " << rank_ << " of the rows and the server of one slice of every block";
+    DFH_CALL(dfh_bcd_create_sharded(DeviceContext::Get(), comm_, &obj_));
+  } else {
+    DFH_CALL(dfh_bcd_create(DeviceContext::Get(), &obj_));
+  }
   return remain;
 }
 
@@ -86,7 +112,7 @@ void BCDLearner::PrepareData(std::vector<real_t>* fea_stats) {
   const size_t chunk_bytes = std::max<size_t>(64, static_cast<size_t>(param_.data_chunk_size));
   bcd::FeaGroupStats stats(param_.num_feature_group_bits);
   auto read = [&](const std::string& uri, int is_val) {
-    Reader reader(uri, param_.data_format, 0, 1, chunk_bytes);
+    Reader reader(uri, param_.data_format, rank_, world_, chunk_bytes);   // part rank_ of world_
     ForEachChunk(&reader, kMaxChunkNnz, [&](size_t r0, size_t r1, const dmlc::RowBlock<feaid_t>& blk) {
       if (!is_val) {
         stats.Add(r1 - r0, blk.offset + r0, blk.index);   // bcd_learner.cc:107
@@ -97,6 +123,18 @@ void BCDLearner::PrepareData(std::vector<real_t>* fea_stats) {
   };
   read(param_.data_in, 0);
   stats.Get(fea_stats);
+  if (comm_) {
+    // every rank's statistics added in rank order (they are counts: the floats of one process reading every row while
+    // they stay below 2^24), so every rank cuts the same blocks
+    LOG(INFO) << "rank " << rank_ << ": " << fea_stats->back() << " training examples in " << chunk_rows_.size() << " chunks";
+    for (size_t i = 0; i < fea_stats->size(); i += 64) {
+      double t[64];
+      const int n = static_cast<int>(std::min<size_t>(64, fea_stats->size() - i));
+      for (int k = 0; k < n; ++k) t[k] = (*fea_stats)[i + k];
+      DFH_CALL(dfh_comm_allreduce_sum(comm_, t, n));
+      for (int k = 0; k < n; ++k) (*fea_stats)[i + k] = static_cast<real_t>(t[k]);
+    }
+  }
   if (param_.data_val.size()) read(param_.data_val, 1);   // bcd_learner.cc:118-129
 }
 
@@ -143,7 +181,7 @@ void BCDLearner::RunScheduler() {
     LL << "epoch: " << epoch << ", objv: " << progress[1] / cnt << ", auc: " << progress[2] / cnt
        << ", acc: " << progress[3] / cnt;
   }
-  if (param_.model_out.size()) SaveModel();
+  if (param_.model_out.size() && rank_ == 0) SaveModel();   // the model is replicated: one file, from rank 0
 }
 
 // model_in: the file's w joined onto the model's keys on the device, the predictions of every chunk rebuilt from it

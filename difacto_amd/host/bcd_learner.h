@@ -16,6 +16,12 @@
  *     path; keys the feature map does not hold are dropped, delta starts at 1 as in a cold run
  *   - a sharded store (DMLC_ROLE / DMLC_NUM_WORKER > 1) is refused with a message; so is task = predict for a caller of
  *     Learner::Create("bcd") (the command line scores a model through learner = sgd's prediction path itself)
+ *   - shard_rows = 1 (default 0) with the complete environment of a rank (DMLC_ROLE=worker, DMLC_NUM_WORKER, DIFACTO_RANK,
+ *     DIFACTO_RENDEZVOUS): one process per GPU.  Every rank reads part rank of the rows, holds the whole model and runs
+ *     this scheduler loop itself on its own RefRand stream (same seed, same block order); the reference's worker and
+ *     server jobs of a block are the stages of dfh_bcd_create_sharded's block step.  The feature-group statistics and
+ *     the progress are summed over the ranks in rank order, so every rank prints the same lines; rank 0 alone writes
+ *     model_out, as one file.  Without the complete environment shard_rows = 1 is refused, naming what is missing.
  */
 #ifndef DIFACTO_HOST_BCD_LEARNER_H_
 #define DIFACTO_HOST_BCD_LEARNER_H_
@@ -23,7 +29,9 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include <memory>
 #include "./bcd_param.h"
+#include "./comm_setup.h"
 #include "difacto/learner.h"
 #include "difacto_hip.h"
 
@@ -90,6 +98,10 @@ class BCDLearner : public Learner {
   BCDLearnerParam param_;
   BCDUpdaterParam updater_param_;
   dfh_bcd* obj_ = nullptr;
+  // shard_rows = 1: this rank's place and the communicator (comm_setup.h)
+  dfh_comm* comm_ = nullptr;
+  std::unique_ptr<FileExchange> files_;
+  int rank_ = 0, world_ = 1;
   std::vector<size_t> chunk_rows_;
   std::vector<std::function<void(int epoch, const std::vector<real_t>& prog)>> epoch_end_callback_;
 };

@@ -2,7 +2,7 @@
  * comm_setup.h — what every multi-GPU learner of this build does before its first exchange: the process environment
  * of one rank (DMLC_ROLE / DMLC_NUM_WORKER / DIFACTO_RANK, the rank's device) and the communicator (DIFACTO_RENDEZVOUS,
  * DIFACTO_COMM=rccl|file: rank 0 writes the RCCL unique id into the rendezvous file, the others read it).  Used by
- * ShardedDeviceStore (learner = sgd) and by LBFGSLearner's sharded mode.
+ * ShardedDeviceStore (learner = sgd) and by the sharded modes of LBFGSLearner and BCDLearner.
  */
 #ifndef DIFACTO_HOST_COMM_SETUP_H_
 #define DIFACTO_HOST_COMM_SETUP_H_

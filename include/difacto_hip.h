@@ -604,6 +604,29 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
  * bytes needed. */
 typedef struct dfh_bcd dfh_bcd;
 int dfh_bcd_create(dfh_ctx* ctx, dfh_bcd** out);
+/* The same learner over the ranks of a communicator (RCCL or host callback; not the loop-back transport): each rank is a
+ * worker for its own chunks (1/N of the rows) and, in every block step, the server of one slice of the block's keys, what
+ * the reference's RunScheduler does with its worker and server groups (src/bcd/bcd_learner.cc:171-315,
+ * bcd_updater.h:138-162).  The model is REPLICATED: every rank holds keys, w, delta and delta w of the whole model (12
+ * bytes per key).  On such an object EVERY dfh_bcd_* call below is COLLECTIVE: every rank makes the same calls in the
+ * same order with the same arguments apart from the chunks (a rank without rows adds no chunk and still takes part).
+ *   build       the ranks exchange the (key, count) lists of their training chunks; a key's counts are added in
+ *               ascending source rank and tail_feature_filter runs on the global counts, so every rank builds the same
+ *               keys, block positions and colmaps (a key of other ranks' rows alone is a model key here too).
+ *   epoch/step  per block, positions [pb, pe), n = pe - pb, slice r = [pb + floor(r n / W), pb + floor((r + 1) n / W)):
+ *               the rank's partial g, h over its own chunks; the partials of slice p to rank p (all-to-all-v, 16 bytes
+ *               per key); k_bcd_reduce adds each owned key's W partials in ascending source rank; the update on the
+ *               owned slice; the slice's delta w to every peer (all-to-all-v, 4 bytes per key); k_bcd_apply stores w,
+ *               delta and delta w of the other slices exactly as the update stored them; the predictions of the rank's
+ *               own chunks.  A rank sends 16 (n - own) + 4 own (W - 1) bytes per block.  No float atomics: the model has
+ *               the same bits on every rank, run and transport, and with one rank the bits of dfh_bcd_create's object.
+ *               With the RCCL transport everything is queued on the context's stream and an epoch synchronises once.
+ *   step's g, h the global sums (the owners' reduced slices, gathered: one more exchange), the same on every rank.
+ *   progress    taken per local chunk, then summed over the ranks in rank order (dfh_comm_allreduce_sum).
+ *   set_model   every rank passes the same input; nothing crosses the wire.
+ * shape, block_info's positions and get_model see the whole model; block_info's entries and rows and get_pred see the
+ * rank's own chunks.  DFH_ERR_CAPACITY applies per rank. */
+int dfh_bcd_create_sharded(dfh_ctx* ctx, dfh_comm* comm, dfh_bcd** out);
 int dfh_bcd_destroy(dfh_bcd* o);
 /* a chunk of raw rows (Reader::Value()), localized on the device with Localizer(-1) (TileBuilder::Add) and kept */
 int dfh_bcd_add_chunk(dfh_bcd* o, int is_val, size_t nrows, const size_t* offset, const uint64_t* index, const float* value,

@@ -12,6 +12,12 @@ achieved TB/s (its bytes over k_bcd_grad + k_bcd_fixup time) against 5 TB/s.
   python tools/bcd_bench.py [--rows 4000000] [--chunk-rows 1000000] [--block-ratio 1] [--epochs 3] [--out FILE]
   python tools/bcd_bench.py --set-model ...   also: ms of dfh_bcd_set_model (model_in's warm start) with a value for every
                                               key of the model, keys shuffled, next to the epoch; the epochs still start cold
+  python tools/bcd_bench.py --ab N            the plain object against a one-rank dfh_bcd_create_sharded object over the RCCL
+                                              transport on the same chunks: N rounds of one epoch each, alternated A B A B in
+                                              this process; ms per epoch of both and whether progress, model and predictions
+                                              agree bit for bit (default --out profiles/bcd_sharded_ab.json).  Per block with
+                                              keys the sharded object adds two self-copies and k_bcd_reduce (k_bcd_apply has
+                                              no key to apply with one rank and is not launched)
   rocprofv3 --kernel-trace --stats -d DIR -o run -- python tools/bcd_bench.py ...
   python tools/bcd_bench.py --stats DIR/.../run_kernel_stats.csv --model FILE
 """
@@ -49,6 +55,58 @@ def kernel_stats(path, model):
     return out
 
 
+def ab(args):
+    """A = capi.Bcd(ctx), B = capi.Bcd(ctx, comm) with one rank over RCCL; the same chunks, the same block orders"""
+    import bcd_ref as R
+    from difacto_amd import capi
+    from difacto_amd.synth import CriteoSynth
+    ctx = capi.Context(0)
+    comm = capi.Comm.rccl(ctx, 0, 1, capi.Comm.unique_id())
+    objs = [capi.Bcd(ctx), capi.Bcd(ctx, comm=comm)]
+    gen = CriteoSynth(total_ids=args.ids, seed=7)
+    sampled, entries, nchunks = 0, 0, 0
+    for r0 in range(0, args.rows, args.chunk_rows):
+        b = gen.batch(min(args.chunk_rows, args.rows - r0))
+        for o in objs:
+            o.add_chunk(b["offset"], b["index"], None, b["label"])
+        s = len(range(0, len(b["label"]), 10))
+        sampled += s
+        entries += 39 * s
+        nchunks += 1
+    st = np.array([entries, sampled, args.rows], np.float32)
+    ranges = R.partition_feature(0, R.block_counts(st, args.block_ratio))
+    nkeys = [o.build(ranges, tail_feature_filter=args.tail_feature_filter, l1=1.0, lr=0.9) for o in objs]
+    stream = R.RefRand()
+    order = list(range(len(ranges)))
+    stream.shuffle(order)
+    for o in objs:
+        o.epoch(order)   # warm
+    ms, same = [[], []], True
+    for _ in range(args.ab):
+        stream.shuffle(order)
+        progs = []
+        for i, o in enumerate(objs):
+            t = time.perf_counter()
+            progs.append(o.epoch(order))
+            ms[i].append(1e3 * (time.perf_counter() - t))
+        same = same and progs[0].tobytes() == progs[1].tobytes()
+    ma, mb = (o.get_model() for o in objs)
+    same = same and all(ma[k].tobytes() == mb[k].tobytes() for k in ma)
+    same = same and all(objs[0].get_pred(i).tobytes() == objs[1].get_pred(i).tobytes() for i in range(nchunks))
+    sent, recv, groups = comm.stats()
+    res = dict(workload="Criteo-shaped synthetic: %d rows x 39 slots, %d ids, no values, chunks of %d rows, block_ratio %g, "
+               "tail_feature_filter %d" % (args.rows, args.ids, args.chunk_rows, args.block_ratio, args.tail_feature_filter),
+               transport=comm.info(), nkeys=nkeys[0], nblk=len(ranges), rounds=args.ab,
+               plain_ms_per_epoch=ms[0], sharded_world1_ms_per_epoch=ms[1],
+               plain_ms_median=float(np.median(ms[0])), sharded_world1_ms_median=float(np.median(ms[1])),
+               bits_agree=bool(same and nkeys[0] == nkeys[1]), wire_bytes_sent=int(sent), exchanges=int(groups))
+    for o in objs:
+        o.close()
+    comm.close()
+    ctx.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4_000_000)
@@ -58,6 +116,7 @@ def main():
     ap.add_argument("--tail-feature-filter", type=int, default=4)
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--set-model", action="store_true")
+    ap.add_argument("--ab", type=int, default=0)
     ap.add_argument("--out")
     ap.add_argument("--stats")
     ap.add_argument("--model")
@@ -67,6 +126,12 @@ def main():
         print(json.dumps(r))
         if args.out:
             open(args.out, "w").write(json.dumps(r) + "\n")
+        return
+    if args.ab:
+        r = ab(args)
+        print(json.dumps(r))
+        out = args.out or os.path.join(ROOT, "profiles", "bcd_sharded_ab.json")
+        open(out, "w").write(json.dumps(r) + "\n")
         return
     import bcd_ref as R
     from difacto_amd import capi
