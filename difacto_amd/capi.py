@@ -41,6 +41,8 @@ SYMBOLS = [
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
     "dfh_bcd_create_sharded",
+    "dfh_textchunk_create", "dfh_textchunk_destroy", "dfh_textchunk_parse_criteo", "dfh_textchunk_rows", "dfh_textchunk_ids",
+    "dfh_rowbuf_load_slices",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -60,6 +62,11 @@ class Progress(C.Structure):
     """sgd::Progress (src/sgd/sgd_utils.h:40-75)"""
     _fields_ = [("loss", C.c_float), ("penalty", C.c_float), ("auc", C.c_float),
                 ("nnz_w", C.c_float), ("nrows", C.c_float)]
+
+
+class Slice(C.Structure):
+    """dfh_slice: host arrays (chunk = NULL), or ids [first, first + nnz) of a parsed text chunk"""
+    _fields_ = [("index", C.c_void_p), ("value", C.c_void_p), ("chunk", C.c_void_p), ("first", C.c_size_t), ("nnz", C.c_size_t)]
 
 
 # dfh_alltoallv_fn: int (*)(void* user, const void* send, const size_t* send_bytes, void* recv, const size_t* recv_bytes)
@@ -158,6 +165,12 @@ def lib():
     L.dfh_rowbuf_destroy.argtypes = [vp]
     L.dfh_rowbuf_load_host.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.dfh_rowbuf_load_host_slices.argtypes = [vp, C.c_size_t, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.dfh_textchunk_create.argtypes = [vp, sz, PP(vp)]
+    L.dfh_textchunk_destroy.argtypes = [vp]
+    L.dfh_textchunk_parse_criteo.argtypes = [vp, vp, sz, i32, PP(i32), PP(sz), PP(sz)]
+    L.dfh_textchunk_rows.argtypes = [vp, vp, vp]
+    L.dfh_textchunk_ids.argtypes = [vp, vp]
+    L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
     L.dfh_rowbuf_set_labels.argtypes = [vp, C.c_size_t, vp]
@@ -548,6 +561,22 @@ class RowBuf:
         cnt = (C.c_size_t * n)(*[len(i) for i in idx])
         _ck(lib().dfh_rowbuf_load_host_slices(self.h, len(offset) - 1, _p(offset), n, ip, vp, cnt))
 
+    def load_slices(self, offset, slices):
+        """dfh_rowbuf_load_slices: the ids as consecutive pieces, each (index, value or None) host arrays or
+        (TextChunk, first, nnz) = ids [first, first + nnz) of a parsed chunk, copied device to device"""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        arr = (Slice * max(len(slices), 1))()
+        keep = []
+        for g, sl in enumerate(slices):
+            if isinstance(sl[0], TextChunk):
+                arr[g] = Slice(None, None, sl[0].h, int(sl[1]), int(sl[2]))
+            else:
+                idx = np.ascontiguousarray(sl[0], np.uint64)
+                val = None if sl[1] is None else np.ascontiguousarray(sl[1], np.float32)
+                keep.append((idx, val))
+                arr[g] = Slice(idx.ctypes.data, None if val is None else val.ctypes.data, None, 0, len(idx))
+        _ck(lib().dfh_rowbuf_load_slices(self.h, len(offset) - 1, _p(offset), len(slices), arr))
+
     def set_labels(self, label):
         """dfh_rowbuf_set_labels: the labels of the loaded rows (a buffer that stays: Batch.prepare_cached)"""
         label = np.ascontiguousarray(label, np.float32)
@@ -556,6 +585,42 @@ class RowBuf:
     def close(self):
         if self.h:
             lib().dfh_rowbuf_destroy(self.h)
+            self.h = None
+
+
+class TextChunk:
+    """one chunk of criteo text parsed on the device (dfh_textchunk): its ids stay in HBM"""
+
+    def __init__(self, ctx, max_bytes=1 << 16):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _ck(lib().dfh_textchunk_create(ctx.h, max_bytes, C.byref(self.h)))
+
+    def parse_criteo(self, text, is_train=True, address=None):
+        """-> None when the chunk is not regular (the caller parses it on the host), else (offset u32 [nrows + 1], label
+        [nrows], nnz).  `address`: parse len(text) bytes at that address instead of a copy of `text`"""
+        buf = None
+        if address is None:
+            buf = C.create_string_buffer(bytes(text), len(text)) if len(text) else C.create_string_buffer(1)
+            address = C.addressof(buf)
+        reg, nrows, nnz = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        _ck(lib().dfh_textchunk_parse_criteo(self.h, C.c_void_p(address), len(text), 1 if is_train else 0, C.byref(reg), C.byref(nrows),
+                                             C.byref(nnz)))
+        if not reg.value:
+            return None
+        off = np.zeros(nrows.value + 1, np.uint32)
+        lab = np.zeros(max(nrows.value, 1), np.float32)
+        _ck(lib().dfh_textchunk_rows(self.h, _p(off), _p(lab)))
+        return off, lab[:nrows.value], nnz.value
+
+    def ids(self, nnz):
+        out = np.zeros(max(nnz, 1), np.uint64)
+        _ck(lib().dfh_textchunk_ids(self.h, _p(out)))
+        return out[:nnz]
+
+    def close(self):
+        if self.h:
+            lib().dfh_textchunk_destroy(self.h)
             self.h = None
 
 

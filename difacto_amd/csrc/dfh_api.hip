@@ -31,6 +31,8 @@ struct dfh_ctx {
   // prepared take them round-robin while an earlier batch trains on `stream`
   std::vector<hipStream_t> preps;
   std::vector<hipStream_t> extra;  // other streams that carry work on this context's tables (a shard's collectives stream): drained by sync_all
+  hipStream_t parse = nullptr;     // the device text parse (dfh_textparse.hip): one stream for all of a context's chunks, created with the first
+  std::mutex parse_mu;
   unsigned nprep = 0;       // streams in use (0: pipelining off, everything on `stream`)
   unsigned next_prep = 0;
   bool pipeline = false;
@@ -1092,6 +1094,10 @@ int dfh_ctx_destroy(dfh_ctx* c) {
   for (hipStream_t p : c->preps) {
     hipStreamSynchronize(p);
     hipStreamDestroy(p);
+  }
+  if (c->parse) {
+    hipStreamSynchronize(c->parse);
+    hipStreamDestroy(c->parse);
   }
   if (c->own_stream) hipStreamDestroy(c->stream);
   delete c;
@@ -2387,6 +2393,7 @@ int dfh_batch_destroy(dfh_batch* b) {
 
 }  // extern "C"
 
+#include "dfh_textparse.hip"   // the device text parse: chunks whose ids the feed's uploads take device to device
 #include "dfh_feed.hip"   // the device feed, and the staging helpers the load calls below share with it
 
 extern "C" {

@@ -100,11 +100,12 @@ __global__ void k_fill_f32(float* __restrict__ p, size_t n, float v) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// The body of both uploads: `offset` [nrows + 1] are the buffer's own (cumulative) offsets, the ids / values arrive as
-// `nslices` pieces that follow one another (slice g: nnz_of[g] ids at index[g], values at value[g]; with has_value, a slice
-// without a value array holds ones).  One copy per piece, straight out of the caller's arrays, which are free on return.
-int rowbuf_upload(const char* name, dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const uint64_t* const* index,
-                  const float* const* value, const size_t* nnz_of, bool has_value) {
+// The body of the uploads: `offset` [nrows + 1] are the buffer's own (cumulative) offsets, the ids / values arrive as
+// `nslices` pieces that follow one another (slice g: nnz ids at index, values at value; with has_value, a slice without a
+// value array holds ones; a slice that names a parsed text chunk takes its ids from [first, first + nnz) of the chunk's ids
+// in HBM, which dfh_textchunk_parse_criteo has completed).  One copy per piece, straight out of the caller's arrays, which
+// are free on return.
+int rowbuf_upload(const char* name, dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const dfh_slice* slices, bool has_value) {
   const size_t base = offset[0], nnz = offset[nrows] - base;
   DFH_HIP(hipSetDevice(rb->ctx->device));
   {
@@ -127,11 +128,16 @@ int rowbuf_upload(const char* name, dfh_rowbuf* rb, size_t nrows, const size_t* 
   DFH_HIP(hipMemcpyAsync(rb->d_off, rb->off32.data(), (nrows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, rb->up));
   size_t at = 0;
   for (int g = 0; g < nslices; ++g) {
-    const size_t n = nnz_of[g];
+    const dfh_slice& sl = slices[g];
+    const size_t n = sl.nnz;
     if (!n) continue;
-    DFH_HIP(hipMemcpyAsync(rb->d_idx + at, index[g], n * sizeof(uint64_t), hipMemcpyHostToDevice, rb->up));
-    if (has_value && value[g]) {
-      DFH_HIP(hipMemcpyAsync(rb->d_val + at, value[g], n * sizeof(float), hipMemcpyHostToDevice, rb->up));
+    if (sl.chunk) {
+      DFH_HIP(hipMemcpyAsync(rb->d_idx + at, sl.chunk->d_ids + sl.first, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, rb->up));
+    } else {
+      DFH_HIP(hipMemcpyAsync(rb->d_idx + at, sl.index, n * sizeof(uint64_t), hipMemcpyHostToDevice, rb->up));
+    }
+    if (has_value && !sl.chunk && sl.value) {
+      DFH_HIP(hipMemcpyAsync(rb->d_val + at, sl.value, n * sizeof(float), hipMemcpyHostToDevice, rb->up));
     } else if (has_value) {
       hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, rb->up, rb->d_val + at, n, 1.0f);
       DFH_HIP(hipGetLastError());
@@ -454,9 +460,8 @@ int dfh_rowbuf_load_host(dfh_rowbuf* rb, size_t nrows, const size_t* offset, con
   DFH_ARG(nnz <= rb->max_nnz, "dfh_rowbuf_load_host: more nonzeros than the buffer holds");
   DFH_ARG(nnz == 0 || index, "dfh_rowbuf_load_host: index is NULL");
   // one slice; without a value array the buffer has no values (the gather reads its rows as ones)
-  const uint64_t* idx = nnz ? index + base : nullptr;
-  const float* val = value ? value + base : nullptr;
-  return rowbuf_upload("dfh_rowbuf_load_host", rb, nrows, offset, 1, &idx, &val, &nnz, value != nullptr);
+  const dfh_slice sl{nnz ? index + base : nullptr, value ? value + base : nullptr, nullptr, 0, nnz};
+  return rowbuf_upload("dfh_rowbuf_load_host", rb, nrows, offset, 1, &sl, value != nullptr);
 }
 
 // dfh_rowbuf_load_host for a buffer that was never assembled on the host: the buffer has values iff one of its slices has
@@ -468,13 +473,39 @@ int dfh_rowbuf_load_host_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offs
   DFH_ARG(nnz <= rb->max_nnz, "dfh_rowbuf_load_host_slices: more nonzeros than the buffer holds");
   size_t total = 0;
   bool any_value = false;
+  std::vector<dfh_slice> slices((size_t)nslices);
   for (int g = 0; g < nslices; ++g) {
     DFH_ARG(nnz_of[g] == 0 || index[g], "dfh_rowbuf_load_host_slices: a slice without ids");
     total += nnz_of[g];
     any_value = any_value || (nnz_of[g] && value[g]);
+    slices[g] = dfh_slice{index[g], value[g], nullptr, 0, nnz_of[g]};
   }
   DFH_ARG(total == nnz, "dfh_rowbuf_load_host_slices: the slices must hold the buffer's nonzeros");
-  return rowbuf_upload("dfh_rowbuf_load_host_slices", rb, nrows, offset, nslices, index, value, nnz_of, any_value);
+  return rowbuf_upload("dfh_rowbuf_load_host_slices", rb, nrows, offset, nslices, slices.data(), any_value);
+}
+
+// dfh_rowbuf_load_host_slices where a slice may name the ids of a parsed text chunk (dfh_textparse.hip) instead of host arrays:
+// those are copied device to device on the buffer's stream; such a slice has no values (ones beside slices with values)
+int dfh_rowbuf_load_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const dfh_slice* slices) {
+  DFH_ARG(rb && offset && nrows >= 1 && nrows <= rb->max_rows, "dfh_rowbuf_load_slices: bad argument / more rows than the buffer holds");
+  DFH_ARG(nslices >= 0 && (nslices == 0 || slices), "dfh_rowbuf_load_slices: NULL slice array");
+  const size_t nnz = offset[nrows] - offset[0];
+  DFH_ARG(nnz <= rb->max_nnz, "dfh_rowbuf_load_slices: more nonzeros than the buffer holds");
+  size_t total = 0;
+  bool any_value = false;
+  for (int g = 0; g < nslices; ++g) {
+    const dfh_slice& sl = slices[g];
+    if (sl.chunk) {
+      DFH_ARG(sl.chunk->ctx == rb->ctx && sl.chunk->valid && sl.first <= sl.chunk->nnz && sl.nnz <= sl.chunk->nnz - sl.first,
+              "dfh_rowbuf_load_slices: a slice beyond the ids of its parsed chunk (or of a chunk that was not regular)");
+    } else {
+      DFH_ARG(sl.nnz == 0 || sl.index, "dfh_rowbuf_load_slices: a slice without ids");
+      any_value = any_value || (sl.nnz && sl.value);
+    }
+    total += sl.nnz;
+  }
+  DFH_ARG(total == nnz, "dfh_rowbuf_load_slices: the slices must hold the buffer's nonzeros");
+  return rowbuf_upload("dfh_rowbuf_load_slices", rb, nrows, offset, nslices, slices, any_value);
 }
 
 // The labels of the rows a row buffer holds (after dfh_rowbuf_load_host / _slices, same thread): with them — and its own

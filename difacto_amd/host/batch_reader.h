@@ -49,7 +49,31 @@
 
 namespace difacto {
 
-typedef dmlc::data::RowBlockContainer<feaid_t> RowChunk;
+/*! \brief the rows of one parsed chunk.  A chunk parsed on the device (ParseHook) keeps its ids there: offset and label are
+ * filled, index stays empty, and `dev` names the ids (on_device).  `dev` travels with the container through swaps and the
+ * reader's pool, so the device-side arrays are reused like the host-side ones */
+struct RowChunk : public dmlc::data::RowBlockContainer<feaid_t> {
+  std::shared_ptr<void> dev;   // opaque to this header: whoever installs the hook owns its meaning
+  bool on_device = false;
+  void Clear() {
+    dmlc::data::RowBlockContainer<feaid_t>::Clear();
+    on_device = false;
+  }
+};
+
+/*! \brief view of a row container; a described minibatch (and a chunk whose ids are on the device) has offsets and labels but
+ * no index / value arrays */
+inline dmlc::RowBlock<feaid_t> ViewOf(const RowChunk& c) {
+  if (!c.index.empty() || c.offset.back() == 0) return c.GetBlock();
+  dmlc::RowBlock<feaid_t> b;
+  b.size = c.offset.size() - 1;
+  b.offset = c.offset.data();
+  b.label = c.label.empty() ? nullptr : c.label.data();
+  b.weight = nullptr;
+  b.index = nullptr;
+  b.value = nullptr;
+  return b;
+}
 
 /*! \brief a parser yields the rows of its part of the file chunk by chunk, in two stages so that the
  * expensive one can run on several threads: Fetch (sequential, file order) and Parse (a pure function
@@ -62,6 +86,11 @@ struct RawChunk {
   std::string own;
   void Own() { data = own.data(); size = own.size(); }
 };
+
+/*! \brief a parse of a fetched chunk that runs somewhere else (the SGD learner's text_parse = device installs one): true =
+ * *out holds the chunk's rows; false = not taken, the chunk's own parser runs as if there were no hook.  Called on the
+ * parser threads, like ChunkParser::Parse */
+typedef std::function<bool(const RawChunk& raw, RowChunk* out)> ParseHook;
 
 class ChunkParser {
  public:
@@ -648,7 +677,8 @@ class CrbRecordParser : public ChunkParser {
 class Reader {
  public:
   Reader(const std::string& uri, const std::string& format, unsigned part, unsigned nparts, size_t chunk_bytes = 1 << 24,
-         int nthreads = 0) {
+         int nthreads = 0, ParseHook hook = nullptr)
+      : hook_(hook) {
     if (const char* e = getenv("DIFACTO_CHUNK_BYTES")) chunk_bytes = std::max<size_t>(64, strtoull(e, nullptr, 10));  // text formats
     if (format == "libsvm") {
       parser_.reset(new LibsvmChunkParser(uri, part, nparts, chunk_bytes));
@@ -720,7 +750,7 @@ class Reader {
       lk.unlock();
       cv_.notify_all();
       if (cur_.Size() == 0) continue;  // a chunk of comment / empty lines
-      blk_ = cur_.GetBlock();
+      blk_ = ViewOf(cur_);
       return true;
     }
   }
@@ -747,7 +777,7 @@ class Reader {
       pool->spare.emplace_back(p);
     });
     std::swap(*c, cur_);   // cur_ (and through it a parser's slot) gets the recycled storage
-    blk_ = c->GetBlock();
+    blk_ = ViewOf(*c);
     *out = std::move(c);
     return true;
   }
@@ -785,7 +815,7 @@ class Reader {
         s->seq = fetched_++;
       }
       const auto p0 = std::chrono::steady_clock::now();
-      parser_->Parse(s->raw, &s->rows);
+      if (!(hook_ && hook_(s->raw, &s->rows))) parser_->Parse(s->raw, &s->rows);
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count();
       {
         std::lock_guard<std::mutex> lk(mu_);
@@ -796,6 +826,7 @@ class Reader {
     }
   }
   std::unique_ptr<ChunkParser> parser_;
+  ParseHook hook_;
   std::vector<std::thread> workers_;
   std::mutex mu_;
   std::condition_variable cv_;
@@ -821,23 +852,13 @@ struct RowSeg {
 struct BufSlice {
   std::shared_ptr<RowChunk> chunk;
   size_t row0, nrows;
-  const feaid_t* index() const { return chunk->index.data() + chunk->offset[row0]; }
+  const feaid_t* index() const { return chunk->on_device ? nullptr : chunk->index.data() + chunk->offset[row0]; }
+  /*! \brief the chunk's ids are on the device: its handle (RowChunk::dev), the slice's ids are [first(), first() + nnz()) there */
+  void* device() const { return chunk->on_device ? chunk->dev.get() : nullptr; }
+  size_t first() const { return chunk->offset[row0]; }
   const real_t* value() const { return chunk->value.empty() ? nullptr : chunk->value.data() + chunk->offset[row0]; }
   size_t nnz() const { return chunk->offset[row0 + nrows] - chunk->offset[row0]; }
 };
-
-/*! \brief view of a row container; a described minibatch has offsets and labels but no index / value arrays */
-inline dmlc::RowBlock<feaid_t> ViewOf(const RowChunk& c) {
-  if (!c.index.empty() || c.offset.back() == 0) return c.GetBlock();
-  dmlc::RowBlock<feaid_t> b;
-  b.size = c.offset.size() - 1;
-  b.offset = c.offset.data();
-  b.label = c.label.empty() ? nullptr : c.label.data();
-  b.weight = nullptr;
-  b.index = nullptr;
-  b.value = nullptr;
-  return b;
-}
 
 /*! \brief anything that hands out row blocks one after another (BatchReader, and the thread that runs one ahead) */
 class BatchSource {
@@ -1025,16 +1046,19 @@ class BatchReader : public BatchSource {
    *  assembled on the host — offsets and labels only, the ids / values stay in the parsed chunks.  `on_built`, if given, is
    *  called for every buffer (serial 1, 2, ..) on the thread that builds the buffers, as soon as the buffer exists — one
    *  buffer AHEAD of the one being cut into minibatches: where the device feed starts its upload, so that the copy
-   *  is over when the first minibatch of the buffer wants its rows */
+   *  is over when the first minibatch of the buffer wants its rows.  `parse_hook` (with slice_buffers only: a chunk it takes
+   *  may keep its ids on the device, BufSlice::device()) and `parser_threads` (> 0: that many) go to the file's Reader */
   BatchReader(const std::string& uri, const std::string& format, unsigned part_index, unsigned num_parts, unsigned batch_size,
               unsigned shuffle_buf_size = 0, float neg_sampling = 1.0f, bool slice_buffers = false, SliceFn on_built = nullptr,
-              bool permute = true)
+              bool permute = true, ParseHook parse_hook = nullptr, int parser_threads = 0)
       : batch_size_(batch_size), shuf_buf_(shuffle_buf_size), neg_sampling_(neg_sampling), permute_(permute) {
     CHECK_GT(batch_size, 0u);
+    CHECK(!parse_hook || slice_buffers || !shuf_buf_) << "a parse hook's chunks are read as slices: slice_buffers";
     if (shuf_buf_) {
       CHECK_GE(shuf_buf_, batch_size_);
       // the next shuffle buffer is assembled (on its own thread) while this one is being cut into minibatches
-      BatchReader* inner = new BatchReader(uri, format, part_index, num_parts, shuf_buf_);
+      BatchReader* inner = new BatchReader(uri, format, part_index, num_parts, shuf_buf_, 0, 1.0f, false, nullptr, true, parse_hook,
+                                           parser_threads);
       inner->keep_slices_ = slice_buffers;
       inner->on_built_ = on_built;
       sliced_ = slice_buffers;
@@ -1043,7 +1067,7 @@ class BatchReader : public BatchSource {
       buf_reader_.reset(new PrefetchSource(inner, slice_buffers ? 2 : 1));
     } else {
       CHECK(!slice_buffers) << "slice_buffers needs a shuffle buffer";
-      reader_.reset(new Reader(uri, format, part_index, num_parts, 1 << 24));
+      reader_.reset(new Reader(uri, format, part_index, num_parts, 1 << 24, parser_threads, parse_hook));
     }
   }
 

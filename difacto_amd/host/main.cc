@@ -82,6 +82,11 @@ int main(int argc, char* argv[]) {
   for (int i = 1; i < argc; ++i) parser.AddArg(argv[i]);
   DifactoParam param;
   auto kwargs_remain = param.InitAllowUnknown(parser.GetKWArgs());
+  // text_parse = device is a key of learner = sgd's device feed: the other learners would only warn about a key they do not know
+  for (const auto& kw : kwargs_remain)
+    CHECK(!(kw.first == "text_parse" && kw.second == "device" && param.learner != "sgd"))
+        << "text_parse=device with learner=" << param.learner << ": only learner=sgd reads its training data through the device "
+           "feed, whose text the device parses; leave text_parse out";
   if (param.task == "train") {
     Learner* learner = Learner::Create(param.learner);
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));

@@ -7,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -54,6 +55,26 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
       CHECK(!(kv.first == "device_path" && kv.second == "literal"))
           << "data_cache=hbm with device_path=literal: the literal loop hands host arrays to Store and Loss, only "
              "device_path=fused gathers its minibatches out of device row buffers";
+  }
+  // text_parse: checked before anything touches the device, like data_cache.  "device" is accepted only where the device feed
+  // reads the training data (IterateDataFused); validation and prediction readers outside the feed keep the host parser
+  for (const auto& kv : remain) {
+    if (kv.first != "text_parse") continue;
+    CHECK(kv.second == "host" || kv.second == "device")
+        << "text_parse=" << kv.second << " is not one of host (the default) and device";
+    if (kv.second != "device") continue;
+    CHECK(param_.data_format == "criteo" || param_.data_format == "criteo_test")
+        << "text_parse=device with data_format=" << param_.data_format << ": the device parses criteo and criteo_test text only "
+           "(libsvm and adfea need the host's number parsing, rec is not text)";
+    CHECK(!IsDistributed()) << "text_parse=device with a sharded store (DMLC_ROLE is set): the sharded worker loop does not read "
+                               "through the device feed; run one process, or leave text_parse out";
+    for (const auto& kw : remain)
+      CHECK(!(kw.first == "device_path" && kw.second == "literal"))
+          << "text_parse=device with device_path=literal: the literal loop hands host arrays to Store and Loss, only "
+             "device_path=fused reads its minibatches out of device row buffers";
+    CHECK(param_.shuffle > 0 || param_.data_cache == "hbm" || param_.task == "predict")
+        << "text_parse=device without a shuffle buffer: training data goes through the device feed only with shuffle > 0 or "
+           "data_cache=hbm; set one of them, or leave text_parse out";
   }
   auto updater = new DeviceSGDUpdater();
   remain = updater->Init(remain);
@@ -225,6 +246,10 @@ void SGDLearner::IterateData(const sgd::Job& job, sgd::Progress* prog) {
 }
 
 namespace {
+// parser threads of a reader whose chunks the device parses (text_parse = device): a thread uploads a chunk and waits for
+// the device, so a few keep the copy of one chunk beside the kernels of another
+constexpr int kDeviceParseThreads = 3;
+
 // Device feed: the reader's shuffle buffers in HBM.  The reader thread uploads every buffer once, when it becomes current
 // (BatchReader::Describe), into a device row buffer; the worker loop then sends 4 B per row of a minibatch and the rows are
 // gathered on the device (dfh_batch_gather_rows) instead of being copied twice on the host (into the minibatch, into the
@@ -417,7 +442,16 @@ struct DeviceFeed {
       val[g] = slices[g].value();
       cnt[g] = slices[g].nnz();
     }
-    DFH_CALL(dfh_rowbuf_load_host_slices(rb, nrows, j.offset.data(), static_cast<int>(slices.size()), idx.data(), val.data(), cnt.data()));
+    bool any_device = false;
+    for (const BufSlice& sl : slices) any_device = any_device || sl.device() != nullptr;
+    if (any_device) {   // text_parse = device: those slices' ids are in HBM already
+      std::vector<dfh_slice> mixed(slices.size());
+      for (size_t g = 0; g < slices.size(); ++g)
+        mixed[g] = dfh_slice{idx[g], val[g], static_cast<dfh_textchunk*>(slices[g].device()), slices[g].first(), cnt[g]};
+      DFH_CALL(dfh_rowbuf_load_slices(rb, nrows, j.offset.data(), static_cast<int>(mixed.size()), mixed.data()));
+    } else {
+      DFH_CALL(dfh_rowbuf_load_host_slices(rb, nrows, j.offset.data(), static_cast<int>(slices.size()), idx.data(), val.data(), cnt.data()));
+    }
     if (keep) DFH_CALL(dfh_rowbuf_set_labels(rb, nrows, j.label.data()));
     {
       std::lock_guard<std::mutex> lk(mu);
@@ -514,6 +548,10 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   // minibatches are cut (permutation + row selection) two ahead on the reader's own thread, the reference's reader /
   // executor overlap (sgd_learner.cc:196-224).  Training with a shuffle buffer: the buffers go to HBM and the rows are
   // gathered there (device feed; DIFACTO_HOST_FEED=1 keeps the host-side gather)
+  // text_parse = device: the reader's parser threads hand every chunk of criteo text to the device (dfh_textchunk_parse_criteo:
+  // upload, parse, 8 B per row back); the ids stay in HBM with the chunk's container and DeviceFeed::DoUpload copies them
+  // device to device.  A chunk that is not regular is left to the host parser (counted: logged at the end of the job)
+  std::atomic<size_t> tp_chunks{0}, tp_fallback{0};
   DeviceFeed feed;   // outlives the reader, whose thread uploads into it
   feed.ctx = ctx;
   const bool device_feed = feed_wanted;
@@ -534,12 +572,45 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
     upload = [&feed](const dmlc::RowBlock<feaid_t>& blk, const std::vector<BufSlice>& slices, uint64_t serial) {
       feed.Upload(blk, slices, serial);
     };
+  const bool criteo = param_.data_format == "criteo" || param_.data_format == "criteo_test";
+  const bool device_parse = GetUpdater()->device_param().text_parse == "device" && device_feed && !cpart && criteo;
+  ParseHook parse_hook;
+  if (device_parse) {
+    const int is_train_format = param_.data_format == "criteo" ? 1 : 0;
+    parse_hook = [ctx, is_train_format, &tp_chunks, &tp_fallback](const RawChunk& raw, RowChunk* out) {
+      if (!out->dev) {   // (the container comes out of the reader's pool: its device-side arrays are reused like its vectors)
+        dfh_textchunk* tc = nullptr;
+        DFH_CALL(dfh_textchunk_create(ctx, std::max<size_t>(raw.size, 1), &tc));
+        out->dev = std::shared_ptr<void>(tc, [](void* p) { dfh_textchunk_destroy(static_cast<dfh_textchunk*>(p)); });
+      }
+      dfh_textchunk* tc = static_cast<dfh_textchunk*>(out->dev.get());
+      int regular = 0;
+      size_t nrows = 0, nnz = 0;
+      DFH_CALL(dfh_textchunk_parse_criteo(tc, raw.data, raw.size, is_train_format, &regular, &nrows, &nnz));
+      ++tp_chunks;
+      if (!regular) {
+        ++tp_fallback;
+        return false;
+      }
+      static thread_local std::vector<uint32_t> off32;
+      off32.resize(nrows + 1);
+      out->Clear();
+      out->label.resize(nrows);
+      DFH_CALL(dfh_textchunk_rows(tc, off32.data(), out->label.data()));
+      out->offset.assign(off32.begin(), off32.end());
+      out->on_device = true;
+      return true;
+    };
+  }
+  // the device parses: the parser threads only upload and wait (kDeviceParseThreads; DIFACTO_PARSER_THREADS overrides)
+  const int parser_threads = device_parse && getenv("DIFACTO_PARSER_THREADS") == nullptr ? kDeviceParseThreads : 0;
   // device feed: buffers as slices of the parsed chunks (no host assembly), uploaded by the thread that builds them
   BatchReader* batch_reader =
       cpart ? new BatchReader(new CachedBuffers(cpart), param_.batch_size, cache_buf_rows, train ? param_.neg_sampling : 1.0f, permute)
             : new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
                               cache_fill ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0),
-                              train ? param_.neg_sampling : 1.0f, device_feed, upload, cache_fill ? permute : true);
+                              train ? param_.neg_sampling : 1.0f, device_feed, upload, cache_fill ? permute : true, parse_hook,
+                              parser_threads);
   if (device_feed && !cpart) batch_reader->DescribeSlices(nullptr);
   // described minibatches are ~120 KB each: a deeper queue lets the loop ride out the reader's pause at a buffer boundary
   PrefetchSource reader(batch_reader, device_feed ? kFusedBatches : 2);
@@ -698,6 +769,13 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   }
   uint64_t nkeys;
   DFH_CALL(dfh_table_size(table, &nkeys));  // surfaces a full table as an error
+  if (device_parse) {
+    const size_t nf = tp_fallback.load(), nc = tp_chunks.load();
+    LOG(INFO) << "text_parse=device: " << nc - nf << " of " << nc << " chunks of " << JobData(job) << " parsed on the device, " << nf
+              << " fell back to the host parser";
+    if (nf) LOG(WARNING) << "text_parse=device: " << nf << " of " << nc << " chunks are not made of regular rows alone (CRLF, blank lines, "
+                            "odd labels or field lengths) and were parsed on the host";
+  }
   if (cache_on) {   // one line per job: where its rows came from
     const std::string what = "part " + std::to_string(job.part_idx) + " of " + std::to_string(job.num_parts) +
                              (train ? " (training): " : " (validation): ");

@@ -98,7 +98,13 @@ struct DeviceParam : public dmlc::Parameter<DeviceParam> {
   /*! \brief ids per row the device feed's row buffers and batch objects are first sized for (the criteo rows of the
    *  reference's example have 39); data with more ids per row re-creates them at the size it needs */
   int feed_ids_per_row;
+  /*! \brief where data_format = criteo / criteo_test text is parsed for the device feed of the fused SGD loop: "host" (default:
+   *  the parser threads) or "device" (csrc/dfh_textparse.hip: the text is uploaded, the ids never visit the host; a chunk
+   *  that is not made of regular rows alone is still parsed on the host).  SGDLearner::Init refuses "device" wherever the
+   *  training data is not read through the device feed */
+  std::string text_parse;
   DMLC_DECLARE_PARAMETER(DeviceParam) {
+    DMLC_DECLARE_FIELD(text_parse).set_default("host");
     DMLC_DECLARE_FIELD(feed_ids_per_row).set_range(1, 1 << 20).set_default(48);
     DMLC_DECLARE_FIELD(shard_ranges).set_default("balanced");
     DMLC_DECLARE_FIELD(shard_exchange).set_default("overlap");

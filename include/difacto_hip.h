@@ -266,6 +266,34 @@ int dfh_rowbuf_load_host(dfh_rowbuf* rb, size_t nrows, const size_t* offset, con
  * out of the parser's chunks (round 4: assembling 31 MB per buffer on one host thread was what the worker loop waited for) */
 int dfh_rowbuf_load_host_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const uint64_t* const* index,
                                 const float* const* value, const size_t* nnz);
+/* Device text parse (the SGD learner's text_parse = device).  A dfh_textchunk is one parsed chunk of criteo text: the text and
+ * its delimiter positions in HBM, the ids in HBM, the rows' offsets and labels on the host.  dfh_textchunk_parse_criteo uploads
+ * `len` bytes of `text` (data_format = criteo: is_train = 1, criteo_test: 0), parses them on the device and returns when the
+ * host-side results are there.  *regular = 1: the chunk is made of regular rows only (it is non-empty, ends with '\n' and holds
+ * no '\r'; no empty line; every line has 39 / 38 tabs; the label is one character '0'..'9'; an integer field has 0 .. 16 bytes;
+ * a categorical field 0 bytes, or 8 that do not start with ' ', '\v' or '\f') and *nrows, *nnz, the offsets, labels and ids are
+ * CriteoParser::ParseNext's (src/reader/criteo_parser.h:40-94), bit for bit.  *regular = 0 is not an error: nothing else is
+ * valid and the caller parses the chunk on the host.  The object's arrays grow to what a chunk needs (max_bytes: the text
+ * buffer's first size; a chunk has fewer than 2^31 bytes); all chunks of a context share one stream, a call waits for its
+ * own work only, and calls on different objects may run on different threads.  dfh_textchunk_rows: the host copies
+ * (offset [nrows + 1], label [nrows]); dfh_textchunk_ids: the ids [nnz] copied back (tests). */
+typedef struct dfh_textchunk dfh_textchunk;
+int dfh_textchunk_create(dfh_ctx* ctx, size_t max_bytes, dfh_textchunk** out);
+int dfh_textchunk_destroy(dfh_textchunk* tc);
+int dfh_textchunk_parse_criteo(dfh_textchunk* tc, const char* text, size_t len, int is_train, int* regular, size_t* nrows, size_t* nnz);
+int dfh_textchunk_rows(dfh_textchunk* tc, uint32_t* offset, float* label);
+int dfh_textchunk_ids(dfh_textchunk* tc, uint64_t* index);
+/* dfh_rowbuf_load_host_slices whose slices are either host arrays (chunk = NULL; value may be NULL = all ones) or ids
+ * [first, first + nnz) of a regular parsed chunk (index and value unused; no values), copied device to device on the
+ * buffer's stream.  Same contract: it returns when the sources may be reused (the chunk may be parsed into again). */
+typedef struct {
+  const uint64_t* index;
+  const float* value;
+  dfh_textchunk* chunk;
+  size_t first;
+  size_t nnz;
+} dfh_slice;
+int dfh_rowbuf_load_slices(dfh_rowbuf* rb, size_t nrows, const size_t* offset, int nslices, const dfh_slice* slices);
 int dfh_batch_gather_rows(dfh_batch* b, size_t nrows, const size_t* offset, const float* label, int nseg, dfh_rowbuf* const* bufs,
                           const uint32_t* const* rows, const size_t* seg_rows);
 /* dfh_batch_gather_rows + dfh_localize + dfh_batch_lookup as ONE preparation phase — what a worker loop queues per
