@@ -37,7 +37,7 @@ SYMBOLS = [
     "dfh_vec_inner_multi", "dfh_vec_combine", "dfh_vec_line_step", "dfh_lbfgs_create", "dfh_lbfgs_destroy", "dfh_lbfgs_add_chunk",
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
     "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate", "dfh_lbfgs_create_sharded",
-    "dfh_lbfgs_owned_range", "dfh_lbfgs_set_model", "dfh_bcd_set_model",
+    "dfh_lbfgs_owned_range", "dfh_lbfgs_set_model", "dfh_lbfgs_get_vector", "dfh_bcd_set_model",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
     "dfh_bcd_create_sharded",
@@ -249,6 +249,7 @@ def lib():
     L.dfh_lbfgs_calc_direction.argtypes = [vp, vp, PP(f32)]
     L.dfh_lbfgs_line_search.argtypes = [vp, f32, f32, PP(f32), PP(f32), PP(f32)]
     L.dfh_lbfgs_evaluate.argtypes = [vp, PP(f32), PP(f32), PP(f32)]
+    L.dfh_lbfgs_get_vector.argtypes = [vp, i32, i32, vp]
     L.dfh_bcd_create.argtypes = [vp, PP(vp)]
     L.dfh_bcd_create_sharded.argtypes = [vp, vp, PP(vp)]
     L.dfh_bcd_destroy.argtypes = [vp]
@@ -938,6 +939,12 @@ class Lbfgs:
         va, nnz, r = C.c_float(0), C.c_float(0), C.c_float(0)
         _ck(lib().dfh_lbfgs_evaluate(self.h, C.byref(va) if val else None, C.byref(nnz), C.byref(r)))
         return (va.value if val else None), nnz.value, r.value
+
+    def vector(self, which, i=0):
+        """-> a copy of g_new (which = 0), g (1), s (2) or y (3) [n]; i: logical history index of s / y, oldest first"""
+        out = np.zeros(max(self.n, 1), np.float32)
+        _ck(lib().dfh_lbfgs_get_vector(self.h, int(which), int(i), _p(out)))
+        return out[:self.n]
 
     def close(self):
         if self.h:

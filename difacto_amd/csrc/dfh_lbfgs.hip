@@ -1455,4 +1455,27 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
   return DFH_OK;
 }
 
+int dfh_lbfgs_get_vector(dfh_lbfgs* o, int which, int i, float* out) {
+  DFH_ARG(o && o->inited && (out || !o->n), "dfh_lbfgs_get_vector: the model is not initialised or out is NULL");
+  DFH_ARG(which >= 0 && which <= 3, "dfh_lbfgs_get_vector: which must be 0 (g_new), 1 (g), 2 (s) or 3 (y)");
+  const float* src = nullptr;
+  if (which == 0) {
+    src = o->d_gnew;
+  } else if (which == 1) {
+    DFH_ARG(o->have_g, "dfh_lbfgs_get_vector: g does not exist before the first dfh_lbfgs_prepare_direction");
+    src = o->d_g;
+  } else if (which == 2) {
+    DFH_ARG(i >= 0 && i < o->s_count, "dfh_lbfgs_get_vector: the s index is outside the history");
+    src = lb_s(o, i);
+  } else {
+    DFH_ARG(i >= 0 && i < o->y_count, "dfh_lbfgs_get_vector: the y index is outside the history");
+    src = lb_y(o, i);
+  }
+  if (!o->n) return DFH_OK;
+  DFH_HIP(hipSetDevice(o->ctx->device));
+  DFH_HIP(hipMemcpyAsync(out, src, o->n * sizeof(float), hipMemcpyDeviceToHost, o->ctx->stream));
+  DFH_HIP(hipStreamSynchronize(o->ctx->stream));
+  return DFH_OK;
+}
+
 }  // extern "C"

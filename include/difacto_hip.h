@@ -623,6 +623,14 @@ int dfh_lbfgs_calc_direction(dfh_lbfgs* o, const float* d, float* p_g);
 int dfh_lbfgs_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, float* p_g, float* auc_n);
 /* Evaluate: validation AUC x n (NULL: skipped), nnz(w), r(w) */
 int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w);
+/* read one of the object's model-sized vectors back, out [nparams] (on a sharded object the rank's owned slice): a copy on
+ * the context's stream and a synchronise, no kernel.  It exists so that tests can assert the state element by element.
+ *   which 0  g_new  (i ignored)
+ *         1  g      (i ignored; DFH_ERR_ARG before the first dfh_lbfgs_prepare_direction)
+ *         2  s      logical index i, oldest first, 0 <= i < the number of s vectors held
+ *         3  y      logical index i, oldest first, 0 <= i < the number of y vectors held
+ * Any other which, or an index outside the history, is DFH_ERR_ARG. */
+int dfh_lbfgs_get_vector(dfh_lbfgs* o, int which, int i, float* out);
 
 /* ------------------------------------------------ block coordinate descent (learner = bcd) */
 /* The learner's state, resident in HBM from load to finish: the localized training and validation chunks (one dfh_batch

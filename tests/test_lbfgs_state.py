@@ -6,6 +6,9 @@ import os
 import numpy as np
 import pytest
 
+import bcd_ref as R
+from lbfgs_ref import Model
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA = os.path.join(ROOT, "tests", "golden", "rcv1_100.libsvm")
@@ -27,65 +30,12 @@ def ctx(capi):
 
 
 def _rcv1():
-    off, idx, val, lab = [0], [], [], []
-    for line in open(DATA):
-        t = line.split()
-        if not t:
-            continue
-        lab.append(float(t[0]))
-        for kv in t[1:]:
-            i, v = kv.split(":")
-            idx.append(int(i))
-            val.append(float(v))
-        off.append(len(idx))
-    return np.array(off, np.uint64), np.array(idx, np.uint64), np.array(val, np.float32), np.array(lab, np.float32)
+    return R.read_libsvm(DATA)
 
 
-class Model:
-    """numpy view of the object's ragged model: dense X over the model's keys, w, V (zero rows without V)"""
-
-    def __init__(self, capi, obj, data):
-        off, idx, val, lab = data
-        m = obj.get_model()
-        self.lens, self.keys = m["lens"], m["keys"]
-        self.pos = np.concatenate([[0], np.cumsum(self.lens)])[:-1]
-        self.y = np.where(lab > 0, 1.0, -1.0)
-        self.X = np.zeros((len(lab), len(self.keys)))
-        rk = np.array([capi.reverse_bytes(int(i)) for i in idx], np.uint64)
-        col = np.searchsorted(self.keys, rk)
-        for r in range(len(lab)):
-            for j in range(int(off[r]), int(off[r + 1])):
-                self.X[r, col[j]] += float(val[j])
-        self.isV = np.zeros(int(self.lens.sum()), bool)
-        for i in np.nonzero(self.lens > 1)[0]:
-            self.isV[self.pos[i] + 1: self.pos[i] + self.lens[i]] = True
-
-    def split(self, w):
-        W = w[self.pos].astype(np.float64)
-        V = np.zeros((len(self.keys), K))
-        has = self.lens > 1
-        V[has] = np.stack([w[self.pos[i] + 1: self.pos[i] + 1 + K] for i in np.nonzero(has)[0]])
-        return W, V
-
-    def loss_grad(self, w):
-        """FMLoss::Predict / Evaluate / CalcGrad (fm_loss.h:67-199) in float64; the gradient in the ragged layout"""
-        W, V = self.split(w)
-        X, y = self.X, self.y
-        XV = X @ V
-        f = np.clip(X @ W + 0.5 * ((XV ** 2) - (X ** 2) @ (V ** 2)).sum(1), -20, 20)
-        loss = np.logaddexp(0, -y * f).sum()
-        p = -y / (1 + np.exp(y * f))
-        gW = X.T @ p
-        gV = X.T @ (p[:, None] * XV) - V * ((X ** 2).T @ p)[:, None]
-        g = np.zeros(len(w))
-        g[self.pos] = gW
-        for i in np.nonzero(self.lens > 1)[0]:
-            g[self.pos[i] + 1: self.pos[i] + 1 + K] = gV[i]
-        return loss, g
-
-    def reg(self, w):
-        c = np.where(self.isV, VL2, L2)
-        return 0.5 * (c * w.astype(np.float64) ** 2).sum(), c * w.astype(np.float64)
+def _model(data):
+    """the float64 reference of the one-chunk model these tests drive; nothing of it comes from the device"""
+    return Model([data], V_dim=K, V_threshold=VTH, l2=L2, V_l2=VL2)
 
 
 def _obj(capi, ctx, data):
@@ -100,9 +50,10 @@ def test_mixed_lens_gradient_and_prepared_history(capi, ctx):
     data = _rcv1()
     obj = _obj(capi, ctx, data)
     try:
-        M = Model(capi, obj, data)
+        M = _model(data)
         assert 0 < (M.lens > 1).sum() < len(M.lens), "the model must mix keys with and without V"
         m = obj.get_model()
+        assert np.array_equal(m["keys"], M.keys) and np.array_equal(m["lens"], M.lens) and np.array_equal(m["cnt"], M.cnt)
         assert np.array_equal(M.lens > 1, m["cnt"] > VTH)
         w0 = m["w"]
         loss0, gl0 = M.loss_grad(w0)
@@ -140,7 +91,7 @@ def test_gamma(capi, ctx):
     data = _rcv1()
     obj = _obj(capi, ctx, data)
     try:
-        M = Model(capi, obj, data)
+        M = _model(data)
         w0 = obj.get_model()["w"]
         _, gl = M.loss_grad(w0)
         gg = np.where(gl > 0, 1.0, -1.0) * np.abs(gl) ** 0.5
