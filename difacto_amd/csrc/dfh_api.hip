@@ -3138,6 +3138,7 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 
 }  // extern "C"
 
+#include "dfh_comm.hip"
 #include "dfh_shard.hip"
 #include "dfh_join.hip"
 #include "dfh_chunks.hip"

@@ -545,30 +545,13 @@ int bcd_gather_gh(dfh_bcd* o, int blk) {
   return comm_exchange(o->comm, gh, 2, nullptr, DFH_XCHG_GRADS);
 }
 
-// sharded, set-up: every rank's n[p] elements of `elem` host bytes to every rank, in rank order; synchronous
+// sharded, set-up: every rank's n[p] elements of `elem` host bytes to every rank, in rank order; synchronous (the
+// host-staged exchange of dfh_comm.hip, transient buffers; one send buffer for every peer: offsets all zero)
 int bcd_allgatherv(dfh_bcd* o, const void* mine, size_t elem, const std::vector<uint64_t>& n, void* all) {
-  const int W = o->comm->world, r = o->comm->rank;
-  hipStream_t s = o->ctx->stream;
-  std::vector<size_t> sb(W, (size_t)n[r] * elem), so(W, 0), rb(W);
-  size_t rt = 0;
-  for (int p = 0; p < W; ++p) rt += rb[p] = (size_t)n[p] * elem;
-  char *d_s = nullptr, *d_r = nullptr;
-  DFH_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), std::max<size_t>(sb[r], 16)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_r), std::max<size_t>(rt, 16)) != hipSuccess) {
-    (void)hipFree(d_s);
-    set_error("dfh_bcd_build: no device memory for the exchange of the ranks' keys");
-    return DFH_ERR_HIP;
-  }
-  int rc = DFH_OK;
-  if (sb[r] && hipMemcpyAsync(d_s, mine, sb[r], hipMemcpyHostToDevice, s) != hipSuccess) rc = DFH_ERR_HIP;
-  const XPart x{d_s, sb.data(), so.data(), d_r, rb.data(), nullptr};
-  if (!rc) rc = comm_exchange(o->comm, &x, 1, nullptr, DFH_XCHG_KEYS);
-  if (!rc && rt && hipMemcpyAsync(all, d_r, rt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = DFH_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = DFH_ERR_HIP;
-  (void)hipFree(d_s);
-  (void)hipFree(d_r);
-  if (rc == DFH_ERR_HIP) set_error("dfh_bcd_build: the exchange of the ranks' keys failed");
-  return rc;
+  const int W = o->comm->world;
+  std::vector<size_t> sb(W, (size_t)n[o->comm->rank] * elem), so(W, 0), rb(W);
+  for (int p = 0; p < W; ++p) rb[p] = (size_t)n[p] * elem;
+  return HostXchg{o->comm, "dfh_bcd_build", HostXchg::TRANSIENT}.exchange(mine, sb.data(), so.data(), all, rb.data(), DFH_XCHG_KEYS);
 }
 
 // one block (order[at]) over every chunk: the gradient over the training chunks, the update, the predictions of every chunk

@@ -841,30 +841,6 @@ int dfh_lbfgs_add_chunk(dfh_lbfgs* o, int is_val, size_t nrows, const size_t* of
 
 namespace {
 
-// an all-to-all-v of host bytes over the communicator, staged through device buffers; synchronous (set-up only)
-int lb_xchg_host(dfh_lbfgs* o, const void* send, const std::vector<size_t>& sb, void* recv, const std::vector<size_t>& rb) {
-  size_t st = 0, rt = 0;
-  for (size_t x : sb) st += x;
-  for (size_t x : rb) rt += x;
-  hipStream_t s = o->ctx->stream;
-  char *d_s = nullptr, *d_r = nullptr;
-  DFH_HIP(hipMalloc(reinterpret_cast<void**>(&d_s), std::max<size_t>(st, 16)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_r), std::max<size_t>(rt, 16)) != hipSuccess) {
-    (void)hipFree(d_s);
-    set_error("dfh_lbfgs_init_model: no device memory for the set-up exchange");
-    return DFH_ERR_HIP;
-  }
-  int rc = DFH_OK;
-  if (st && hipMemcpyAsync(d_s, send, st, hipMemcpyHostToDevice, s) != hipSuccess) rc = DFH_ERR_HIP;
-  if (!rc) rc = comm_alltoallv(o->comm, d_s, sb.data(), d_r, rb.data());
-  if (!rc && rt && hipMemcpyAsync(recv, d_r, rt, hipMemcpyDeviceToHost, s) != hipSuccess) rc = DFH_ERR_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = DFH_ERR_HIP;
-  (void)hipFree(d_s);
-  (void)hipFree(d_r);
-  if (rc == DFH_ERR_HIP) set_error("dfh_lbfgs_init_model: the set-up exchange failed");
-  return rc;
-}
-
 // what a worker asks a key's owner: the key, this rank's merged training count, whether its training chunks hold it
 // (a key of the validation chunks alone is asked for its row and never enters the model)
 struct LbReq {
@@ -907,16 +883,17 @@ int lb_shard_model(dfh_lbfgs* o, float filter, int V_threshold, const std::vecto
     owner[i] = (int)(std::upper_bound(splits.begin(), splits.begin() + (W - 1), req[i].key) - splits.begin());
     ++nreq[owner[i]];
   }
-  rc = lb_xchg_host(o, nreq.data(), std::vector<size_t>(W, 8), nrecv.data(), std::vector<size_t>(W, 8));
+  // the set-up's three all-to-all-vs of host bytes: the host-staged exchange (dfh_comm.hip) with transient buffers; synchronous
+  std::vector<size_t> sb(W, 8), rb(W, 8), seg(W + 1, 0);
+  rc = HostXchg{o->comm, "dfh_lbfgs_init_model", HostXchg::TRANSIENT}.exchange(nreq.data(), sb.data(), nullptr, nrecv.data(), rb.data(), DFH_XCHG_OTHER);
   if (rc) return rc;
-  std::vector<size_t> sb(W), rb(W), seg(W + 1, 0);
   for (int p = 0; p < W; ++p) {
     sb[p] = nreq[p] * sizeof(LbReq);
     rb[p] = nrecv[p] * sizeof(LbReq);
     seg[p + 1] = seg[p] + nrecv[p];
   }
   std::vector<LbReq> got(seg[W]);
-  rc = lb_xchg_host(o, req.data(), sb, got.data(), rb);
+  rc = HostXchg{o->comm, "dfh_lbfgs_init_model", HostXchg::TRANSIENT}.exchange(req.data(), sb.data(), nullptr, got.data(), rb.data(), DFH_XCHG_OTHER);
   if (rc) return rc;
   // owner: every source's list is ascending and the sources lie in rank order; a stable sort by key keeps that order
   std::vector<uint32_t> ord(got.size());
@@ -966,7 +943,7 @@ int lb_shard_model(dfh_lbfgs* o, float filter, int V_threshold, const std::vecto
     sb[p] = nrecv[p] * sizeof(int32_t);
     rb[p] = nreq[p] * sizeof(int32_t);
   }
-  rc = lb_xchg_host(o, reply.data(), sb, ans.data(), rb);
+  rc = HostXchg{o->comm, "dfh_lbfgs_init_model", HostXchg::TRANSIENT}.exchange(reply.data(), sb.data(), nullptr, ans.data(), rb.data(), DFH_XCHG_OTHER);
   if (rc) return rc;
   // worker: its local model, the surviving keys in ascending order (grouped by owner: the owners' slices ascend)
   o->loc_b.assign(W, 0);

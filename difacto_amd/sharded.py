@@ -1,6 +1,6 @@
 """Multi-GPU FM/SGD worker path, Python side: key-range helpers and the N > 1 bench driver.
 
-The exchange itself lives in libdifacto_hip.so (csrc/dfh_shard.hip: dfh_comm / dfh_shard / dfh_shard_step over RCCL
+The exchange itself lives in libdifacto_hip.so (csrc/dfh_comm.hip, csrc/dfh_shard.hip: dfh_comm / dfh_shard / dfh_shard_step over RCCL
 ncclSend / ncclRecv, sync or overlapped): one process per GPU, the model row-sharded by contiguous ranges of the
 reversed keys — what ReverseBytes is for (include/difacto/base.h:29-38) — and because the Localizer emits a minibatch's
 keys in ascending order (src/data/localizer.cc:28-48) each owner's keys are one contiguous slice of it.  The ranges are
