@@ -43,6 +43,7 @@ SYMBOLS = [
     "dfh_bcd_create_sharded",
     "dfh_textchunk_create", "dfh_textchunk_destroy", "dfh_textchunk_parse_criteo", "dfh_textchunk_rows", "dfh_textchunk_ids",
     "dfh_rowbuf_load_slices",
+    "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -170,6 +171,12 @@ def lib():
     L.dfh_textchunk_parse_criteo.argtypes = [vp, vp, sz, i32, PP(i32), PP(sz), PP(sz)]
     L.dfh_textchunk_rows.argtypes = [vp, vp, vp]
     L.dfh_textchunk_ids.argtypes = [vp, vp]
+    L.dfh_lz4_compress.argtypes = [vp, vp, sz, vp, sz, PP(sz)]
+    L.dfh_crb_create.argtypes = [vp, PP(vp)]
+    L.dfh_crb_destroy.argtypes = [vp]
+    L.dfh_crb_encode_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, PP(sz)]
+    L.dfh_crb_encode_textchunk.argtypes = [vp, vp, PP(sz)]
+    L.dfh_crb_record.argtypes = [vp, vp]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -622,6 +629,61 @@ class TextChunk:
     def close(self):
         if self.h:
             lib().dfh_textchunk_destroy(self.h)
+            self.h = None
+
+
+def lz4_compress(ctx, data):
+    """one LZ4 block of `data` (bytes), encoded on the device (dfh_lz4_compress)"""
+    data = bytes(data)
+    n = len(data)
+    cap = n + n // 255 + 16
+    src = C.create_string_buffer(data, n) if n else C.create_string_buffer(1)
+    dst = C.create_string_buffer(cap)
+    out = C.c_size_t(0)
+    _ck(lib().dfh_lz4_compress(ctx.h, src, n, dst, cap, C.byref(out)))
+    return dst.raw[:out.value]
+
+
+class CrbEncoder:
+    """writes CompressedRowBlock records on the device (dfh_crb): the payload of one RecordIO record of a .rec file"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _ck(lib().dfh_crb_create(ctx.h, C.byref(self.h)))
+
+    def _record(self, nbytes):
+        dst = C.create_string_buffer(nbytes)
+        _ck(lib().dfh_crb_record(self.h, dst))
+        return dst.raw
+
+    def encode_host(self, offset, label, index=None, value=None, weight=None):
+        """offset u64 [nrows + 1], label f32 [nrows], index u64 / value f32 [nnz] (the block's own), weight f32 [nrows] -> bytes"""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        label = np.ascontiguousarray(label, np.float32)
+        keep = [offset, label]
+        ptr = []
+        for a, t in ((index, np.uint64), (value, np.float32), (weight, np.float32)):
+            if a is None:
+                ptr.append(None)
+            else:
+                a = np.ascontiguousarray(a, t)
+                keep.append(a)
+                ptr.append(C.c_void_p(a.ctypes.data) if a.size else None)   # (an array of zero elements is written as absent)
+        n = C.c_size_t(0)
+        lab = _p(label) if label.size else C.create_string_buffer(8)
+        _ck(lib().dfh_crb_encode_host(self.h, len(offset) - 1, _p(offset), lab, ptr[0], ptr[1], ptr[2], C.byref(n)))
+        return self._record(n.value)
+
+    def encode_textchunk(self, tc):
+        """the record of the regular chunk last parsed into the TextChunk `tc`"""
+        n = C.c_size_t(0)
+        _ck(lib().dfh_crb_encode_textchunk(self.h, tc.h, C.byref(n)))
+        return self._record(n.value)
+
+    def close(self):
+        if self.h:
+            lib().dfh_crb_destroy(self.h)
             self.h = None
 
 

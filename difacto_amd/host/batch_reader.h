@@ -646,7 +646,8 @@ inline void DecompressRowBlock(const char* data, size_t size, RowChunk* blk) {
   for (int i = 0; i < nrows; ++i) CHECK_LE(blk->offset[i], blk->offset[i + 1]) << "corrupt compressed row block: offsets decrease at row " << i;
   const size_t nnz = blk->offset[nrows] - blk->offset[0];
   CHECK_LE(nnz * sizeof(real_t), max_out) << "corrupt compressed row block: " << nnz << " nonzeros in " << size << " bytes";
-  if (blk->offset[0] != 0) for (auto& o : blk->offset) o -= blk->offset[0];
+  const size_t first = blk->offset[0];   // (a copy: the loop changes offset[0] itself)
+  if (first != 0) for (auto& o : blk->offset) o -= first;
   blk->index.resize(nnz);
   if (!inflate(blk->index.data(), nnz * sizeof(feaid_t))) blk->index.clear();
   blk->value.resize(nnz);

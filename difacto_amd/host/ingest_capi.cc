@@ -1,10 +1,11 @@
 /**
  * ingest_capi.cc — extern "C" view of the host-side ingest code (cityhash.h, lz4_block.h, batch_reader.h)
- * for the CPU tests in tests/test_ingest.py (ctypes).  Host only: no device is touched.
+ * and of the RecordIO writer (recordio_writer.h) for the CPU tests (ctypes).  Host only: no device is touched.
  */
 #include <cstring>
 #include <map>
 #include "./batch_reader.h"
+#include "./recordio_writer.h"
 
 using namespace difacto;
 
@@ -158,6 +159,15 @@ long ingest_parse_criteo(const char* text, size_t len, int is_train, int mode, s
   memcpy(label, c.label.data(), c.label.size() * sizeof(float));
   memcpy(index, c.index.data(), c.index.size() * sizeof(uint64_t));
   return static_cast<long>(c.label.size());
+}
+
+/*! \brief RecordIOWriter::WriteRecord of one payload: the bytes it puts into the file, or -1 when dst is too small */
+long ingest_write_recordio(const char* payload, size_t n, char* dst, size_t cap) {
+  std::string out;
+  RecordIOWriter::Append(payload, n, &out);
+  if (out.size() > cap) return -1;
+  memcpy(dst, out.data(), out.size());
+  return static_cast<long>(out.size());
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <sstream>
+#include "./converter.h"
 #include "difacto/learner.h"
 #include "dmlc/config.h"
 #include "dmlc/parameter.h"
@@ -15,7 +16,7 @@
 namespace difacto {
 
 struct DifactoParam : public dmlc::Parameter<DifactoParam> {
-  std::string task;     // train (default) | predict
+  std::string task;     // train (default) | predict | convert
   std::string learner;  // sgd
   DMLC_DECLARE_PARAMETER(DifactoParam) {
     DMLC_DECLARE_FIELD(learner).set_default("sgd");
@@ -23,6 +24,7 @@ struct DifactoParam : public dmlc::Parameter<DifactoParam> {
   }
 };
 DMLC_REGISTER_PARAMETER(DifactoParam);
+DMLC_REGISTER_PARAMETER(ConverterParam);
 
 /*! \brief collects argv tokens and config-file text, then parses them as one "k = v" stream */
 class ArgParser {
@@ -84,7 +86,7 @@ int main(int argc, char* argv[]) {
   auto kwargs_remain = param.InitAllowUnknown(parser.GetKWArgs());
   // text_parse = device is a key of learner = sgd's device feed: the other learners would only warn about a key they do not know
   for (const auto& kw : kwargs_remain)
-    CHECK(!(kw.first == "text_parse" && kw.second == "device" && param.learner != "sgd"))
+    CHECK(!(kw.first == "text_parse" && kw.second == "device" && param.learner != "sgd" && param.task != "convert"))
         << "text_parse=device with learner=" << param.learner << ": only learner=sgd reads its training data through the device "
            "feed, whose text the device parses; leave text_parse out";
   if (param.task == "train") {
@@ -124,8 +126,13 @@ int main(int argc, char* argv[]) {
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));
     learner->Run();
     delete learner;
+  } else if (param.task == "convert") {
+    // src/main.cc:57-60: data_in -> data_out (libsvm or rec); the row blocks of a .rec file are compressed on the device
+    Converter converter;
+    WarnUnknownKWArgs(param, converter.Init(kwargs_remain));
+    converter.Run();
   } else {
-    LOG(FATAL) << "unknown task: " << param.task << " (this build provides train and predict)";
+    LOG(FATAL) << "unknown task: " << param.task << " (this build provides train, predict and convert)";
   }
   return 0;
 }

@@ -13,6 +13,7 @@
 #include <memory>
 #include <thread>
 #include <unistd.h>
+#include "./device_text_parse.h"
 #include "./hip_fm_loss.h"
 #include "./host_localizer.h"
 #include "./libsvm_reader.h"
@@ -246,10 +247,6 @@ void SGDLearner::IterateData(const sgd::Job& job, sgd::Progress* prog) {
 }
 
 namespace {
-// parser threads of a reader whose chunks the device parses (text_parse = device): a thread uploads a chunk and waits for
-// the device, so a few keep the copy of one chunk beside the kernels of another
-constexpr int kDeviceParseThreads = 3;
-
 // Device feed: the reader's shuffle buffers in HBM.  The reader thread uploads every buffer once, when it becomes current
 // (BatchReader::Describe), into a device row buffer; the worker loop then sends 4 B per row of a minibatch and the rows are
 // gathered on the device (dfh_batch_gather_rows) instead of being copied twice on the host (into the minibatch, into the
@@ -551,7 +548,7 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   // text_parse = device: the reader's parser threads hand every chunk of criteo text to the device (dfh_textchunk_parse_criteo:
   // upload, parse, 8 B per row back); the ids stay in HBM with the chunk's container and DeviceFeed::DoUpload copies them
   // device to device.  A chunk that is not regular is left to the host parser (counted: logged at the end of the job)
-  std::atomic<size_t> tp_chunks{0}, tp_fallback{0};
+  DeviceTextParse text_parse;   // (outlives the reader, whose parser threads count into it)
   DeviceFeed feed;   // outlives the reader, whose thread uploads into it
   feed.ctx = ctx;
   const bool device_feed = feed_wanted;
@@ -575,35 +572,9 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   const bool criteo = param_.data_format == "criteo" || param_.data_format == "criteo_test";
   const bool device_parse = GetUpdater()->device_param().text_parse == "device" && device_feed && !cpart && criteo;
   ParseHook parse_hook;
-  if (device_parse) {
-    const int is_train_format = param_.data_format == "criteo" ? 1 : 0;
-    parse_hook = [ctx, is_train_format, &tp_chunks, &tp_fallback](const RawChunk& raw, RowChunk* out) {
-      if (!out->dev) {   // (the container comes out of the reader's pool: its device-side arrays are reused like its vectors)
-        dfh_textchunk* tc = nullptr;
-        DFH_CALL(dfh_textchunk_create(ctx, std::max<size_t>(raw.size, 1), &tc));
-        out->dev = std::shared_ptr<void>(tc, [](void* p) { dfh_textchunk_destroy(static_cast<dfh_textchunk*>(p)); });
-      }
-      dfh_textchunk* tc = static_cast<dfh_textchunk*>(out->dev.get());
-      int regular = 0;
-      size_t nrows = 0, nnz = 0;
-      DFH_CALL(dfh_textchunk_parse_criteo(tc, raw.data, raw.size, is_train_format, &regular, &nrows, &nnz));
-      ++tp_chunks;
-      if (!regular) {
-        ++tp_fallback;
-        return false;
-      }
-      static thread_local std::vector<uint32_t> off32;
-      off32.resize(nrows + 1);
-      out->Clear();
-      out->label.resize(nrows);
-      DFH_CALL(dfh_textchunk_rows(tc, off32.data(), out->label.data()));
-      out->offset.assign(off32.begin(), off32.end());
-      out->on_device = true;
-      return true;
-    };
-  }
-  // the device parses: the parser threads only upload and wait (kDeviceParseThreads; DIFACTO_PARSER_THREADS overrides)
-  const int parser_threads = device_parse && getenv("DIFACTO_PARSER_THREADS") == nullptr ? kDeviceParseThreads : 0;
+  if (device_parse) parse_hook = text_parse.Hook(ctx, param_.data_format == "criteo" ? 1 : 0);
+  // the device parses: the parser threads only upload and wait (DeviceTextParse::kThreads; DIFACTO_PARSER_THREADS overrides)
+  const int parser_threads = device_parse && getenv("DIFACTO_PARSER_THREADS") == nullptr ? DeviceTextParse::kThreads : 0;
   // device feed: buffers as slices of the parsed chunks (no host assembly), uploaded by the thread that builds them
   BatchReader* batch_reader =
       cpart ? new BatchReader(new CachedBuffers(cpart), param_.batch_size, cache_buf_rows, train ? param_.neg_sampling : 1.0f, permute)
@@ -769,13 +740,7 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   }
   uint64_t nkeys;
   DFH_CALL(dfh_table_size(table, &nkeys));  // surfaces a full table as an error
-  if (device_parse) {
-    const size_t nf = tp_fallback.load(), nc = tp_chunks.load();
-    LOG(INFO) << "text_parse=device: " << nc - nf << " of " << nc << " chunks of " << JobData(job) << " parsed on the device, " << nf
-              << " fell back to the host parser";
-    if (nf) LOG(WARNING) << "text_parse=device: " << nf << " of " << nc << " chunks are not made of regular rows alone (CRLF, blank lines, "
-                            "odd labels or field lengths) and were parsed on the host";
-  }
+  if (device_parse) text_parse.Log(JobData(job));
   if (cache_on) {   // one line per job: where its rows came from
     const std::string what = "part " + std::to_string(job.part_idx) + " of " + std::to_string(job.num_parts) +
                              (train ? " (training): " : " (validation): ");

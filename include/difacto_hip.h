@@ -283,6 +283,29 @@ int dfh_textchunk_destroy(dfh_textchunk* tc);
 int dfh_textchunk_parse_criteo(dfh_textchunk* tc, const char* text, size_t len, int is_train, int* regular, size_t* nrows, size_t* nnz);
 int dfh_textchunk_rows(dfh_textchunk* tc, uint32_t* offset, float* label);
 int dfh_textchunk_ids(dfh_textchunk* tc, uint64_t* index);
+/* task = convert: .rec records written on the device (csrc/dfh_lz4enc.hip).  dfh_lz4_compress: `n` bytes at `src` (host; they are
+ * uploaded) -> ONE LZ4 block at `dst` that a conforming decoder (LZ4_decompress_safe, host/lz4_block.h) inflates to exactly those
+ * bytes: the last sequence is literals only, the last 5 bytes are literals, no match starts within the last 12 bytes, offsets are
+ * 1 .. 65535; *out_bytes <= n + n / 255 + 16 (DFH_ERR_ARG when cap is smaller than the block).  The bytes are not liblz4's; the
+ * same input gives the same bytes on every run.  n >= 2^31 - 2^25 is refused (DFH_ERR_ARG).
+ * A dfh_crb is an encoder with its device arrays and a stream of its own; the arrays grow to what a block needs.
+ * dfh_crb_encode_host: CompressedRowBlock::Compress (src/data/compressed_row_block.h:23-49) of host arrays: label [nrows],
+ * offset [nrows + 1] (written as given), index / value [offset[nrows] - offset[0]] = the block's own nonzeros (index[0] is the
+ * first id of row 0), weight [nrows]; index, value and weight may be NULL (index only without nonzeros).  The record is int32
+ * magic 1196140743, int32 8, int32 nrows, then per array label, offset, index, value, weight: int32 size of the LZ4 block and
+ * the block; an absent array, an array of zero elements and values that are all exactly 1 are written as int32 0.
+ * dfh_crb_encode_textchunk: the same for a regular parsed chunk of criteo text — the ids are taken where they are in HBM, the
+ * offsets widened to 64 bits on the device, no values — byte for byte the record dfh_crb_encode_host gives for the chunk's rows.
+ * An encode call returns when the caller's arrays (the text chunk) may be reused and *record_bytes is known; dfh_crb_record
+ * copies the record of the last encode to dst [record_bytes].  Calls on different objects may run on different threads. */
+int dfh_lz4_compress(dfh_ctx* c, const void* src, size_t n, void* dst, size_t cap, size_t* out_bytes);
+typedef struct dfh_crb dfh_crb;
+int dfh_crb_create(dfh_ctx* c, dfh_crb** out);
+int dfh_crb_destroy(dfh_crb* e);
+int dfh_crb_encode_host(dfh_crb* e, size_t nrows, const size_t* offset, const float* label, const uint64_t* index, const float* value,
+                        const float* weight, size_t* record_bytes);
+int dfh_crb_encode_textchunk(dfh_crb* e, dfh_textchunk* tc, size_t* record_bytes);
+int dfh_crb_record(dfh_crb* e, void* dst);
 /* dfh_rowbuf_load_host_slices whose slices are either host arrays (chunk = NULL; value may be NULL = all ones) or ids
  * [first, first + nnz) of a regular parsed chunk (index and value unused; no values), copied device to device on the
  * buffer's stream.  Same contract: it returns when the sources may be reused (the chunk may be parsed into again). */
