@@ -44,6 +44,7 @@ SYMBOLS = [
     "dfh_textchunk_create", "dfh_textchunk_destroy", "dfh_textchunk_parse_criteo", "dfh_textchunk_rows", "dfh_textchunk_ids",
     "dfh_rowbuf_load_slices",
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
+    "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -63,6 +64,12 @@ class Progress(C.Structure):
     """sgd::Progress (src/sgd/sgd_utils.h:40-75)"""
     _fields_ = [("loss", C.c_float), ("penalty", C.c_float), ("auc", C.c_float),
                 ("nnz_w", C.c_float), ("nrows", C.c_float)]
+
+
+class EvalResult(C.Structure):
+    """dfh_eval_result: the exact whole-set metrics (auc2 = 2 x pairs ranked right + tied pairs)"""
+    _fields_ = [("n", C.c_uint64), ("n_pos", C.c_uint64), ("n_neg", C.c_uint64), ("n_nan", C.c_uint64), ("auc2", C.c_uint64),
+                ("correct", C.c_uint64), ("objv", C.c_double)]
 
 
 class Slice(C.Structure):
@@ -177,6 +184,12 @@ def lib():
     L.dfh_crb_encode_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, PP(sz)]
     L.dfh_crb_encode_textchunk.argtypes = [vp, vp, PP(sz)]
     L.dfh_crb_record.argtypes = [vp, vp]
+    L.dfh_eval_create.argtypes = [vp, sz, PP(vp)]
+    L.dfh_eval_destroy.argtypes = [vp]
+    L.dfh_eval_reset.argtypes = [vp]
+    L.dfh_eval_append_batch.argtypes = [vp, vp]
+    L.dfh_eval_append_host.argtypes = [vp, vp, vp, sz]
+    L.dfh_eval_finish.argtypes = [vp, PP(EvalResult)]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -684,6 +697,39 @@ class CrbEncoder:
     def close(self):
         if self.h:
             lib().dfh_crb_destroy(self.h)
+            self.h = None
+
+
+class Eval:
+    """whole-set evaluation on the device (dfh_eval): exact AUC, logloss and accuracy of the appended rows"""
+
+    def __init__(self, ctx, capacity_hint=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _ck(lib().dfh_eval_create(ctx.h, capacity_hint, C.byref(self.h)))
+
+    def reset(self):
+        _ck(lib().dfh_eval_reset(self.h))
+
+    def append_batch(self, batch):
+        """the batch's predictions and labels, queued behind its last step; does not wait"""
+        _ck(lib().dfh_eval_append_batch(self.h, batch.h))
+
+    def append_host(self, label, pred):
+        label = np.ascontiguousarray(label, np.float32)
+        pred = np.ascontiguousarray(pred, np.float32)
+        assert label.shape == pred.shape and label.ndim == 1
+        _ck(lib().dfh_eval_append_host(self.h, _p(label), _p(pred), label.size))
+
+    def finish(self):
+        """-> EvalResult; everything appended since the last reset (waits; nothing is consumed)"""
+        r = EvalResult()
+        _ck(lib().dfh_eval_finish(self.h, C.byref(r)))
+        return r
+
+    def close(self):
+        if self.h:
+            lib().dfh_eval_destroy(self.h)
             self.h = None
 
 

@@ -29,6 +29,7 @@ DMLC_REGISTER_PARAMETER(DeviceParam);
 DMLC_REGISTER_PARAMETER(FMLossParam);
 
 SGDLearner::~SGDLearner() {
+  if (eval_) dfh_eval_destroy(eval_);
   for (auto& b : batch_)
     if (b) dfh_batch_destroy(b);
   delete loss_;
@@ -56,6 +57,20 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
       CHECK(!(kv.first == "device_path" && kv.second == "literal"))
           << "data_cache=hbm with device_path=literal: the literal loop hands host arrays to Store and Loss, only "
              "device_path=fused gathers its minibatches out of device row buffers";
+  }
+  // exact_metrics: checked before anything touches the device, like data_cache
+  CHECK(param_.exact_metrics == 0 || param_.exact_metrics == 1)
+      << "exact_metrics=" << param_.exact_metrics << " is not one of 0 (off, the default) and 1";
+  if (param_.exact_metrics == 1) {
+    CHECK(!IsDistributed()) << "exact_metrics=1 with a sharded store (DMLC_ROLE is set): the pairs of all ranks would have to meet "
+                               "on one device, which this build does not do; run one process, or leave exact_metrics out";
+    for (const auto& kv : remain)
+      CHECK(!(kv.first == "device_path" && kv.second == "literal"))
+          << "exact_metrics=1 with device_path=literal: the literal loop keeps its predictions in host arrays, only "
+             "device_path=fused leaves them on the device; use device_path=fused, or leave exact_metrics out";
+    CHECK(param_.task != "train" || param_.data_val.size())
+        << "exact_metrics=1 with task=train and no data_val: there is nothing to evaluate; name a validation file with "
+           "data_val=<file>, or leave exact_metrics out";
   }
   // text_parse: checked before anything touches the device, like data_cache.  "device" is accepted only where the device feed
   // reads the training data (IterateDataFused); validation and prediction readers outside the feed keep the host parser
@@ -167,9 +182,37 @@ void SGDLearner::RunEpoch(int epoch, int job_type, sgd::Progress* prog) {
     jobs.emplace_back(0, std::string());
     job.SerializeToString(&jobs.back().second);
   }
+  // exact_metrics = 1: the evaluator starts the pass empty; the worker loop appends every minibatch of it
+  const bool exact = param_.exact_metrics == 1 && job_type != sgd::Job::kTraining;
+  if (exact) {
+    if (!eval_) DFH_CALL(dfh_eval_create(DeviceContext::Get(), 0, &eval_));
+    DFH_CALL(dfh_eval_reset(eval_));
+  }
   tracker_->Issue(jobs);
   while (tracker_->NumRemains()) std::this_thread::sleep_for(std::chrono::microseconds(200));
   if (sharded) MergeAcrossRanks(prog);
+  if (exact) LogExactMetrics(job_type == sgd::Job::kValidation ? " - Validation (whole set): " : "whole file: ");
+}
+
+void SGDLearner::LogExactMetrics(const char* what) {
+  dfh_eval_result r;
+  DFH_CALL(dfh_eval_finish(CHECK_NOTNULL(eval_), &r));
+  char num[3][40];
+  const uint64_t rows = r.n - r.n_nan;
+  if (r.n_pos && r.n_neg) {
+    snprintf(num[0], sizeof(num[0]), "%.17g", static_cast<double>(r.auc2) / (2.0 * r.n_pos * r.n_neg));
+  } else {
+    snprintf(num[0], sizeof(num[0]), "undefined");
+  }
+  if (rows) {
+    snprintf(num[1], sizeof(num[1]), "%.17g", r.objv / rows);
+    snprintf(num[2], sizeof(num[2]), "%.17g", static_cast<double>(r.correct) / rows);
+  } else {
+    snprintf(num[1], sizeof(num[1]), "undefined");
+    snprintf(num[2], sizeof(num[2]), "undefined");
+  }
+  LOG(INFO) << what << "rows=" << r.n << " pos=" << r.n_pos << " neg=" << r.n_neg << " nan=" << r.n_nan << " auc2=" << r.auc2
+            << " auc=" << num[0] << " logloss=" << num[1] << " accuracy=" << num[2];
 }
 
 // task = predict (src/main.cc:61-62 is a TODO in the reference; sgd_param.h:24-28: "model_in ... should be specified if it
@@ -698,6 +741,7 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   auto step_one = [&] {
     const int cur = i % nrot;
     DFH_CALL(dfh_sgd_step(table, batch_[cur], train ? 1 : 0, push_cnt ? 1 : 0));
+    if (eval_ && !train) DFH_CALL(dfh_eval_append_batch(eval_, batch_[cur]));  // exact_metrics = 1: queued behind the step
     if (predict) WritePredictions(batch_[cur]);
     ++i;
   };

@@ -57,6 +57,8 @@ class SGDLearner : public Learner {
   void RunPrediction();
   /*! \brief prediction jobs: the step's logits, one line per example, appended to the job's output file */
   void WritePredictions(dfh_batch* b);
+  /*! \brief exact_metrics = 1: the whole-set figures of the pass that has just ended, as one log line behind `what` */
+  void LogExactMetrics(const char* what);
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
   const std::string& JobData(const sgd::Job& job) const;
   void IterateData(const sgd::Job& job, sgd::Progress* prog);
@@ -87,6 +89,7 @@ class SGDLearner : public Learner {
   SGDDataCache cache_;              // data_cache = hbm: the row buffers of the parts read so far; destroyed with the learner
   FILE* pred_file_ = nullptr;       // open while a prediction job runs
   std::vector<float> pred_buf_;
+  dfh_eval* eval_ = nullptr;        // exact_metrics = 1: the rows of the current validation / prediction pass
 };
 
 }  // namespace difacto

@@ -35,12 +35,16 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   // every data part stay in device memory after the epoch that read them, later epochs open no file (sgd_data_cache.h)
   std::string data_cache;    // "" (default: every epoch reads its files) | "hbm"
   float data_cache_max_gb;   // > 0: device bytes the cache may hold, in GB (2^30); a part that does not fit is read every epoch
+  // exact_metrics = 1 (a key of this build): validation epochs and task = predict keep every prediction and label on the device
+  // and report the exact AUC, logloss and accuracy of the whole set in one more log line (dfh_eval); nothing else changes
+  int exact_metrics;         // 0 (default) | 1
   DMLC_DECLARE_PARAMETER(SGDLearnerParam) {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
     DMLC_DECLARE_FIELD(pred_prob).set_default(0);
     DMLC_DECLARE_FIELD(data_cache).set_default("");
     DMLC_DECLARE_FIELD(data_cache_max_gb).set_default(0);
+    DMLC_DECLARE_FIELD(exact_metrics).set_default(0);
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_in);
     DMLC_DECLARE_FIELD(data_val).set_default("");

@@ -726,6 +726,36 @@ int dfh_bcd_get_model(dfh_bcd* o, uint64_t* keys, float* feacnt, float* w, float
 /* the predictions of a chunk (pred NULL: only *nrows) */
 int dfh_bcd_get_pred(dfh_bcd* o, int is_val, int chunk, float* pred, size_t* nrows);
 
+/* ------------------------------------------------ whole-set evaluation (exact_metrics = 1) */
+/* BinClassMetric::AUC (src/loss/bin_class_metric.h:35-56) is taken per minibatch and averaged by the reference's learner, which
+ * is not the AUC of the set.  A dfh_eval keeps every (label, prediction) row appended since the last reset in device memory
+ * (8 B per row; the arrays grow by doubling, earlier content survives) and ranks them once (csrc/dfh_eval.hip).
+ *   - a row is positive iff label > 0 (the reference's rule: a NaN label is negative); a row whose prediction is a NaN is
+ *     counted in n_nan and takes part in nothing else; scores compare as floats (-0.0 == +0.0, +-inf are ordinary values)
+ *   - auc2 is exact (an integer); AUC = auc2 / (2 n_pos n_neg), undefined when either count is 0 (then auc2 = 0)
+ *   - objv is summed in fp64 in a fixed order, each term in the stable form max(-m, 0) + log1p(exp(-|m|)), m = y s; objv and
+ *     correct cover the rows that are not counted in n_nan
+ *   - the same appended sequence gives the same bits in every field on every run, however it was cut into appends
+ * dfh_eval_append_batch queues a copy of the batch's nrows predictions and labels on the context's stream, behind the batch's
+ * last step (dfh_sgd_step), and does not wait for the device; call it before the next minibatch is loaded into the batch
+ * object (with pipelining on, that load waits for the copies: the call moves the object's `free` event behind them).
+ * dfh_eval_append_host copies host arrays and returns when they are free.  An evaluator holds fewer than 2^32 - 16 rows (DFH_ERR_ARG); a failed allocation is DFH_ERR_CAPACITY with the
+ * bytes needed in the message.  capacity_hint: the rows of the first allocation (0: 65 536).  dfh_eval_finish waits and covers
+ * everything appended since the last reset; it changes nothing: more may be appended and a later finish covers all of it. */
+typedef struct dfh_eval dfh_eval;
+typedef struct {
+  uint64_t n, n_pos, n_neg, n_nan;   /* n = n_pos + n_neg + n_nan                      */
+  uint64_t auc2;                     /* 2 * #{(p,q): s_p > s_q} + #{(p,q): s_p == s_q}, p over the positives, q over the negatives */
+  uint64_t correct;                  /* (label > 0 && s > 0) || (!(label > 0) && s <= 0) */
+  double   objv;                     /* sum of log(1 + exp(-y s)), y = label > 0 ? 1 : -1 */
+} dfh_eval_result;
+int dfh_eval_create(dfh_ctx* ctx, size_t capacity_hint, dfh_eval** out);
+int dfh_eval_destroy(dfh_eval* e);
+int dfh_eval_reset(dfh_eval* e);
+int dfh_eval_append_batch(dfh_eval* e, dfh_batch* b);
+int dfh_eval_append_host(dfh_eval* e, const float* label, const float* pred, size_t n);
+int dfh_eval_finish(dfh_eval* e, dfh_eval_result* out);
+
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
 int dfh_free(dfh_ctx* ctx, void* dptr);
