@@ -45,6 +45,7 @@ SYMBOLS = [
     "dfh_rowbuf_load_slices",
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
     "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
+    "dfh_batch_key_view_info", "dfh_batch_get_key_view",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -75,6 +76,14 @@ class EvalResult(C.Structure):
 class Slice(C.Structure):
     """dfh_slice: host arrays (chunk = NULL), or ids [first, first + nnz) of a parsed text chunk"""
     _fields_ = [("index", C.c_void_p), ("value", C.c_void_p), ("chunk", C.c_void_p), ("first", C.c_size_t), ("nnz", C.c_size_t)]
+
+
+class KeyViewInfo(C.Structure):
+    """dfh_key_view_info: the sizes of what dfh_batch_get_key_view fills, and the class bounds of the build"""
+    _fields_ = [("U", C.c_uint64), ("nnz", C.c_uint64), ("has_value", C.c_uint32), ("seg_nb", C.c_uint32), ("P", C.c_uint32),
+                ("split_n", C.c_uint32), ("few_cap", C.c_uint64), ("mid_cap", C.c_uint64), ("hot_cap", C.c_uint64),
+                ("split_cap", C.c_uint64), ("bwd_small", C.c_uint32), ("bwd_mid", C.c_uint32), ("hot_split", C.c_uint32),
+                ("hot_split_min", C.c_uint32)]
 
 
 # dfh_alltoallv_fn: int (*)(void* user, const void* send, const size_t* send_bytes, void* recv, const size_t* recv_bytes)
@@ -143,6 +152,8 @@ def lib():
     L.dfh_batch_destroy.argtypes = [vp]
     L.dfh_batch_create_many.argtypes = [vp, i32, sz, sz, PP(vp)]
     L.dfh_batch_split_entries.argtypes = [vp, vp]
+    L.dfh_batch_key_view_info.argtypes = [vp, PP(KeyViewInfo)]
+    L.dfh_batch_get_key_view.argtypes = [vp] * 12
     L.dfh_batch_load_host.argtypes = [vp, sz, vp, vp, vp, vp]
     L.dfh_batch_load_device.argtypes = [vp, sz, sz, vp, vp, vp, vp]
     L.dfh_batch_attach_device.argtypes = [vp, sz, sz, vp, vp, vp, vp]
@@ -871,6 +882,35 @@ class Batch:
         n = C.c_uint32(0)
         _ck(lib().dfh_batch_split_entries(self.h, C.byref(n)))
         return int(n.value)
+
+    def get_key_view(self):
+        """the key-ordered view and the segment lists as the backward and update passes walk them (dfh_batch_get_key_view):
+        col_ptr, s_row, s_val (None: binary); few / mid / hot = dict(desc [seg_nb, 2] {cnt, off}, cap, buckets = the entries
+        [cnt, 4] of every list bucket's [off, off + cnt), None where that range leaves the array); split [split_n, 4];
+        P and bstart [P + 1] where the minibatch came out of the sample sort (else P = 0, bstart None); the class bounds"""
+        info = KeyViewInfo()
+        _ck(lib().dfh_batch_key_view_info(self.h, C.byref(info)))
+        U, nnz, nb = int(info.U), int(info.nnz), int(info.seg_nb)
+        col_ptr = np.zeros(U + 1, np.uint32)
+        s_row = np.zeros(max(nnz, 1), np.uint32)
+        s_val = np.zeros(max(nnz, 1), np.float32) if info.has_value else None
+        caps = dict(few=int(info.few_cap), mid=int(info.mid_cap), hot=int(info.hot_cap))
+        desc = {k: np.zeros((max(nb, 1), 2), np.uint32) for k in caps}
+        ent = {k: np.zeros((caps[k], 4), np.uint32) for k in caps}
+        ns = min(int(info.split_n), int(info.split_cap))
+        split = np.zeros((max(ns, 1), 4), np.uint32)
+        bstart = np.zeros(int(info.P) + 1, np.uint32) if info.P else None
+        _ck(lib().dfh_batch_get_key_view(self.h, _p(col_ptr), _p(s_row), _p(s_val), _p(desc["few"]), _p(ent["few"]),
+                                         _p(desc["mid"]), _p(ent["mid"]), _p(desc["hot"]), _p(ent["hot"]), _p(split), _p(bstart)))
+        out = dict(U=U, nnz=nnz, col_ptr=col_ptr, s_row=s_row[:nnz], s_val=None if s_val is None else s_val[:nnz],
+                   seg_nb=nb, P=int(info.P), bstart=bstart, split_n=int(info.split_n), split_cap=int(info.split_cap),
+                   split=split[:ns], BWD_SMALL=int(info.bwd_small), BWD_MID=int(info.bwd_mid), HOT_SPLIT=int(info.hot_split),
+                   HOT_SPLIT_MIN=int(info.hot_split_min))
+        for k in caps:
+            d = desc[k][:nb]
+            out[k] = dict(desc=d, cap=caps[k],
+                          buckets=[ent[k][int(o):int(o) + int(c)].copy() if int(o) + int(c) <= caps[k] else None for c, o in d])
+        return out
 
     def forward(self, V_dim, d_rows):
         _ck(lib().dfh_batch_forward(self.h, V_dim, _dp(d_rows)))

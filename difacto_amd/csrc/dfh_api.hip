@@ -200,7 +200,9 @@ struct dfh_batch {
   int split_sel = 0, split_last = 0;
   bool split_listing = false;
   uint32_t seg_nb = 0;                              // list buckets of the current localized view
-  uint2* d_uw = nullptr;           // {table row, w} per unique key, written by the step's k_lookup
+  uint32_t view_P = 0;                              // ... which came out of the sample sort with this many buckets (d_bstart); 0: not
+  size_t few_cap = 0, mid_cap = 0, hot_cap = 0;     // entries d_few_ent / d_mid_ent / d_hot_ent hold (dfh_batch_get_key_view)
+  uint2* d_uw = nullptr;          // {table row, w} per unique key, written by the step's k_lookup
   uint32_t *d_urow = nullptr, *d_need = nullptr, *d_rank = nullptr, *d_total = nullptr;
   float *d_pred = nullptr, *d_slope = nullptr, *d_xv = nullptr;
   size_t xv_floats = 0;
@@ -2278,10 +2280,14 @@ static int batch_create_impl(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_ba
   DFH_ALLOC(b->d_U, 64, uint32_t);
   DFH_ALLOC(b->d_urow, N, uint32_t);
   DFH_ALLOC(b->d_uw, N, uint2);
-  // bucket q of the sample sort may list n_q / 9 + 2 mid and n_q / 257 + 2 hot keys (k_loc_emit)
-  DFH_ALLOC(b->d_mid_ent, N / (BWD_SMALL + 1) + 2 * LOC_BIG_BUCKETS + 16, SegEnt);
-  DFH_ALLOC(b->d_hot_ent, N / (BWD_MID + 1) + 2 * LOC_BIG_BUCKETS + 16, SegEnt);
-  DFH_ALLOC(b->d_few_ent, N / 2 + 2 * LOC_BIG_BUCKETS + 16, SegEnt);
+  // bucket q of the sample sort may list n_q / 2 + 2 few, n_q / (BWD_SMALL + 1) + 2 mid and n_q / (BWD_MID + 1) + 2 hot keys
+  // (k_loc_emit: its slot range starts at beg_q / 2 + 2 q, beg_q / (BWD_SMALL + 1) + 2 q and beg_q / (BWD_MID + 1) + 2 q)
+  b->mid_cap = N / (BWD_SMALL + 1) + 2 * LOC_BIG_BUCKETS + 16;
+  b->hot_cap = N / (BWD_MID + 1) + 2 * LOC_BIG_BUCKETS + 16;
+  b->few_cap = N / 2 + 2 * LOC_BIG_BUCKETS + 16;
+  DFH_ALLOC(b->d_mid_ent, b->mid_cap, SegEnt);
+  DFH_ALLOC(b->d_hot_ent, b->hot_cap, SegEnt);
+  DFH_ALLOC(b->d_few_ent, b->few_cap, SegEnt);
   b->split_cap = 2 * (N / HOT_SPLIT) + 16;   // >= the sum over the segments longer than HOT_SPLIT_MIN of ceil(len / HOT_SPLIT)
   DFH_ALLOC(b->d_split_ent, b->split_cap, SegEnt);
   DFH_ALLOC(b->d_split_ticket, b->split_cap, uint32_t);
@@ -2595,6 +2601,7 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
     DFH_HIP(hipMemsetAsync(b->d_U, 0, 64 * sizeof(uint32_t), s));  // U = 0
     DFH_HIP(hipMemsetAsync(b->d_col_ptr, 0, 4, s));
     b->seg_nb = 0;  // no long segments
+    b->view_P = 0;
     b->localized = true;
     return prep_end(b);
   }
@@ -2709,6 +2716,7 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
     }
     b->spl_P = P;  // k_loc_emit leaves this minibatch's exact P-quantiles as the next call's splitters
     b->seg_nb = (uint32_t)P;
+    b->view_P = (uint32_t)P;
   } else {
     // very large batches: library LSD radix sort
     hipLaunchKernelGGL(k_rdx_keys, dim3(g), dim3(256), 0, s, b->d_raw, N, max_index, b->d_keys, b->d_pos);
@@ -2725,6 +2733,7 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
     hipLaunchKernelGGL(k_seg_lists, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((N + 1023) / 1024, 256))), dim3(1024), 0, s,
                        b->d_col_ptr, b->d_U, b->d_mid, b->d_hot, b->d_few, b->d_mid_ent, b->d_hot_ent, b->d_few_ent);
     b->seg_nb = 1;
+    b->view_P = 0;
     if (probe)  // the library sort's path has no emit pass to carry the probe
       hipLaunchKernelGGL(k_lookup, dim3(grid_for_threads(b->nnz, c)), dim3(256), 0, s, probe->v, b->d_feaids, b->d_U, 0u, b->d_urow,
                          (const float*)nullptr, b->d_col_ptr, 0, (uint32_t*)nullptr, 0, (uint2*)nullptr, AucFin{nullptr, 0u, nullptr});
@@ -2860,6 +2869,7 @@ int dfh_batch_load_localized_host(dfh_batch* b, size_t nrows, const size_t* offs
                        b->d_U, b->d_mid, b->d_hot, b->d_few, b->d_mid_ent, b->d_hot_ent, b->d_few_ent);
   }
   b->seg_nb = 1;
+  b->view_P = 0;
   DFH_HIP(hipGetLastError());
   DFH_HIP(hipStreamSynchronize(s));
   b->nrows = nrows;
@@ -3031,6 +3041,75 @@ int dfh_batch_split_entries(dfh_batch* b, uint32_t* n) {
   if (b->ready_pending) DFH_HIP(hipStreamWaitEvent(c->stream, b->ev_ready, 0));
   DFH_HIP(hipMemcpyAsync(n, b->d_U + 2 + b->split_last, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   DFH_HIP(hipStreamSynchronize(c->stream));
+  return DFH_OK;
+}
+
+namespace {
+// what both key-view calls do first: everything queued for the batch has run (as dfh_batch_shape), U and the split counter read
+int key_view_begin(dfh_batch* b, uint32_t* U, uint32_t* split_n) {
+  dfh_ctx* c = b->ctx;
+  DFH_HIP(hipSetDevice(c->device));
+  int rc = flush_pending(b);
+  if (rc) return rc;
+  rc = sync_all(c);
+  if (rc) return rc;
+  DFH_HIP(hipMemcpy(U, b->d_U, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  DFH_HIP(hipMemcpy(split_n, b->d_U + 2 + b->split_last, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (*U > b->nnz) *U = (uint32_t)b->nnz;   // (never more keys than pairs: what is copied stays inside the arrays)
+  return DFH_OK;
+}
+}  // namespace
+
+int dfh_batch_key_view_info(dfh_batch* b, dfh_key_view_info* out) {
+  DFH_ARG(b && out, "dfh_batch_key_view_info: NULL argument");
+  if (!b->localized) {
+    set_error("dfh_batch_key_view_info: batch is not localized");
+    return DFH_ERR_STATE;
+  }
+  uint32_t U = 0, sn = 0;
+  int rc = key_view_begin(b, &U, &sn);
+  if (rc) return rc;
+  out->U = U;
+  out->nnz = b->nnz;
+  out->has_value = b->has_value ? 1u : 0u;
+  out->seg_nb = b->seg_nb;
+  out->P = b->view_P;
+  out->split_n = sn;
+  out->few_cap = b->few_cap;
+  out->mid_cap = b->mid_cap;
+  out->hot_cap = b->hot_cap;
+  out->split_cap = b->split_cap;
+  out->bwd_small = BWD_SMALL;
+  out->bwd_mid = BWD_MID;
+  out->hot_split = HOT_SPLIT;
+  out->hot_split_min = HOT_SPLIT_MIN;
+  return DFH_OK;
+}
+
+int dfh_batch_get_key_view(dfh_batch* b, uint32_t* col_ptr, uint32_t* s_row, float* s_val, uint32_t* few_desc, uint32_t* few_ent,
+                           uint32_t* mid_desc, uint32_t* mid_ent, uint32_t* hot_desc, uint32_t* hot_ent, uint32_t* split_ent,
+                           uint32_t* bstart) {
+  DFH_ARG(b, "dfh_batch_get_key_view: NULL batch");
+  if (!b->localized) {
+    set_error("dfh_batch_get_key_view: batch is not localized");
+    return DFH_ERR_STATE;
+  }
+  uint32_t U = 0, sn = 0;
+  int rc = key_view_begin(b, &U, &sn);
+  if (rc) return rc;
+  const size_t nnz = b->nnz, nb = b->seg_nb;
+  if (col_ptr) DFH_HIP(hipMemcpy(col_ptr, b->d_col_ptr, ((size_t)U + 1) * 4, hipMemcpyDeviceToHost));
+  if (s_row && nnz) DFH_HIP(hipMemcpy(s_row, b->d_s_row, nnz * 4, hipMemcpyDeviceToHost));
+  if (s_val && nnz && b->has_value) DFH_HIP(hipMemcpy(s_val, b->d_s_val, nnz * 4, hipMemcpyDeviceToHost));
+  if (few_desc && nb) DFH_HIP(hipMemcpy(few_desc, b->d_few, nb * sizeof(uint2), hipMemcpyDeviceToHost));
+  if (mid_desc && nb) DFH_HIP(hipMemcpy(mid_desc, b->d_mid, nb * sizeof(uint2), hipMemcpyDeviceToHost));
+  if (hot_desc && nb) DFH_HIP(hipMemcpy(hot_desc, b->d_hot, nb * sizeof(uint2), hipMemcpyDeviceToHost));
+  if (few_ent) DFH_HIP(hipMemcpy(few_ent, b->d_few_ent, b->few_cap * sizeof(SegEnt), hipMemcpyDeviceToHost));
+  if (mid_ent) DFH_HIP(hipMemcpy(mid_ent, b->d_mid_ent, b->mid_cap * sizeof(SegEnt), hipMemcpyDeviceToHost));
+  if (hot_ent) DFH_HIP(hipMemcpy(hot_ent, b->d_hot_ent, b->hot_cap * sizeof(SegEnt), hipMemcpyDeviceToHost));
+  const size_t ns = std::min<size_t>(sn, b->split_cap);
+  if (split_ent && ns) DFH_HIP(hipMemcpy(split_ent, b->d_split_ent, ns * sizeof(SegEnt), hipMemcpyDeviceToHost));
+  if (bstart && b->view_P) DFH_HIP(hipMemcpy(bstart, b->d_bstart, ((size_t)b->view_P + 1) * 4, hipMemcpyDeviceToHost));
   return DFH_OK;
 }
 

@@ -361,6 +361,27 @@ int dfh_batch_get_pred(dfh_batch* b, float* pred);                  /* synchroni
  * localized.  Read-only; synchronises. */
 int dfh_batch_split_entries(dfh_batch* b, uint32_t* n);
 
+/* The localized minibatch as the backward and update passes walk it, read back for the tests: the key-ordered view and the
+ * segment lists.  dfh_batch_key_view_info gives the sizes to allocate; dfh_batch_get_key_view fills host arrays (any may be
+ * NULL).  Both synchronise the way dfh_batch_shape does, launch nothing and write no batch state: a step taken afterwards
+ * gives the bits it would have given without them.  A batch that is not localized is refused and stays usable. */
+typedef struct dfh_key_view_info {
+  uint64_t U, nnz;
+  uint32_t has_value;   /* 0: a binary minibatch, there is no s_val */
+  uint32_t seg_nb;      /* list buckets: every list has seg_nb {cnt, off} descriptors */
+  uint32_t P;           /* sort buckets, where the view came out of the sample sort (then seg_nb == P); else 0 */
+  uint32_t split_n;     /* entries of the split list: what dfh_batch_split_entries reads */
+  uint64_t few_cap, mid_cap, hot_cap, split_cap;   /* entries the four arrays were allocated for (dfh_batch_create) */
+  uint32_t bwd_small, bwd_mid, hot_split, hot_split_min;   /* the class bounds the library was built with */
+} dfh_key_view_info;
+int dfh_batch_key_view_info(dfh_batch* b, dfh_key_view_info* out);
+/* col_ptr [U + 1], s_row [nnz], s_val [nnz] (ignored for a binary minibatch); few / mid / hot: desc [seg_nb][2] = {cnt, off}
+ * and ent [cap][4] = the WHOLE entry array {u, beg, end, 0}, of which only the ranges [off, off + cnt) of the descriptors
+ * mean anything; split_ent [split_n][4] = {u, beg_p, end_p, p << 16 | nparts}; bstart [P + 1] where P > 0. */
+int dfh_batch_get_key_view(dfh_batch* b, uint32_t* col_ptr, uint32_t* s_row, float* s_val, uint32_t* few_desc, uint32_t* few_ent,
+                           uint32_t* mid_desc, uint32_t* mid_ent, uint32_t* hot_desc, uint32_t* hot_ent, uint32_t* split_ent,
+                           uint32_t* bstart);
+
 /* -------------------------------------------- sharded (multi-GPU) building blocks */
 /* Rows cross the wire in a fixed-stride layout of dfh_row_stride(V_dim) floats:
  *   [w, has_V (0/1 as float), 0, 0 | V[0..V_dim) zero-padded to a multiple of 4]

@@ -12,7 +12,8 @@ How the pairs land in one bucket (dfh_api.hip: localize_impl; nothing here depen
   * 1 024 pairs: a first minibatch of 300 pairs whose keys all have the top byte 0xFF leaves P = 2 and a splitter with such a
     key; a second minibatch whose keys are all smaller falls into bucket 0 as a whole (1 024 = the LDS capacity).
 
-Nothing the C API returns shows the bucket count, so the one-bucket premise above is NOT asserted here: it holds for LOC_MIN_AVG = 48,
+The one-bucket premise above is NOT asserted here (dfh_batch_get_key_view shows the bucket starts since; tests/test_key_view.py
+asserts the premises of its own designs through it): it holds for LOC_MIN_AVG = 48,
 LOC_MAX_AVG = 700 (dfh_localize.hip), DFH_LOC_SMALL_AVG = 192 (dfh_api.hip) and splitters = the previous minibatch's quantiles; a
 change to any of them turns the larger cases into ordinary multi-bucket sorts (still correct, no longer this file's subject).  A
 comment next to the constants points back here.
@@ -20,7 +21,7 @@ comment next to the constants points back here.
 What these cases can NOT see is the order of the tags among equal keys: U, feaids, feacnt and index are the same whichever
 order equal keys end up in (all_equal gives one key and an all-zero index).  A comparator that ignored the tag would only show
 here when it loses a pair.  The tie order decides the order of the key-ordered (row, value) view the update sums over: it is
-pinned by the training-step parity tests of tests/test_gpu_parity.py, which read that view, not by this file.
+pinned exactly by tests/test_key_view.py, which reads that view back, not by this file.
 
 The expectation is numpy's stable sort of (ReverseBytes(id), position) (Localizer::Compact, localizer.cc:22-77); the CPU test
 checks that expectation against the oracle's Localizer on every case, the GPU tests check the device against it.
