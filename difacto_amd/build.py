@@ -25,7 +25,8 @@ def hip_sources():
 
 
 def build_hip(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -> difacto_amd/libdifacto_hip.so"""
+    """hipcc --offload-arch=gfx950 -> difacto_amd/libdifacto_hip.so: one translation unit, dfh_api.hip, which includes the
+    other files of csrc/ (dfh_rowstore.hip last); hip_sources() lists them all for the staleness check"""
     if not force and not _newer(LIB, hip_sources()):
         return LIB
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",

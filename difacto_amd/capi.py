@@ -46,6 +46,8 @@ SYMBOLS = [
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
     "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
+    "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
+    "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
@@ -195,6 +197,15 @@ def lib():
     L.dfh_crb_encode_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, PP(sz)]
     L.dfh_crb_encode_textchunk.argtypes = [vp, vp, PP(sz)]
     L.dfh_crb_record.argtypes = [vp, vp]
+    L.dfh_rowstore_create.argtypes = [vp, sz, PP(vp)]
+    L.dfh_rowstore_destroy.argtypes = [vp]
+    L.dfh_rowstore_append_host.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    L.dfh_rowstore_append_textchunk.argtypes = [vp, vp]
+    L.dfh_rowstore_shape.argtypes = [vp, PP(C.c_uint64), PP(C.c_uint64), PP(i32), PP(i32), PP(C.c_uint64)]
+    L.dfh_rowstore_order.argtypes = [vp, i32, C.c_uint64]
+    L.dfh_rowstore_get_order.argtypes = [vp, vp]
+    L.dfh_rowstore_read.argtypes = [vp, C.c_uint64, sz, vp, vp, vp, vp, vp, PP(sz)]
+    L.dfh_crb_encode_rowstore.argtypes = [vp, vp, C.c_uint64, sz, PP(sz)]
     L.dfh_eval_create.argtypes = [vp, sz, PP(vp)]
     L.dfh_eval_destroy.argtypes = [vp]
     L.dfh_eval_reset.argtypes = [vp]
@@ -705,9 +716,69 @@ class CrbEncoder:
         _ck(lib().dfh_crb_encode_textchunk(self.h, tc.h, C.byref(n)))
         return self._record(n.value)
 
+    def encode_rowstore(self, store, first, count):
+        """the record of rows order[first .. first + count) of the ordered RowStore `store`"""
+        n = C.c_size_t(0)
+        _ck(lib().dfh_crb_encode_rowstore(self.h, store.h, first, count, C.byref(n)))
+        return self._record(n.value)
+
     def close(self):
         if self.h:
             lib().dfh_crb_destroy(self.h)
+            self.h = None
+
+
+class RowStore:
+    """the rows of a whole data set in HBM (dfh_rowstore): appended chunk by chunk, ordered once, read or encoded block by block"""
+
+    def __init__(self, ctx, slab_bytes=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _ck(lib().dfh_rowstore_create(ctx.h, slab_bytes, C.byref(self.h)))
+
+    def append_host(self, offset, label, index=None, value=None, weight=None):
+        """offset u64 [nrows + 1], label f32 [nrows], index u64 / value f32 [nnz] (the chunk's own), weight f32 [nrows]"""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        label = np.ascontiguousarray(label, np.float32)
+        arrs = [None if a is None else np.ascontiguousarray(a, t) for a, t in ((index, np.uint64), (value, np.float32), (weight, np.float32))]
+        ptr = [None if a is None else (_p(a) if a.size else C.create_string_buffer(8)) for a in arrs]
+        lab = _p(label) if label.size else C.create_string_buffer(8)
+        _ck(lib().dfh_rowstore_append_host(self.h, len(offset) - 1, _p(offset), lab, ptr[0], ptr[1], ptr[2]))
+
+    def append_textchunk(self, tc):
+        """the regular chunk last parsed into the TextChunk `tc`, device to device"""
+        _ck(lib().dfh_rowstore_append_textchunk(self.h, tc.h))
+
+    def shape(self):
+        """-> dict(nrows, nnz, has_value, has_weight, device_bytes)"""
+        nrows, nnz, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        hv, hw = C.c_int(0), C.c_int(0)
+        _ck(lib().dfh_rowstore_shape(self.h, C.byref(nrows), C.byref(nnz), C.byref(hv), C.byref(hw), C.byref(nb)))
+        return dict(nrows=nrows.value, nnz=nnz.value, has_value=bool(hv.value), has_weight=bool(hw.value), device_bytes=nb.value)
+
+    def order(self, shuffle, seed=0):
+        _ck(lib().dfh_rowstore_order(self.h, int(shuffle), seed))
+
+    def get_order(self):
+        out = np.zeros(max(self.shape()["nrows"], 1), np.uint32)
+        _ck(lib().dfh_rowstore_get_order(self.h, _p(out)))
+        return out[:self.shape()["nrows"]]
+
+    def read(self, first, count):
+        """rows order[first .. first + count) -> (offset u64 [count + 1], label, index, value, weight | None)"""
+        off = np.zeros(count + 1, np.uint64)
+        lab = np.zeros(max(count, 1), np.float32)
+        nnz = C.c_size_t(0)
+        _ck(lib().dfh_rowstore_read(self.h, first, count, _p(off), _p(lab), None, None, None, C.byref(nnz)))
+        idx = np.zeros(max(nnz.value, 1), np.uint64)
+        val = np.zeros(max(nnz.value, 1), np.float32)
+        wgt = np.zeros(max(count, 1), np.float32) if self.shape()["has_weight"] else None
+        _ck(lib().dfh_rowstore_read(self.h, first, count, _p(off), _p(lab), _p(idx), _p(val), _p(wgt), C.byref(nnz)))
+        return off, lab[:count], idx[:nnz.value], val[:nnz.value], None if wgt is None else wgt[:count]
+
+    def close(self):
+        if self.h:
+            lib().dfh_rowstore_destroy(self.h)
             self.h = None
 
 

@@ -35,7 +35,8 @@ struct dfh_crb {
   uint2* d_segpos = nullptr;    // [segments] {output position, start of the literals that come in}
   uint4* d_head = nullptr;      // [5] {block size, start of the last literals, their output position, 0}
   uint32_t* h_head = nullptr;   // page-locked copy
-  size_t cap_in = 0, cap_out = 0, cap_seq = 0, cap_meta = 0, cap_segpos = 0;
+  char* d_gather = nullptr;     // labels, offsets and weights of a block gathered out of a row store (dfh_rowstore.hip)
+  size_t cap_in = 0, cap_out = 0, cap_seq = 0, cap_meta = 0, cap_segpos = 0, cap_gather = 0;
   // the last encode
   int nrows = 0;
   size_t out_at[5] = {0, 0, 0, 0, 0};
@@ -345,7 +346,8 @@ int dfh_crb_destroy(dfh_crb* e) {
   hipSetDevice(e->ctx->device);
   if (e->s) hipStreamSynchronize(e->s);
   if (e->ev) hipEventDestroy(e->ev);
-  for (void* p : {(void*)e->d_in, (void*)e->d_out, (void*)e->d_seq, (void*)e->d_meta, (void*)e->d_segpos, (void*)e->d_head})
+  for (void* p : {(void*)e->d_in, (void*)e->d_out, (void*)e->d_seq, (void*)e->d_meta, (void*)e->d_segpos, (void*)e->d_head,
+                  (void*)e->d_gather})
     if (p) hipFree(p);
   if (e->h_head) hipHostFree(e->h_head);
   if (e->s) hipStreamDestroy(e->s);

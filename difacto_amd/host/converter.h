@@ -3,10 +3,15 @@
  * .rec file, one RecordIO record of one CompressedRowBlock per chunk.  The row blocks are compressed ON THE DEVICE
  * (csrc/dfh_lz4enc.hip through dfh_crb_*: the product carries no liblz4 and there is no host encoder); with text_parse = device
  * the chunks of a criteo file are parsed there too and their ids never leave HBM between the parse and the encoder.
+ * shuffle_rows / val_fraction: the rows of the whole input are first collected in one row store in HBM (csrc/dfh_rowstore.hip),
+ * ordered there, and the records of data_out and data_val_out are gathered out of that order (WriteOrdered).
  */
 #ifndef DIFACTO_HOST_CONVERTER_H_
 #define DIFACTO_HOST_CONVERTER_H_
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <deque>
 #include <future>
 #include <memory>
@@ -40,7 +45,19 @@ struct ConverterParam : public dmlc::Parameter<ConverterParam> {
   int part_size;
   /** \brief host (default) | device: where criteo text is parsed */
   std::string text_parse;
+  /** \brief 1: the rows of the whole input are written in a shuffled order (dfh_rowstore_order); 0 (default): in file order */
+  int shuffle_rows;
+  /** \brief the seed of that order */
+  uint64_t shuffle_seed;
+  /** \brief the last floor(val_fraction * n) rows of the order go to data_val_out instead of data_out; in [0, 1), default 0 */
+  double val_fraction;
+  /** \brief the validation output, in data_out_format; always one file */
+  std::string data_val_out;
   DMLC_DECLARE_PARAMETER(ConverterParam) {
+    DMLC_DECLARE_FIELD(shuffle_rows).set_default(0);
+    DMLC_DECLARE_FIELD(shuffle_seed).set_default(0);
+    DMLC_DECLARE_FIELD(val_fraction).set_default(0);
+    DMLC_DECLARE_FIELD(data_val_out).set_default("");
     DMLC_DECLARE_FIELD(data_in).set_default("");
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_out).set_default("");
@@ -67,6 +84,16 @@ class Converter {
     CHECK(param_.text_parse != "device" || param_.data_format == "criteo" || param_.data_format == "criteo_test")
         << "text_parse=device with data_format=" << param_.data_format << ": the device parses criteo and criteo_test text only";
     CHECK_GT(param_.chunk_size, 0) << "chunk_size is a size in MB";
+    CHECK(param_.shuffle_rows == 0 || param_.shuffle_rows == 1)
+        << "shuffle_rows=" << param_.shuffle_rows << " is not one of 0 (file order, the default) and 1";
+    CHECK(param_.val_fraction >= 0 && param_.val_fraction < 1)
+        << "val_fraction=" << param_.val_fraction << ": the share of the rows that goes to data_val_out lies in [0, 1)";
+    CHECK(!(param_.val_fraction > 0) || !param_.data_val_out.empty())
+        << "val_fraction=" << param_.val_fraction << " needs data_val_out, the file the validation rows are written to";
+    CHECK(param_.val_fraction > 0 || param_.data_val_out.empty())
+        << "data_val_out=" << param_.data_val_out << " with val_fraction=0: no row would be written to it; give val_fraction";
+    CHECK(param_.data_val_out.empty() || param_.data_val_out != param_.data_out)
+        << "data_val_out and data_out are the same file, " << param_.data_out;
     return remain;
   }
 
@@ -84,6 +111,16 @@ class Converter {
     // a small pool of encoders: the encode of chunk t + 1 runs while the record of chunk t is copied back and written
     std::vector<dfh_crb*> pool(rec ? kEncoders : 0, nullptr);
     for (auto& e : pool) DFH_CALL(dfh_crb_create(ctx, &e));
+    out_name_ = param_.data_out;
+    parts_ = param_.part_size >= 0;
+    if (param_.shuffle_rows || param_.val_fraction > 0) {
+      WriteOrdered(ctx, &in, pool);
+      for (auto e : pool) dfh_crb_destroy(e);
+      Close();
+      LOG(INFO) << "done. written " << nwrite_ << " bytes";
+      if (hook) text_parse.Log(param_.data_in);
+      return;
+    }
     std::deque<std::future<Encoded>> pending;   // in file order
     size_t taken = 0;
     std::shared_ptr<RowChunk> chunk;
@@ -129,13 +166,109 @@ class Converter {
     DFH_CALL(dfh_crb_record(e, &out.record[0]));
     return out;
   }
+  static Encoded EncodeRows(dfh_crb* e, dfh_rowstore* st, uint64_t first, size_t count) {
+    Encoded out;
+    out.nrows = count;
+    size_t bytes = 0;
+    DFH_CALL(dfh_crb_encode_rowstore(e, st, first, count, &bytes));
+    out.record.resize(bytes);
+    DFH_CALL(dfh_crb_record(e, &out.record[0]));
+    return out;
+  }
+  /*!
+   * \brief shuffle_rows / val_fraction: every chunk is appended to one row store in HBM, in file order (a regular device-parsed
+   * chunk device to device); at the end of the input the order is fixed once, and the outputs are cut out of it in records of
+   * R = ceil(n / C) rows, C the input's non-empty chunks — the record size of an unshuffled conversion.  Nothing can be written
+   * before the last chunk is in.  An input that does not fit in HBM ends the run with the store's capacity message
+   */
+  void WriteOrdered(dfh_ctx* ctx, Reader* in, const std::vector<dfh_crb*>& pool) {
+    dfh_rowstore* st = nullptr;
+    const char* slab = getenv("DIFACTO_SLAB_BYTES");   // (tests: many slabs out of a small input)
+    DFH_CALL(dfh_rowstore_create(ctx, slab ? static_cast<size_t>(atoll(slab)) : 0, &st));
+    std::shared_ptr<void> owner(st, [](void* p) { dfh_rowstore_destroy(static_cast<dfh_rowstore*>(p)); });
+    uint64_t chunks = 0;
+    std::shared_ptr<RowChunk> chunk;
+    while (in->NextShared(&chunk)) {
+      const RowChunk& c = *chunk;
+      const size_t nrows = c.offset.size() - 1;
+      if (nrows == 0) continue;
+      ++chunks;
+      if (c.on_device) {
+        DFH_CALL(dfh_rowstore_append_textchunk(st, static_cast<dfh_textchunk*>(c.dev.get())));
+      } else {
+        const size_t first = c.offset[0];
+        DFH_CALL(dfh_rowstore_append_host(st, nrows, c.offset.data(), c.label.data(), c.index.empty() ? nullptr : c.index.data() + first,
+                                          c.value.empty() ? nullptr : c.value.data() + first, c.weight.empty() ? nullptr : c.weight.data()));
+      }
+      chunk.reset();
+    }
+    DFH_CALL(dfh_rowstore_order(st, param_.shuffle_rows, param_.shuffle_seed));
+    uint64_t n = 0, nnz = 0, device_bytes = 0;
+    int has_value = 0, has_weight = 0;
+    DFH_CALL(dfh_rowstore_shape(st, &n, &nnz, &has_value, &has_weight, &device_bytes));
+    const uint64_t n_val = static_cast<uint64_t>(std::floor(param_.val_fraction * static_cast<double>(n)));
+    const uint64_t R = std::max<uint64_t>(chunks ? (n + chunks - 1) / chunks : 1, 1);
+    LOG(INFO) << "ordered " << n << " rows in HBM (" << device_bytes << " bytes): " << n - n_val << " training and " << n_val
+              << " validation rows, records of " << R << " rows, shuffle_rows=" << param_.shuffle_rows << " shuffle_seed=" << param_.shuffle_seed;
+    WriteRows(st, pool, 0, n - n_val, R, has_value != 0, has_weight != 0);
+    if (param_.data_val_out.empty()) return;
+    Close();
+    LOG(INFO) << "done. written " << nwrite_ << " bytes";
+    out_name_ = param_.data_val_out;
+    parts_ = false;
+    nwrite_ = nrows_ = 0;
+    WriteRows(st, pool, n - n_val, n_val, R, has_value != 0, has_weight != 0);
+  }
+  /*! \brief rows order[first .. first + count) to the current output, R per record (per piece of libsvm text) */
+  void WriteRows(dfh_rowstore* st, const std::vector<dfh_crb*>& pool, uint64_t first, uint64_t count, uint64_t R, bool has_value,
+                 bool has_weight) {
+    if (count == 0) NextFile();   // (the file exists even when no row goes to it)
+    if (pool.empty()) {
+      std::vector<size_t> offset;
+      std::vector<real_t> label, value, weight;
+      std::vector<feaid_t> index;
+      for (uint64_t at = first; at < first + count; at += R) {
+        const size_t cnt = static_cast<size_t>(std::min<uint64_t>(R, first + count - at));
+        size_t nnz = 0;
+        offset.resize(cnt + 1);
+        label.resize(cnt);
+        DFH_CALL(dfh_rowstore_read(st, at, cnt, offset.data(), label.data(), nullptr, nullptr, nullptr, &nnz));
+        index.resize(std::max<size_t>(nnz, 1));
+        if (has_value) value.resize(std::max<size_t>(nnz, 1));
+        if (has_weight) weight.resize(cnt);
+        DFH_CALL(dfh_rowstore_read(st, at, cnt, offset.data(), label.data(), index.data(), has_value ? value.data() : nullptr,
+                                   has_weight ? weight.data() : nullptr, &nnz));
+        dmlc::RowBlock<feaid_t> blk;
+        blk.size = cnt;
+        blk.offset = offset.data();
+        blk.label = label.data();
+        blk.weight = has_weight ? weight.data() : nullptr;
+        blk.index = index.data();
+        blk.value = has_value ? value.data() : nullptr;
+        WriteLibsvm(blk);
+      }
+      return;
+    }
+    std::deque<std::future<Encoded>> pending;   // in the order's order
+    size_t taken = 0;
+    for (uint64_t at = first; at < first + count; at += R) {
+      const size_t cnt = static_cast<size_t>(std::min<uint64_t>(R, first + count - at));
+      if (pending.size() == pool.size()) {
+        WriteRecord(pending.front().get());
+        pending.pop_front();
+      }
+      dfh_crb* e = pool[taken++ % pool.size()];
+      pending.push_back(std::async(std::launch::async, [e, st, at, cnt] { return EncodeRows(e, st, at, cnt); }));
+    }
+    for (; !pending.empty(); pending.pop_front()) WriteRecord(pending.front().get());
+  }
   /*! \brief a new part when there is no file yet, or the current one holds part_size MB (converter.h:68-79) */
   void NextFile() {
-    const bool parts = param_.part_size >= 0;
+    const bool parts = parts_;
     if (out_ && !(parts && nwrite_ / 1000000 >= static_cast<size_t>(param_.part_size))) return;
     if (out_) LOG(INFO) << "done. written " << nwrite_ << " bytes";
     Close();
-    const std::string name = parts ? param_.data_out + "-part_" + std::to_string(ipart_++) : param_.data_out;
+    const std::string name = parts ? out_name_ + "-part_" + std::to_string(ipart_++) : out_name_;
     out_ = fopen(name.c_str(), "wb");
     CHECK(out_ != nullptr) << "cannot open " << name << " for writing";
     nwrite_ = 0;
@@ -179,6 +312,8 @@ class Converter {
 
   ConverterParam param_;
   FILE* out_ = nullptr;
+  std::string out_name_;   // the output being written: data_out (or the prefix of its parts), then data_val_out
+  bool parts_ = false;
   int ipart_ = 0;
   size_t nwrite_ = 0, nrows_ = 0;
   std::string framed_;

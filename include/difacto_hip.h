@@ -306,6 +306,40 @@ int dfh_crb_encode_host(dfh_crb* e, size_t nrows, const size_t* offset, const fl
                         const float* weight, size_t* record_bytes);
 int dfh_crb_encode_textchunk(dfh_crb* e, dfh_textchunk* tc, size_t* record_bytes);
 int dfh_crb_record(dfh_crb* e, void* dst);
+/* task = convert with shuffle_rows / val_fraction: the rows of a whole data set in HBM (csrc/dfh_rowstore.hip).  A dfh_rowstore
+ * holds ids (u64), labels and row lengths, values once a chunk brought some and weights when every chunk brings them.  Ids and
+ * values live in slabs of slab_bytes (0: 64 MiB; 1 KiB .. 16 GiB): a row never straddles two slabs, a row longer than a slab
+ * gets one of its own size, and an append allocates what it adds and copies nothing that is stored.  An allocation that fails is
+ * DFH_ERR_CAPACITY with the bytes it needed in the message and leaves the store as it was; a store holds fewer than 2^32 - 16
+ * rows (DFH_ERR_ARG).
+ * dfh_rowstore_append_host: arguments as dfh_crb_encode_host (index / value are the chunk's own nonzeros; value and weight may
+ * be NULL); dfh_rowstore_append_textchunk: the regular chunk last parsed into `tc`, its ids copied device to device.  Both
+ * return when the source may be reused.  A chunk without values counts as all 1.0f; weights in some chunks and not in others
+ * are DFH_ERR_ARG.  Rows are numbered in the order they were appended, however they were cut into appends; an append drops
+ * the order.
+ * dfh_rowstore_order fixes the order of the rows: shuffle = 0 the identity, shuffle = 1 ascending by (key(r), r), key(r) =
+ * output r of splitmix64 seeded with `seed` (z = seed + (r + 1) 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31; mod 2^64), made and sorted on the device: a stable argsort of the keys.
+ * It may be called again; no encode or read may run beside it.  dfh_rowstore_get_order: order [nrows] (tests).
+ * dfh_rowstore_read: rows order[first .. first + count) on the host: offset [count + 1] from 0, label [count], *nnz, and when
+ * index is not NULL index [*nnz], value [*nnz] (all 1.0f from a store without values) and weight [count] (only of a store
+ * that has weights); value and weight may be NULL.  A caller that does not know *nnz asks with index = NULL first.
+ * dfh_crb_encode_rowstore: the same rows gathered on the encoder's stream into its own staging and encoded: byte for byte
+ * the record dfh_crb_encode_host gives for them with offsets from 0 (values that are all 1.0f in the block are dropped).
+ * Several encoders may work on one ordered store from different threads.  Without an order read and encode are
+ * DFH_ERR_STATE; first + count > nrows is DFH_ERR_ARG. */
+typedef struct dfh_rowstore dfh_rowstore;
+int dfh_rowstore_create(dfh_ctx* c, size_t slab_bytes, dfh_rowstore** out);
+int dfh_rowstore_destroy(dfh_rowstore* st);
+int dfh_rowstore_append_host(dfh_rowstore* st, size_t nrows, const size_t* offset, const float* label, const uint64_t* index,
+                             const float* value, const float* weight);
+int dfh_rowstore_append_textchunk(dfh_rowstore* st, dfh_textchunk* tc);
+int dfh_rowstore_shape(dfh_rowstore* st, uint64_t* nrows, uint64_t* nnz, int* has_value, int* has_weight, uint64_t* device_bytes);
+int dfh_rowstore_order(dfh_rowstore* st, int shuffle, uint64_t seed);
+int dfh_rowstore_get_order(dfh_rowstore* st, uint32_t* order);
+int dfh_rowstore_read(dfh_rowstore* st, uint64_t first, size_t count, size_t* offset, float* label, uint64_t* index, float* value,
+                      float* weight, size_t* nnz);
+int dfh_crb_encode_rowstore(dfh_crb* e, dfh_rowstore* st, uint64_t first, size_t count, size_t* record_bytes);
 /* dfh_rowbuf_load_host_slices whose slices are either host arrays (chunk = NULL; value may be NULL = all ones) or ids
  * [first, first + nnz) of a regular parsed chunk (index and value unused; no values), copied device to device on the
  * buffer's stream.  Same contract: it returns when the sources may be reused (the chunk may be parsed into again). */
