@@ -251,7 +251,9 @@ def test_golden_localizer(capi, ctx, rcv1):
 def test_store_trajectory_vs_oracle(capi, ctx, oracle, V_dim, mode):
     """Pull / Push(kFeaCount) / Push(kGradient) over several batches and epochs:
     FTRL(w), AdaGrad(V), lazy InitV.  Gradients come from the oracle so only the
-    store is under test."""
+    store is under test: both stores apply the same operations to the same values (ftrl_update_w / adagrad_update_v are
+    the reference's operation for operation), so the pulled values and, after every push, every field of every entry
+    are compared as bit patterns."""
     from oracle import bindings as ob
     rng = np.random.default_rng(70 + V_dim)
     kw = dict(V_dim=V_dim, l1=0.05, l2=0.01, lr=0.2, V_lr=0.1, V_l2=0.02, V_threshold=2, V_init_scale=0.3, seed=3)
@@ -270,13 +272,23 @@ def test_store_trajectory_vs_oracle(capi, ctx, oracle, V_dim, mode):
             vo, lo = so.pull(loc["feaids"])
             vg, lg = tb.pull(loc["feaids"])
             assert np.array_equal(lo, lg), (epoch, "lens")
-            assert_close(vg, vo, what="pulled weights epoch %d" % epoch, rtol=2e-5)
+            assert np.array_equal(vg.view(np.uint32), vo.view(np.uint32)), "pulled weights epoch %d" % epoch
             saw_v = saw_v or bool(np.any(lo > 1))
             w_pos, V_pos = oracle.get_pos(lo) if V_dim else (None, None)
             pred = oracle.fm_predict(V_dim, loc["offset"], loc["index"], b["value"], vo, w_pos, V_pos)
             grad = oracle.fm_calcgrad(V_dim, loc["offset"], loc["index"], b["value"], b["label"], vo, pred, w_pos, V_pos)
             so.push(loc["feaids"], ob.GRADIENT, grad, lo)
             tb.push(loc["feaids"], capi.GRADIENT, grad, lg)
+            # the whole table after the step: fea_cnt, w, sqrt_g, z, has_V, V and accumulators of every key
+            ek, escal, ehas, eV = _export_index(tb)
+            assert len(ek) == so.size()
+            for i, key in enumerate(ek):
+                o = so.peek(int(key))
+                want = np.array([o["fea_cnt"], o["w"], o["sqrt_g"], o["z"]], np.float32)
+                assert np.array_equal(escal[i].view(np.uint32), want.view(np.uint32)), (epoch, int(key), escal[i], want)
+                assert bool(ehas[i]) == (o["V"] is not None), (epoch, int(key))
+                if o["V"] is not None:
+                    assert np.array_equal(eV[i].view(np.uint32), o["V"].view(np.uint32)), (epoch, int(key))
     assert tb.size() == so.size()
     assert saw_v == (V_dim > 0)
     tb.close()
@@ -1271,8 +1283,12 @@ def test_owner_side_forms_match_per_source_calls(capi, ctx, V_dim, form, G):
     vb, lb = tb.pull(universe)
     assert np.array_equal(la, lb)
     assert (la > 1).any() or V_dim == 0
-    assert_close(va, vb, rtol=1e-6, what="weights")
+    assert np.array_equal(va.view(np.uint32), vb.view(np.uint32)), "weights"
     assert ta.size() == tb.size()
+    # the same values in the same order on both tables: every field of every entry, as bit patterns
+    for x, y, name in zip(_export_index(ta), _export_index(tb), ("keys", "fea_cnt | w | sqrt_g | z", "has_V", "V | accumulators")):
+        assert (x is None and y is None) or np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x,
+                                                           y.view(np.uint32) if y.dtype == np.float32 else y), name
     if form in ("multi", "listed"):  # every source mask was cleared: a fresh multi step must see clean rows
         keys = torch.from_numpy(universe[:100].view(np.int64).copy()).to(dev)
         rowid = torch.empty(capi.multi_words(100, 2), dtype=torch.int32, device=dev)
@@ -1296,7 +1312,7 @@ def test_owner_side_forms_match_per_source_calls(capi, ctx, V_dim, form, G):
         tb.shard_push_grad(keys, 100, grads)
         v2a, _ = ta.pull(universe[:100])
         v2b, _ = tb.pull(universe[:100])
-        assert_close(v2a, v2b, rtol=1e-6, what="weights after a clean multi step")
+        assert np.array_equal(v2a.view(np.uint32), v2b.view(np.uint32)), "weights after a clean multi step"
     for o in (ta, tb):
         o.close()
 
