@@ -628,7 +628,13 @@ __device__ __forceinline__ void upd_singles_tile(const UpdArgs& a, bool valid, u
         const float xx = xs[q];
         // one occurrence: the segmented sums of the other roles with a single term (0 + term)
         const float gw = p != 0.f ? p * xx : 0.f, xxp = p != 0.f ? p * (xx * xx) : 0.f;  // spmv.h:155
-        const float4 g4 = make_float4((xvi.x * p) * xx, (xvi.y * p) * xx, (xvi.z * p) * xx, (xvi.w * p) * xx);
+        float4 g4 = make_float4((xvi.x * p) * xx, (xvi.y * p) * xx, (xvi.z * p) * xx, (xvi.w * p) * xx);
+        if (MIXED) {
+          // that "0 +" spelled out for the V part: where XV_d = 0 (every padded coordinate) the term is a zero with the
+          // sign of p x, and another rank's key carries it to its owner in a gradient row — whose zeros are +0 on every
+          // other role and path.  (The in-place update of an own key gives the same state for either zero.)
+          g4.x += 0.0f; g4.y += 0.0f; g4.z += 0.0f; g4.w += 0.0f;
+        }
         upd_apply<EXACT, MIXED>(a, rr[q] & kRowMask, uu[q], h0[q], vv[q], ac[q], gw, xxp, g4, sub, sub_ok, k, kp, pen, fcs[q], 1.0f,
                                 (rr[q] & kCountLater) != 0u, (rr[q] & kRemoteRow) != 0u);
       }
