@@ -38,6 +38,7 @@ SYMBOLS = [
     "dfh_lbfgs_init_model", "dfh_lbfgs_shape", "dfh_lbfgs_get_model", "dfh_lbfgs_set_weights", "dfh_lbfgs_calc_grad",
     "dfh_lbfgs_prepare_direction", "dfh_lbfgs_calc_direction", "dfh_lbfgs_line_search", "dfh_lbfgs_evaluate", "dfh_lbfgs_create_sharded",
     "dfh_lbfgs_owned_range", "dfh_lbfgs_set_model", "dfh_lbfgs_get_vector", "dfh_bcd_set_model",
+    "dfh_lbfgs_set_l1", "dfh_lbfgs_get_owlqn_vector", "dfh_lbfgs_drop_last_pair", "dfh_lbfgs_get_owlqn_moved",
     "dfh_bcd_create", "dfh_bcd_destroy", "dfh_bcd_add_chunk", "dfh_bcd_build", "dfh_bcd_shape", "dfh_bcd_block_info",
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
     "dfh_bcd_create_sharded",
@@ -292,6 +293,10 @@ def lib():
     L.dfh_lbfgs_line_search.argtypes = [vp, f32, f32, PP(f32), PP(f32), PP(f32)]
     L.dfh_lbfgs_evaluate.argtypes = [vp, PP(f32), PP(f32), PP(f32)]
     L.dfh_lbfgs_get_vector.argtypes = [vp, i32, i32, vp]
+    L.dfh_lbfgs_set_l1.argtypes = [vp, f32]
+    L.dfh_lbfgs_get_owlqn_vector.argtypes = [vp, i32, vp]
+    L.dfh_lbfgs_drop_last_pair.argtypes = [vp]
+    L.dfh_lbfgs_get_owlqn_moved.argtypes = [vp, dp]
     L.dfh_bcd_create.argtypes = [vp, PP(vp)]
     L.dfh_bcd_create_sharded.argtypes = [vp, vp, PP(vp)]
     L.dfh_bcd_destroy.argtypes = [vp]
@@ -1164,6 +1169,26 @@ class Lbfgs:
         out = np.zeros(max(self.n, 1), np.float32)
         _ck(lib().dfh_lbfgs_get_vector(self.h, int(which), int(i), _p(out)))
         return out[:self.n]
+
+    def set_l1(self, l1):
+        """l1 on w (OWL-QN), after init_model and before the first calc_grad; 0 changes nothing"""
+        _ck(lib().dfh_lbfgs_set_l1(self.h, l1))
+
+    def owlqn_vector(self, which):
+        """-> a copy of the pseudo-gradient (which = 0) or of the line search's origin w0 (1) [n]"""
+        out = np.zeros(max(self.n, 1), np.float32)
+        _ck(lib().dfh_lbfgs_get_owlqn_vector(self.h, int(which), _p(out)))
+        return out[:self.n]
+
+    def drop_last_pair(self):
+        """between prepare_direction and calc_direction: drop the newest (s, y) pair"""
+        _ck(lib().dfh_lbfgs_drop_last_pair(self.h))
+
+    def owlqn_moved(self):
+        """-> elements the last line_search trial moved off w0"""
+        v = C.c_double(0)
+        _ck(lib().dfh_lbfgs_get_owlqn_moved(self.h, C.byref(v)))
+        return v.value
 
     def close(self):
         if self.h:

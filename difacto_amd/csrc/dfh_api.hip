@@ -3223,6 +3223,7 @@ int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n,
 #include "dfh_join.hip"
 #include "dfh_chunks.hip"
 #include "dfh_lbfgs.hip"
+#include "dfh_owlqn.hip"   // l1 on w for learner = lbfgs: the orthant-wise forms of its vector passes
 #include "dfh_bcd.hip"
 #include "dfh_eval.hip"   // whole-set evaluation: exact AUC, logloss and accuracy of the appended (label, prediction) rows
 #include "dfh_rowstore.hip"   // the rows of a whole data set in HBM, their shuffled order, and blocks gathered out of it for the encoder

@@ -16,6 +16,9 @@
 // are joined onto the object's ascending keys on the device (dfh_join.hip); k_lb_set_model copies a matched key's w, and
 // its V where both sides carry one, into the ragged model.  Every other float keeps what InitWeight gave it.
 //
+// l1 on w (dfh_lbfgs_set_l1 with l1 > 0; the reference declares l1 and comments it out, lbfgs_param.h:84-93): the orthant-wise
+// forms of the three vector passes live in dfh_owlqn.hip, included right after this file; with l1 == 0 nothing here changes.
+//
 // Every reduction is deterministic: per-thread fp64 sums, a fixed-order block reduction into one partial per block
 // (the grid depends on n only), then one ordered pass over the partials.  No float atomics.
 #include <cmath>
@@ -554,6 +557,12 @@ struct dfh_lbfgs {
   std::vector<size_t> own_b, loc_b;   // bytes per peer: owner side (pull send = push receive), worker side (the reverse)
   bool pulled = false;             // d_lw holds the current w
   std::vector<uint64_t> splits;    // [world - 1] first keys of shards 1..: the owner of a key is the number of them <= it
+  // ---- l1 on w (dfh_lbfgs_set_l1 with l1 > 0, dfh_owlqn.hip): the pseudo-gradient and the line search's origin
+  float l1 = 0;
+  void* ow_arena = nullptr;        // d_pg and d_w0, allocated by set_l1
+  float *d_pg = nullptr, *d_w0 = nullptr;
+  bool have_w0 = false;            // a direction has been computed: w0 holds its origin
+  double moved = 0;                // elements the last line-search trial moved off w0, over the ranks
 };
 
 namespace {
@@ -575,6 +584,12 @@ int lb_fetch(dfh_lbfgs* o, const double* d, size_t cnt, std::vector<double>* out
 
 constexpr const char* kLbWho = "dfh_lbfgs";
 constexpr const char* kLbTail = "out-of-core L-BFGS is not supported";
+
+// the l1 > 0 forms of prepare_direction, calc_direction, line_search and of evaluate's r(w), defined in dfh_owlqn.hip
+int ow_prepare_direction(dfh_lbfgs* o, float* incr_B, int* mcur);
+int ow_calc_direction(dfh_lbfgs* o, const float* d, float* p_g);
+int ow_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, float* p_g, float* auc_n);
+int ow_reg(dfh_lbfgs* o, double out[3]);
 
 // forward (+ AUC) over a chunk's rows, its loss / AUC into res[0..1]; with grad, the backward and the scatter into g
 int lb_chunk_pass(dfh_lbfgs* o, dfh_lbfgs::Chunk& ch, bool grad, double* res) {
@@ -715,6 +730,7 @@ int lb_free(dfh_lbfgs* o) {
   if (o->d_part) (void)hipFree(o->d_part);
   if (o->d_res) (void)hipFree(o->d_res);
   if (o->sh_arena) (void)hipFree(o->sh_arena);
+  if (o->ow_arena) (void)hipFree(o->ow_arena);
   delete o;
   return DFH_OK;
 }
@@ -1263,6 +1279,7 @@ int dfh_lbfgs_calc_grad(dfh_lbfgs* o, float gamma, float* loss, float* auc_n) {
 int dfh_lbfgs_prepare_direction(dfh_lbfgs* o, float* incr_B, int* mcur) {
   DFH_ARG(o && o->inited && mcur, "dfh_lbfgs_prepare_direction: bad argument");
   DFH_HIP(hipSetDevice(o->ctx->device));
+  if (o->l1 > 0.f) return ow_prepare_direction(o, incr_B, mcur);
   hipStream_t s = o->ctx->stream;
   const uint64_t n = o->n;
   if (!o->have_g) {  // epoch 0: g = g_new + grad r(w), no history yet (lbfgs_updater.h:89-90)
@@ -1325,6 +1342,7 @@ int dfh_lbfgs_calc_direction(dfh_lbfgs* o, const float* d, float* p_g) {
   DFH_ARG(o && o->inited && o->have_g && p_g, "dfh_lbfgs_calc_direction: bad argument or no gradient prepared");
   DFH_ARG(o->y_count == 0 || d, "dfh_lbfgs_calc_direction: the coefficients are missing");
   DFH_HIP(hipSetDevice(o->ctx->device));
+  if (o->l1 > 0.f) return ow_calc_direction(o, d, p_g);
   const int k = o->y_count;
   lb::CombArgs ca{};
   if (k) {
@@ -1368,6 +1386,7 @@ int dfh_lbfgs_calc_direction(dfh_lbfgs* o, const float* d, float* p_g) {
 int dfh_lbfgs_line_search(dfh_lbfgs* o, float alpha, float gamma, float* objv, float* p_g, float* auc_n) {
   DFH_ARG(o && o->inited && o->s_count > 0 && objv && p_g, "dfh_lbfgs_line_search: bad argument or no direction");
   DFH_HIP(hipSetDevice(o->ctx->device));
+  if (o->l1 > 0.f) return ow_line_search(o, alpha, gamma, objv, p_g, auc_n);
   const float* p = lb_s(o, o->s_count - 1);
   double r[3];
   int rc = lb_wstep(o, p, alpha - o->alpha, r);   // Add(alpha - alpha_, p, &w)
@@ -1402,7 +1421,7 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
   DFH_ARG(o && o->inited, "dfh_lbfgs_evaluate: the model is not initialised");
   DFH_HIP(hipSetDevice(o->ctx->device));
   double r[3];
-  int rc = lb_wstep(o, nullptr, 0.f, r);
+  int rc = o->l1 > 0.f ? ow_reg(o, r) : lb_wstep(o, nullptr, 0.f, r);
   if (rc) return rc;
   if (nnz_w) *nnz_w = (float)r[2];
   if (r_w) *r_w = (float)r[0];

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <iomanip>
 #include <memory>
 #include <thread>
 #include "./batch_reader.h"
@@ -89,6 +90,7 @@ void LBFGSLearner::InitServer(std::vector<real_t>* rets) {
   uint64_t nkeys = 0, n = 0;
   DFH_CALL(dfh_lbfgs_init_model(obj_, static_cast<float>(p.tail_feature_filter), p.V_threshold, p.V_init_scale, p.l2, p.V_l2,
                                 &nkeys, &n));
+  DFH_CALL(dfh_lbfgs_set_l1(obj_, p.l1));   // l1 = 0 leaves the object as it is; r(w) below includes l1 |w|
   if (updater_.weight_initializer()) {  // SetWeightInitializer (lbfgs_updater.h:54-56): weight_lens_ is empty without V
     SArray<int> lens;
     SArray<real_t> w(n, 0);
@@ -123,6 +125,17 @@ float LBFGSLearner::Direction() {
   }
   incr.resize(6 * hist + 1);
   twoloop_.ApplyIncreB(incr);
+  // orthant-wise: without the curvature test a pair can have <s, y> <= 0 (incr_B[hist + hist - 1] = <s_last, y_last>); it
+  // leaves both rings and B before the coefficients divide by it
+  if (updater_.param().l1 > 0 && !(incr[2 * hist - 1] > 0)) {
+    LOG(INFO) << " - <s,y> = " << incr[2 * hist - 1] << " <= 0: the pair is dropped";
+    DFH_CALL(dfh_lbfgs_drop_last_pair(obj_));
+    twoloop_.DropLast();
+    if (--hist == 0) {   // no pair left: p = -pg
+      DFH_CALL(dfh_lbfgs_calc_direction(obj_, nullptr, &pg));
+      return pg;
+    }
+  }
   twoloop_.CalcCoefficients(&coef);
   DFH_CALL(dfh_lbfgs_calc_direction(obj_, coef.data(), &pg));
   return pg;
@@ -132,10 +145,20 @@ real_t LBFGSLearner::LineSearch(real_t step, real_t objv, float pg, float* auc) 
   // backtracking until both Wolfe conditions hold, at most max_num_linesearchs trials (lbfgs_learner.cc:52-73)
   real_t f = objv;
   const int trials = param_.max_num_linesearchs;
+  const bool owlqn = updater_.param().l1 > 0;
   for (int t = 1; t <= trials; ++t, step *= param_.rho) {
     float trial_pg = 0;
     DFH_CALL(dfh_lbfgs_line_search(obj_, step, param_.gamma, &f, &trial_pg, auc));
     LOG(INFO) << " - alpha = " << step << ", objv = " << f << ", <p,g> = " << trial_pg;
+    if (owlqn) {
+      // trial_pg = sum pg (w - w0) of the projected step: sufficient decrease alone, no curvature test
+      if (f <= objv + param_.c1 * trial_pg) {
+        LOG(INFO) << " - sufficient decrease is satisfied";
+        break;
+      }
+      if (t == trials) LOG(INFO) << " - reach the maximal number of linesearch steps [" << t << "]";
+      continue;
+    }
     const bool decrease = f <= objv + param_.c1 * step * pg;   // sufficient decrease
     const bool curvature = trial_pg >= param_.c2 * pg;         // curvature
     if (decrease && curvature) {
@@ -165,10 +188,18 @@ void LBFGSLearner::RunScheduler() {
   DFH_CALL(dfh_lbfgs_calc_grad(obj_, param_.gamma, &loss0, &auc));
   real_t f_prev = init[0] + loss0;   // the scheduler adds the server's and the worker's share
 
+  const bool owlqn = updater_.param().l1 > 0;
+  if (owlqn)
+    LOG(INFO) << "l1 = " << updater_.param().l1 << ": orthant-wise L-BFGS on w; the line search accepts on sufficient "
+              << "decrease alone, c2 is unused";
   real_t prev_val_auc = 0;
   for (int epoch = std::max(param_.load_epoch, 0); epoch < param_.max_num_epochs; ++epoch) {
     LOG(INFO) << "Epoch " << epoch << ":";
     const float pg = Direction();
+    if (owlqn && pg == 0) {   // no descent direction in any orthant: w is optimal
+      LOG(INFO) << " - pseudo-gradient is zero: objv = " << std::setprecision(8) << f_prev << std::setprecision(6) << ", training stops";
+      break;
+    }
     LOG(INFO) << " - start linesearch with objv = " << f_prev << ", <p,g> = " << pg;
     // the first epoch's step: init_alpha, or #examples / #nonzeros when it is not positive
     real_t step = param_.alpha;
@@ -180,11 +211,20 @@ void LBFGSLearner::RunScheduler() {
     DFH_CALL(dfh_lbfgs_evaluate(obj_, nval > 0 ? &val_auc_n : nullptr, &nnz, nullptr));
     lbfgs::Progress prog{f, auc / ntrain, val_auc_n, nnz};
     LOG(INFO) << " - training AUC = " << prog.auc;
+    if (owlqn) LOG(INFO) << " - nnz(w) = " << static_cast<uint64_t>(nnz);
     if (nval > 0) {
       prog.val_auc /= nval;
       LOG(INFO) << " - validation AUC = " << prog.val_auc;
     }
     for (const auto& cb : epoch_end_callback_) cb(epoch, prog);
+    if (owlqn) {
+      double moved = 0;
+      DFH_CALL(dfh_lbfgs_get_owlqn_moved(obj_, &moved));
+      if (moved == 0) {
+        LOG(INFO) << " - no coordinate moved, training stops";
+        break;
+      }
+    }
 
     // stop tests, only once more than min_num_epochs have passed (lbfgs_learner.cc:92-110)
     if (epoch > param_.min_num_epochs) {

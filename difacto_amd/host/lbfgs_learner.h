@@ -19,6 +19,14 @@
  *     of a model file of any learner (optimiser state in the file is ignored; with V_dim > 0 the file's V_dim must be
  *     the job's), a file or the parts of a sharded save; a sharded rank reads its own key range.  The s / y history is
  *     not restored and load_epoch keeps its meaning: the first epoch of the loop
+ *   - l1 (the reference declares it for LBFGSUpdater and comments it out, lbfgs_param.h:84-93): with l1 > 0 the objective
+ *     gains l1 |w|_1 on w (V keeps V_l2) and the learner runs orthant-wise L-BFGS (OWL-QN, Andrew & Gao 2007; the rules
+ *     and their fp32 order are stated in csrc/dfh_owlqn.hip): the direction comes from the pseudo-gradient and is kept
+ *     only where it descends along it; every line-search trial starts from the epoch's w0 and is projected onto its
+ *     orthant; a trial is accepted on sufficient decrease alone, F(w) <= F(w0) + c1 sum pg (w - w0) (c2 is unused, the
+ *     log says so once); s is the real displacement w - w0; a pair with <s, y> <= 0 is dropped before the two-loop
+ *     coefficients; training stops with "pseudo-gradient is zero" when <pg, p> == 0 and with "no coordinate moved" when
+ *     the accepted step changed nothing.  l1 = 0, the default, changes no call and no log line
  *   - a multi-process environment that is not complete (see above) is refused with a message; so is task = predict for
  *     a caller of Learner::Create("lbfgs") (the command line scores a model through learner = sgd's prediction path itself)
  */

@@ -84,6 +84,18 @@ class Twoloop {
     B_ = B;
     m_ = m;
   }
+  /*! \brief forget the newest (s, y) pair after ApplyIncreB: its row and column of B (m - 1 and 2m - 1) leave, the other
+   * products stay what they are.  The orthant-wise learner drops a pair with <s, y> <= 0 this way (lbfgs_learner.h) */
+  void DropLast() {
+    CHECK_GE(m_, 1);
+    const int drop[2] = {2 * m_ - 1, m_ - 1};
+    for (int d : drop) {
+      B_.erase(B_.begin() + d);
+      for (auto& row : B_) row.erase(row.begin() + d);
+    }
+    --m_;
+  }
+  int pairs() const { return m_; }
   void CalcDirection(const std::vector<Vec>& s, const std::vector<Vec>& y, const Vec& grad, Vec* p) {
     p->assign(grad.size(), 0);
     std::vector<double> d(2 * m_ + 1, 0.0), alpha(m_, 0.0);

@@ -1,7 +1,9 @@
 /**
  * lbfgs_param.h — the L-BFGS learner's parameters: the same keys, defaults and ranges as the reference
  * (src/lbfgs/lbfgs_param.h:9-99).  data_cache and num_threads are accepted and have no effect here (the data stay
- * resident in HBM, the work runs on the GPU).
+ * resident in HBM, the work runs on the GPU).  One key more than the reference reads: l1, which its LBFGSUpdaterParam
+ * declares and comments out (:84-93).  Here l1 > 0 trains w by orthant-wise L-BFGS (lbfgs_learner.h); l1 = 0, the
+ * default, is the reference's learner.
  */
 #ifndef DIFACTO_HOST_LBFGS_PARAM_H_
 #define DIFACTO_HOST_LBFGS_PARAM_H_
@@ -50,10 +52,11 @@ struct LBFGSUpdaterParam : public dmlc::Parameter<LBFGSUpdaterParam> {
   int V_threshold;
   float V_init_scale;
   int tail_feature_filter;
-  float l2, V_l2;
+  float l1, l2, V_l2;
   int m;
   DMLC_DECLARE_PARAMETER(LBFGSUpdaterParam) {
     DMLC_DECLARE_FIELD(tail_feature_filter).set_default(4);
+    DMLC_DECLARE_FIELD(l1).set_range(0, 1e10).set_default(0);
     DMLC_DECLARE_FIELD(l2).set_default(.1);
     DMLC_DECLARE_FIELD(V_l2).set_default(.01);
     DMLC_DECLARE_FIELD(V_dim);

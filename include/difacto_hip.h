@@ -710,6 +710,29 @@ int dfh_lbfgs_evaluate(dfh_lbfgs* o, float* val_auc_n, float* nnz_w, float* r_w)
  * Any other which, or an index outside the history, is DFH_ERR_ARG. */
 int dfh_lbfgs_get_vector(dfh_lbfgs* o, int which, int i, float* out);
 
+/* l1 on w: orthant-wise L-BFGS (OWL-QN, Andrew & Gao 2007; csrc/dfh_owlqn.hip states every rule and its fp32 order).
+ * The objective becomes F(w) = loss + sum .5 coef w^2 + l1 sum |w| over the w elements; V keeps V_l2 alone.
+ * dfh_lbfgs_set_l1: after dfh_lbfgs_init_model and before the first dfh_lbfgs_calc_grad (DFH_ERR_STATE later); l1 < 0 or
+ * NaN is DFH_ERR_ARG; l1 == 0 leaves the object as it is and allocates nothing: every launch and bit stays what it is
+ * without the call.  l1 > 0 allocates two more model-sized vectors (the pseudo-gradient pg and the line search's origin
+ * w0; DFH_ERR_CAPACITY with the bytes needed) and from then on, on the plain and the sharded object alike:
+ *   prepare_direction  g stays the SMOOTH gradient g' = g_new + coef w and y_last = g' - g_old; pg is the pseudo-gradient
+ *                      of g'; s_last = w - w0, the real displacement; incr_B has its layout with pg in g's place
+ *   calc_direction     the Add chain over s, y, pg and the clamp, then on w elements p is kept only where it descends along
+ *                      pg (else +0); *p_g = <pg, p>; w0 = w
+ *   line_search        w = w0 + alpha p projected onto the orthant of w0 (of -pg where w0 is 0); *objv = F(w) and
+ *                      *p_g = sum pg (w - w0), the term of the sufficient-decrease test F(w) <= F(w0) + c1 *p_g
+ *   evaluate           r_w includes l1 sum |w| */
+int dfh_lbfgs_set_l1(dfh_lbfgs* o, float l1);
+/* out [nparams]: which 0 = the pseudo-gradient (after the first prepare_direction), 1 = w0 (after the first
+ * calc_direction); only on an object with l1 > 0 */
+int dfh_lbfgs_get_owlqn_vector(dfh_lbfgs* o, int which, float* out);
+/* between prepare_direction and calc_direction: drop the newest (s, y) pair from both rings (a pair with <s, y> <= 0, which
+ * a line search without the curvature test can produce); with no pair left calc_direction takes d = NULL: p = -pg */
+int dfh_lbfgs_drop_last_pair(dfh_lbfgs* o);
+/* elements the last line_search trial moved off w0, summed over the ranks (l1 > 0 only) */
+int dfh_lbfgs_get_owlqn_moved(dfh_lbfgs* o, double* moved);
+
 /* ------------------------------------------------ block coordinate descent (learner = bcd) */
 /* The learner's state, resident in HBM from load to finish: the localized training and validation chunks (one dfh_batch
  * each) with their per-block layouts (a column-major slice for the gradient, a row-major slice for the prediction), the
