@@ -2,8 +2,12 @@
 integer), correct rows and the fp64 logloss sum of everything appended, against the numpy / Python-integer oracle of
 tests/eval_ref.py.  Integer fields must be equal; objv within (n + 16) 2^-52 of the sum of the terms' magnitudes.
 
-A tile of the ranking kernels is 2 048 sorted rows (256 threads x 8): the sizes below sit on and around one thread's rows, one
-tile and several tiles, and the tie-heavy cases make every tie group span every tile boundary."""
+A tile of the ranking kernels is 2 048 sorted rows (256 threads x 8).  The small sizes (7 .. 8 193 rows, and sets of up to
+240 000 rows = 118 tiles) sit on and around one thread's rows, one tile and several tiles, and their tie-heavy cases make
+every tie group span every tile boundary.  k_eval_scan, k_eval_reduce and k_eval_final are single blocks that take 256 tiles
+per trip, so the cases from 524 287 rows on (the last section; up to 1 048 581 rows = 513 tiles, a third trip) sit on and
+around 256 tiles: the carries between trips, a tie group and a head record that cross from one trip into a later one, and
+tiles wholly behind the ranked rows."""
 import numpy as np
 import pytest
 
@@ -311,6 +315,138 @@ def test_append_batch_with_pipelined_preparation(rcv1):
     for o in [e] + bs + [tb]:
         o.close()
     ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ beyond 256 tiles
+# k_eval_scan, k_eval_reduce and k_eval_final are single blocks that take 256 tiles per trip: from C + 1 rows on there is a
+# second trip, fed by the carries run_neg and run_head and by the p >= 256 stride of the two reductions.
+T = 2048
+C = 256 * T
+
+
+def shuffled(rng, label, pred):
+    perm = rng.permutation(pred.size)
+    return np.ascontiguousarray(label[perm], np.float32), np.ascontiguousarray(pred[perm], np.float32)
+
+
+def distinct_sorted(n):
+    """n different scores in ascending order, exact in float32"""
+    assert n < 1 << 24
+    return ((np.arange(n) - n // 2) / 4096).astype(np.float32)
+
+
+_BIG = {}
+
+
+def big_rounded(n):
+    if n not in _BIG:
+        rng = np.random.default_rng(n)
+        pred = (np.round(rng.normal(size=n) * 64) / 64).astype(np.float32)
+        _BIG[n] = (labels01(rng, n), pred)
+    return _BIG[n]
+
+
+@pytest.mark.parametrize("n", [C - 1, C, C + 1, C + T + 1, 2 * C + 5])
+def test_rounded_scores_beyond_one_trip(dev, n):
+    """256 tiles less a row, 256 tiles, the first row of a second trip, a whole tile and a row of it, and a third trip"""
+    label, pred = big_rounded(n)
+    assert -(-n // T) == {C - 1: 256, C: 256, C + 1: 257, C + T + 1: 258, 2 * C + 5: 513}[n]
+    R.check(run(dev, label, pred), R.oracle(label, pred), "n = %d" % n)
+
+
+def test_all_tied_beyond_one_trip(dev):
+    """one group: the only head is row 0, every tile's partial is 0 and the whole of auc2 is k_eval_final's last group"""
+    n = C + T + 1
+    label = labels01(np.random.default_rng(21), n)
+    pred = np.full(n, -0.5, np.float32)
+    r = run(dev, label, pred)
+    R.check(r, R.oracle(label, pred))
+    assert r.auc2 == r.n_pos * r.n_neg and r.n_pos > 0 and r.n_neg > 0
+
+
+@pytest.mark.parametrize("at", [C - 1, C, C + 1])
+def test_two_values_switching_at_the_trip_boundary(dev, at):
+    """the second group's head is sorted row `at`: the last row of the first trip, the first row of the second (no head
+    record in front of it but run_head's), and its second row"""
+    n = C + T + 1
+    rng = np.random.default_rng(22 + at)
+    pred = np.where(np.arange(n) < at, -1.0, 1.0).astype(np.float32)
+    label, pred = shuffled(rng, labels01(rng, n), pred)
+    assert int((pred < 0).sum()) == at
+    R.check(run(dev, label, pred), R.oracle(label, pred), "switch at %d" % at)
+
+
+def test_a_tie_group_from_tile_250_to_tile_300(dev):
+    """different scores, one group of equal ones from inside tile 250 to inside tile 300, different scores again: the tiles
+    256 .. 299 of the second trip hold no head and take the first trip's last one, and the group that ends in tile 300
+    reads a head 50 tiles back"""
+    n = 301 * T + 9
+    lo, hi = 250 * T + 100, 300 * T + 57
+    pred = distinct_sorted(n)
+    pred[lo:hi] = pred[lo]
+    assert lo // T == 250 and (hi - 1) // T == 300 and hi // T == 300 and np.unique(pred).size == n - (hi - lo) + 1
+    assert pred[lo - 1] < pred[lo] == pred[hi - 1] < pred[hi]
+    rng = np.random.default_rng(23)
+    label, pred = shuffled(rng, labels01(rng, n), pred)
+    R.check(run(dev, label, pred), R.oracle(label, pred))
+
+
+def test_distinct_scores_beyond_one_trip(dev):
+    """every row is a head"""
+    rng = np.random.default_rng(24)
+    n = C + T + 1
+    pred = (rng.permutation(n).astype(np.float32) - n / 2) / 4096   # exact in float32, all different
+    assert np.unique(pred).size == n
+    label = (rng.random(n) < 1 / (1 + np.exp(-pred / 16))).astype(np.float32)
+    R.check(run(dev, label, pred), R.oracle(label, pred))
+
+
+@pytest.mark.parametrize("negatives_below", [True, False])
+def test_separated_classes_beyond_one_trip(dev, negatives_below):
+    """the lower class fills the first trip and seven rows more, so the upper class lies wholly in later trips: with the
+    negatives below, every NP of a positive's group comes through run_neg"""
+    n = C + T + 1
+    n_low = C + 7
+    rng = np.random.default_rng(25)
+    mag = np.abs(np.round(rng.normal(size=n) * 64) / 64)
+    pred = np.where(np.arange(n) < n_low, -1.0 - mag, 1.0 + mag).astype(np.float32)
+    label = ((np.arange(n) >= n_low) == negatives_below).astype(np.float32)
+    label, pred = shuffled(rng, label, pred)
+    r = run(dev, label, pred)
+    R.check(r, R.oracle(label, pred))
+    n_pos = n - n_low if negatives_below else n_low
+    assert (r.n_pos, r.n_neg) == (n_pos, n - n_pos)
+    assert r.auc2 == (2 * n_pos * (n - n_pos) if negatives_below else 0)
+
+
+def test_nan_tail_of_more_than_three_tiles(dev):
+    """m = n - n_nan is three rows past 256 tiles: tile 256 holds three ranked rows and the last three tiles none"""
+    n = C + 4 * T
+    n_nan = 4 * T - 3
+    rng = np.random.default_rng(26)
+    pred = (np.round(rng.normal(size=n) * 64) / 64).astype(np.float32)
+    nans = f32([0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF])
+    pred[rng.choice(n, size=n_nan, replace=False)] = nans[rng.integers(0, 4, n_nan)]
+    label = labels01(rng, n)
+    want = R.oracle(label, pred)
+    assert want.n_nan == n_nan and n - n_nan == C + 3 and -(-n // T) - -(-(n - n_nan) // T) == 3
+    R.check(run(dev, label, pred), want)
+
+
+def test_same_bits_in_seven_pieces_beyond_two_trips(dev):
+    """2C + 5 rows at once and in 7 uneven pieces from a capacity hint of 1: the arrays grow by doubling under the pieces"""
+    capi, ctx = dev
+    n = 2 * C + 5
+    label, pred = big_rounded(n)
+    at_once = run(dev, label, pred)
+    cuts = [0, 1, 3, T + 1, C - 1, C + 2, 2 * C - 77, n]
+    e = capi.Eval(ctx, 1)
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        e.append_host(label[a:b], pred[a:b])
+    pieces = e.finish()
+    e.close()
+    R.check(pieces, R.oracle(label, pred))
+    assert R.fields(pieces) == R.fields(at_once)
 
 
 def test_too_many_rows_are_refused_by_the_argument(dev):
