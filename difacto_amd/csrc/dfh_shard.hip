@@ -82,6 +82,7 @@ struct dfh_shard {
   hipStream_t cs = nullptr;           // the collectives' own stream (the sync step exchanges on the context's stream)
   hipEvent_t ev_k[2] = {nullptr, nullptr}, ev_r[2] = {nullptr, nullptr}, ev_rw[2] = {nullptr, nullptr};
   hipEvent_t ev_f = nullptr, ev_g = nullptr;
+  hipEvent_t ev_m = nullptr;          // the main stream up to a minibatch's Localizer, where no preparation stream ran it (cs_behind_prep)
   // P (or the release) of the minibatch that last used exchange slot q has been queued and recorded: the next K into
   // r_keys[q] / r_cnt[q] waits for it (P reads r_keys / r_rowid / r_rows on the main stream; K writes on the collectives')
   hipEvent_t ev_p[2] = {nullptr, nullptr};
@@ -197,7 +198,7 @@ int dfh_shard_destroy(dfh_shard* s) {
     if (p) hipFree(p);
   if (s->h_cnt) hipHostFree(s->h_cnt);
   if (s->cnt_ev) hipEventDestroy(s->cnt_ev);
-  for (hipEvent_t e : {s->ev_k[0], s->ev_k[1], s->ev_r[0], s->ev_r[1], s->ev_rw[0], s->ev_rw[1], s->ev_f, s->ev_g, s->ev_p[0], s->ev_p[1]})
+  for (hipEvent_t e : {s->ev_k[0], s->ev_k[1], s->ev_r[0], s->ev_r[1], s->ev_rw[0], s->ev_rw[1], s->ev_f, s->ev_g, s->ev_m, s->ev_p[0], s->ev_p[1]})
     if (e) hipEventDestroy(e);
   for (auto& sp : s->spans) {
     hipEventDestroy(sp.a);
@@ -602,6 +603,22 @@ int shard_step_sync(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, int*
   return b ? main_end(b) : DFH_OK;
 }
 
+// The collectives' stream reads a minibatch's key list (its counts, then K): behind the minibatch's Localizer, wherever that
+// was queued.  With preparation streams that is the batch's ready event.  Without them the Localizer sits on the main stream
+// — on the single queue maybe only noted, to ride in later launches: it is queued here — and nothing else orders the
+// collectives' stream behind it: an event recorded on the main stream now does (everything queued there so far comes first).
+int cs_behind_prep(dfh_shard* s, dfh_batch* b) {
+  if (!b) return DFH_OK;
+  if (int rc = flush_pending(b)) return rc;
+  if (b->ready_pending) {
+    DFH_HIP(hipStreamWaitEvent(s->cs, b->ev_ready, 0));
+  } else if (!b->ctx->pipeline) {
+    DFH_HIP(hipEventRecord(s->ev_m, b->ctx->stream));
+    DFH_HIP(hipStreamWaitEvent(s->cs, s->ev_m, 0));
+  }
+  return DFH_OK;
+}
+
 // ---- the overlap schedule: two minibatches in flight (dfh_shard_set_exchange(s, 1)); world > 1.  K, RW and G on the
 // collectives' stream, events between the stages.
 // cur = the minibatch this call trains.  If it was announced to the previous call (dfh_shard_prefetch_counts) its
@@ -622,7 +639,7 @@ int shard_step_overlap(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, i
   if (!(cur.described && cur.b == b)) {
     // not announced: describe it now (its counts over the collectives' stream, one host wait)
     DFH_ARG(!cur.described || !cur.pulled, "dfh_shard_step: the batch differs from the one announced to dfh_shard_prefetch_counts");
-    if (b && b->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, b->ev_ready, 0));
+    if ((rc = cs_behind_prep(s, b))) return rc;
     {
       StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
       rc = queue_counts(s, b, cs);
@@ -679,7 +696,7 @@ int shard_step_overlap(dfh_shard* s, dfh_batch* b, int is_train, int push_cnt, i
   }
   // ---- counts of the next minibatch: on their way while F is queued and runs
   if (look) {
-    if (nb && nb->ready_pending) DFH_HIP(hipStreamWaitEvent(cs, nb->ev_ready, 0));
+    if ((rc = cs_behind_prep(s, nb))) return rc;
     StageScope ts(s, DFH_SHARD_STAGE_COUNTS, cs);
     rc = queue_counts(s, nb, cs);
     if (rc) return rc;
@@ -747,7 +764,7 @@ int dfh_shard_set_exchange(dfh_shard* s, int mode) {
     // these events order two streams of ONE device: no system-scope fence at the record
     const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
     for (hipEvent_t* e : {&s->ev_k[0], &s->ev_k[1], &s->ev_r[0], &s->ev_r[1], &s->ev_rw[0], &s->ev_rw[1], &s->ev_f, &s->ev_g,
-                          &s->ev_p[0], &s->ev_p[1]})
+                          &s->ev_m, &s->ev_p[0], &s->ev_p[1]})
       DFH_HIP(hipEventCreateWithFlags(e, evf));
   }
   if (s->cs) DFH_HIP(hipStreamSynchronize(s->cs));

@@ -15,7 +15,9 @@ no tolerance, no mask, no skipped key.
           documented order (own count push, the peers' in rank order, the pull, the own keys' gradient, the peers' in
           ascending rank) and the rows the rank answers with and its whole shard must equal it.
 
-Not pinned here: the overlap schedule, a second step, the step's loss and penalty sums.
+This file pins the SYNC schedule, one step.  The overlap schedule — two minibatches in flight, a stream of three steps on
+disjoint key sets — is pinned the same way in test_sharded_overlap_exact.py.  Not pinned in either: a second step on the
+SAME keys, the step's loss and penalty sums.
 """
 import numpy as np
 import pytest
