@@ -9,12 +9,15 @@
  *   LBFGSLearner.Basic / WithV      tests/cpp/lbfgs_learner_test.cc:8-146 (objective trajectories of an
  *                                   L-BFGS loop over Loss::Predict / CalcGrad / Evaluate — lbfgs_mini.h)
  *   StageLayout / tile rows         csrc/dfh_feed_layout.h: the device feed's page-locked block and its tile-row table
+ *   BatchRing / DeviceFeed          batch_ring.h, device_feed.h: the worker loops' minibatch objects and row buffers
  * plus Store Pull/Push and Updater Save/Load round trips.  Needs a GPU, except the reader cases.
  * usage: difacto_host_tests <path to rcv1_100.libsvm> [reader]     ("reader": only the host-only cases)
  */
 #include <cmath>
 #include <cstdio>
 #include <memory>
+#include "./batch_ring.h"
+#include "./device_feed.h"
 #include "./device_store.h"
 #include "./hip_fm_loss.h"
 #include "./host_localizer.h"
@@ -424,6 +427,170 @@ static void TestTileRows() {
   EXPECT(!tile_rows_both({3, 4, 5}, dfh::LOC_GATHER_SEGS + 1, &tile));
 }
 
+// the minibatch objects of the worker loops (batch_ring.h): the fused loop's same-sized objects, the sharded loop's slots,
+// and the two hand-overs between them
+static void TestBatchRing() {
+  dfh_ctx* ctx = DeviceContext::Get();
+  sgd::Progress prog;
+  BatchRing ring;
+  ring.Grow(ctx, 3, 4, 8, &prog);
+  EXPECT(ring.count() == 3 && ring[0] && ring[1] && ring[2] && !ring[3]);
+  EXPECT(ring.AllFit(3, 4, 8) && ring.AllFit(3, 4, 16));   // nnz capacity is 2 x 8
+  EXPECT(!ring.AllFit(3, 5, 8) && !ring.AllFit(3, 4, 17) && !ring.AllFit(4, 4, 8));
+  ring.Grow(ctx, 3, 5, 8, &prog);   // rows = max(old, needed), nnz = max(old, 2 x needed)
+  EXPECT(ring.rows() == 5 && ring.nnz() == 16 && ring.count() == 3);
+  for (int q = 0; q < 3; ++q) EXPECT(ring[q] && ring.rows(q) == 5 && ring.nnz(q) == 16);
+  EXPECT(!ring.AllFit(12, 5, 8));
+  ring.Grow(ctx, 12, 5, 8, &prog);
+  EXPECT(ring.count() == 12 && ring.AllFit(12, 5, 16) && ring.rows() == 5 && ring.nnz() == 16);
+  // the sharded loop's entry: the twelve share one allocation, so all of them go; a slot created afterwards is at least of
+  // the common size
+  ring.TakeOverForSlots(4, &prog);
+  EXPECT(ring.count() == 0 && ring.rows() == 5 && ring.nnz() == 16);
+  ring.GrowSlot(ctx, 0, 1, 1, &prog);
+  EXPECT(ring.count() == 1 && ring.Fits(0, 5, 16) && ring.rows(0) == 5 && ring.nnz(0) == 16 && !ring.Fits(1, 1, 1));
+  // a ring that has seen sharded jobs only: four slots of (4, 16), slot 1 grows alone, the end of the job keeps the largest
+  BatchRing slots;
+  slots.TakeOverForSlots(4, &prog);
+  for (int q = 0; q < 4; ++q) slots.GrowSlot(ctx, q, 4, 8, &prog);
+  dfh_batch* before[4] = {slots[0], slots[1], slots[2], slots[3]};
+  EXPECT(slots.count() == 4 && !slots.Fits(1, 9, 40));
+  slots.GrowSlot(ctx, 1, 9, 40, &prog);
+  EXPECT(slots.rows(1) == 9 && slots.nnz(1) == 80 && slots.Fits(1, 9, 80));
+  for (int q : {0, 2, 3}) EXPECT(slots[q] == before[q] && slots.rows(q) == 4 && slots.nnz(q) == 16);
+  dfh_batch* grown = slots[1];
+  slots.NormalizeSlots(4, &prog);
+  EXPECT(slots.count() == 1 && slots[0] == grown && slots.rows() == 9 && slots.nnz() == 80);
+  EXPECT(slots.rows(0) == 9 && slots.nnz(0) == 80 && slots.AllFit(1, 9, 80) && !slots.AllFit(2, 1, 1));
+  for (int q = 1; q < BatchRing::kMax; ++q) EXPECT(!slots[q] && slots.rows(q) == 0 && slots.nnz(q) == 0);
+  // objects that never stepped: their progress is zeros
+  slots.Drain(&prog);
+  ring.Drain(&prog);
+  ring.Drain(0, nullptr);
+  EXPECT(prog.loss == 0 && prog.penalty == 0 && prog.auc == 0 && prog.nnz_w == 0 && prog.nrows == 0);
+}
+
+// a parsed chunk of the given rows, labels 1, 0, 1, ..; and its upload into the feed as one slice under `serial`
+static std::shared_ptr<RowChunk> make_chunk(const std::vector<std::vector<feaid_t>>& rows) {
+  auto c = std::make_shared<RowChunk>();
+  for (size_t r = 0; r < rows.size(); ++r) {
+    c->index.insert(c->index.end(), rows[r].begin(), rows[r].end());
+    c->offset.push_back(c->index.size());
+    c->label.push_back(r % 2 ? 0.f : 1.f);
+  }
+  return c;
+}
+static std::shared_ptr<RowChunk> make_chunk(size_t nrows, size_t nnz, feaid_t first) {   // ids first, first + 1, ..
+  std::vector<std::vector<feaid_t>> rows(nrows);
+  for (size_t i = 0; i < nnz; ++i) rows[std::min(i / (nnz / nrows), nrows - 1)].push_back(first + i);
+  return make_chunk(rows);
+}
+static void feed_upload(DeviceFeed* feed, const std::shared_ptr<RowChunk>& c, uint64_t serial) {
+  feed->Upload(ViewOf(*c), {BufSlice{c, 0, c->Size()}}, serial);
+}
+// rows `rows` of chunk c, gathered out of its device buffer rb into a batch object and localized: exactly their distinct keys
+static void expect_gathered(dfh_batch* b, dfh_rowbuf* rb, const RowChunk& c, const std::vector<uint32_t>& rows) {
+  std::vector<size_t> off(1, 0);
+  std::vector<float> lab;
+  std::vector<uint64_t> want;
+  for (uint32_t r : rows) {
+    for (size_t i = c.offset[r]; i < c.offset[r + 1]; ++i) want.push_back(ReverseBytes(c.index[i]));
+    off.push_back(want.size());
+    lab.push_back(c.label[r]);
+  }
+  std::sort(want.begin(), want.end());
+  want.erase(std::unique(want.begin(), want.end()), want.end());
+  const uint32_t* rp = rows.data();
+  const size_t n = rows.size();
+  DFH_CALL(dfh_batch_gather_rows(b, n, off.data(), lab.data(), 1, &rb, &rp, &n));
+  DFH_CALL(dfh_localize(b, ~0ULL));
+  size_t U = 0;
+  std::vector<uint64_t> got(off.back());
+  DFH_CALL(dfh_batch_get_localized(b, &U, got.data(), nullptr, nullptr));
+  got.resize(std::min(U, got.size()));
+  EXPECT(U == want.size() && got == want);
+}
+
+// device_feed.h: which buffer an upload lands in (a fitting spare, else a new one in place of a too-small spare), and what a
+// cache-filling job keeps (everything in serial order, or nothing once the budget is exceeded)
+static void TestDeviceFeedRecycling() {
+  dfh_ctx* ctx = DeviceContext::Get();
+  const SgdLoopEnv env;
+  dfh_batch* b = nullptr;
+  DFH_CALL(dfh_batch_create(ctx, 16, 64, &b));
+  auto c1 = make_chunk({{11, 22}, {33, 44}, {22, 55}, {66, 77}}), c2 = make_chunk(4, 8, 100), c3 = make_chunk({{1, 2}, {3, 4}, {5}});
+  auto c4 = make_chunk(9, 40, 1000);
+  EXPECT(c3->Size() == 3 && c3->index.size() == 5 && c4->Size() == 9 && c4->index.size() == 40);
+  {   // streaming
+    DeviceFeed feed(ctx, env);
+    feed.Start(0, 0);
+    feed_upload(&feed, c1, 1);
+    feed_upload(&feed, c2, 2);
+    dfh_rowbuf* rb1 = feed.Of(1);
+    dfh_rowbuf* rb2 = feed.Of(2);
+    EXPECT(rb1 && rb2 && rb1 != rb2 && feed.num_owned() == 2 && feed.num_spare() == 0);
+    expect_gathered(b, rb1, *c1, {0, 2});
+    feed.Release(2);
+    EXPECT(feed.num_spare() == 1 && feed.num_owned() == 2);
+    feed_upload(&feed, c3, 3);   // fits the buffer that was handed back
+    EXPECT(feed.Of(3) == rb1 && feed.num_owned() == 2 && feed.num_spare() == 0);
+    expect_gathered(b, rb1, *c3, {2, 0});
+    feed.Release(4);
+    EXPECT(feed.num_spare() == 2);
+    feed_upload(&feed, c4, 4);   // fits neither spare: a new buffer, and the spare handed back last (rb1) is destroyed for it
+    dfh_rowbuf* rb4 = feed.Of(4);
+    // (rb4 may sit at the address rb1 had: what tells a new buffer is that it holds 40 ids and that rb2 is the spare left)
+    EXPECT(rb4 && rb4 != rb2 && feed.num_owned() == 2 && feed.num_spare() == 1);
+    expect_gathered(b, rb4, *c4, {8, 0, 3});
+  }
+  {   // retaining, budget ample
+    DeviceFeed feed(ctx, env);
+    feed.retain = true;
+    feed.Start(0, 0);
+    const std::shared_ptr<RowChunk> cs[3] = {c1, c3, c4};
+    size_t rows = 0, bytes = 0;
+    for (int s = 0; s < 3; ++s) {
+      feed_upload(&feed, cs[s], s + 1);
+      rows += cs[s]->Size();
+      bytes += DeviceFeed::BytesOf(cs[s]->Size(), cs[s]->index.size());
+    }
+    for (int s = 0; s < 3; ++s) EXPECT(feed.Of(s + 1) != nullptr);
+    EXPECT(feed.num_owned() == 3);
+    expect_gathered(b, feed.Of(2), *c3, {1, 2});
+    feed.Release(4);
+    EXPECT(feed.num_spare() == 0);   // kept, not recycled
+    std::unique_ptr<CachedPart> part = feed.TakeCache();
+    EXPECT(part && part->bufs.size() == 3 && part->rows == rows && part->bytes == bytes && feed.num_owned() == 0);
+    for (int s = 0; part && s < 3 && s < static_cast<int>(part->bufs.size()); ++s) {
+      const CachedBuffer& cb = part->bufs[s];
+      EXPECT(cb.rb && cb.offset == cs[s]->offset && cb.offset[0] == 0 && cb.label == cs[s]->label);
+      EXPECT(cb.bytes == DeviceFeed::BytesOf(cs[s]->Size(), cs[s]->index.size()));
+    }
+    if (part && part->bufs.size() == 3) expect_gathered(b, part->bufs[2].rb, *c4, {7});   // the part owns the buffers now
+  }
+  {   // retaining, the budget holds the first buffer only: the part is given up and streams
+    DeviceFeed feed(ctx, env);
+    feed.retain = true;
+    feed.budget = DeviceFeed::BytesOf(c1->Size(), c1->index.size()) + 1;
+    feed.Start(0, 0);
+    const std::shared_ptr<RowChunk> cs[3] = {c1, c3, c4};
+    size_t rows = 0, bytes = 0;
+    for (int s = 0; s < 3; ++s) {   // one at a time: which upload exceeds the budget does not depend on the upload threads
+      feed_upload(&feed, cs[s], s + 1);
+      dfh_rowbuf* rb = feed.Of(s + 1);
+      EXPECT(rb != nullptr);
+      if (rb) expect_gathered(b, rb, *cs[s], {1, 0});
+      rows += cs[s]->Size();
+      bytes += DeviceFeed::BytesOf(cs[s]->Size(), cs[s]->index.size());
+    }
+    feed.Release(4);
+    EXPECT(feed.TakeCache() == nullptr && feed.overflow);
+    EXPECT(feed.need_bytes == bytes && feed.rows_seen == rows);
+    EXPECT(feed.num_spare() == feed.num_owned() && feed.num_owned() >= 1);   // everything went back to recycling
+  }
+  DFH_CALL(dfh_batch_destroy(b));
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: %s <rcv1_100.libsvm>\n", argv[0]);
@@ -456,6 +623,8 @@ int main(int argc, char** argv) {
       {"SGDLearner.Basic[fused]", [] { TestSGDLearnerBasic("fused"); }},
       {"SGDLearner.Basic[literal]", [] { TestSGDLearnerBasic("literal"); }},
       {"Store+ModelIO", TestStoreAndModelIO},
+      {"BatchRing: same-sized objects, slots, hand-overs", TestBatchRing},
+      {"DeviceFeed: buffer recycling, retained parts", TestDeviceFeedRecycling},
       {"LBFGSLearner.Basic (HipFMLoss, V_dim 0)", [] { TestLBFGSTrajectory(false); }},
       {"LBFGSLearner.WithV (HipFMLoss, V_dim 5)", [] { TestLBFGSTrajectory(true); }},
   };

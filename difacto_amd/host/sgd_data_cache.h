@@ -1,7 +1,7 @@
 /**
  * sgd_data_cache.h — data_cache = hbm of the SGD learner: the parsed rows of a data part stay in device memory.
  *
- * The device feed (sgd_learner.cc) uploads the reader's shuffle buffers into device row buffers (dfh_rowbuf) and recycles
+ * The device feed (device_feed.h) uploads the reader's shuffle buffers into device row buffers (dfh_rowbuf) and recycles
  * them.  With the cache the buffers of a job part — (job type, part) — are KEPT, in the order the reader built them, each
  * with what the host still needs of it: its row offsets (the minibatch boundaries by nnz, the size of the batch objects)
  * and its labels (negative down-sampling tests them), 12 B per row.  The ids and values — everything the parser produced,

@@ -22,8 +22,10 @@
 #include <functional>
 #include <string>
 #include <vector>
+#include "./batch_ring.h"
 #include "./device_store.h"
 #include "./sgd_data_cache.h"
+#include "./sgd_loop_env.h"
 #include "./sgd_param.h"
 #include "./sgd_utils.h"
 #include "difacto/learner.h"
@@ -31,6 +33,8 @@
 #include "difacto/store.h"
 
 namespace difacto {
+struct DeviceFeed;
+struct DeviceTextParse;
 
 class SGDLearner : public Learner {
  public:
@@ -62,7 +66,15 @@ class SGDLearner : public Learner {
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
   const std::string& JobData(const sgd::Job& job) const;
   void IterateData(const sgd::Job& job, sgd::Progress* prog);
+  // the fused loop (sgd_learner.cc): what the job reads from, its reader, the prepare / step loop, the cache's bookkeeping
   void IterateDataFused(const sgd::Job& job, sgd::Progress* prog);
+  struct FusedSource;
+  FusedSource SourceOf(const sgd::Job& job, const SgdLoopEnv& env);
+  BatchReader* NewFusedReader(const sgd::Job& job, const FusedSource& src, const SgdLoopEnv& env, DeviceFeed* feed,
+                              DeviceTextParse* text_parse);
+  void RunFused(const sgd::Job& job, const FusedSource& src, const SgdLoopEnv& env, BatchSource* reader, DeviceFeed* feed,
+                sgd::Progress* prog);
+  void CloseCachedJob(const sgd::Job& job, const FusedSource& src, DeviceFeed* feed);
   void IterateDataLiteral(const sgd::Job& job, sgd::Progress* prog);
   void IterateDataSharded(const sgd::Job& job, sgd::Progress* prog);
   /*! \brief sums the record over the ranks of a sharded run (identity for one process) */
@@ -77,16 +89,8 @@ class SGDLearner : public Learner {
   SGDLearnerParam param_;
   int blk_nthreads_ = DEFAULT_NTHREADS;
   std::vector<std::function<void(int, const sgd::Progress&, const sgd::Progress&)>> epoch_end_callback_;
-  // device batches of the fused path (double-buffered)
-  // minibatch objects in rotation.  The fused loop uses kFusedBatches of them: the reader delivers minibatches in bursts
-  // (ten at a time, when a shuffle buffer becomes current) and the loop queues a whole burst on the device without
-  // waiting for any step — with two or three objects the device idled while the loop waited for the reader and the
-  // loop waited while the device caught up.  The sharded loop uses the first two.
-  static constexpr int kFusedBatches = 12;
-  dfh_batch* batch_[kFusedBatches] = {};
-  size_t batch_rows_ = 0, batch_nnz_ = 0;
-  bool batch_arena_ = false;   // batch_[] were carved from ONE device allocation (dfh_batch_create_many): freed when the last one goes
-  SGDDataCache cache_;              // data_cache = hbm: the row buffers of the parts read so far; destroyed with the learner
+  BatchRing ring_;                  // the minibatch objects the fused and the sharded loop rotate (batch_ring.h)
+  SGDDataCache cache_;             // data_cache = hbm: the row buffers of the parts read so far; destroyed with the learner
   FILE* pred_file_ = nullptr;       // open while a prediction job runs
   std::vector<float> pred_buf_;
   dfh_eval* eval_ = nullptr;        // exact_metrics = 1: the rows of the current validation / prediction pass
