@@ -42,10 +42,15 @@ def area(label, pred):
 
 def auc_times_n_f32(area, tp, n):
     """what the device turns {area, positives, n} into: three double operations, then the cast to float"""
+    return np.float32(auc_times_n_f64(area, tp, n))
+
+
+def auc_times_n_f64(area, tp, n):
+    """the double the device adds to its accumulator (several steps between two reads: the doubles add up, then the cast)"""
     if tp in (0, n):
-        return np.float32(1.0)
+        return np.float64(1.0)
     a = np.float64(area) / (np.float64(tp) * np.float64(n - tp))
-    return np.float32((np.float64(1.0) - a if a < 0.5 else a) * np.float64(n))
+    return (np.float64(1.0) - a if a < 0.5 else a) * np.float64(n)
 
 
 def visible(tp, n):

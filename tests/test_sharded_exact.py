@@ -16,8 +16,12 @@ no tolerance, no mask, no skipped key.
           ascending rank) and the rows the rank answers with and its whole shard must equal it.
 
 This file pins the SYNC schedule, one step.  The overlap schedule — two minibatches in flight, a stream of three steps on
-disjoint key sets — is pinned the same way in test_sharded_overlap_exact.py.  Not pinned in either: a second step on the
-SAME keys, the step's loss and penalty sums.
+disjoint key sets — is pinned the same way in test_sharded_overlap_exact.py.  Every step here is also held to the one right
+Progress of its design (test_update_exact.assert_step_progress): a rank's penalty is that of ALL keys of its minibatch, own and
+pulled, each counted once — by the MIXED update, or with shard_mixed_update = 0 by the gradient-row launch (KeyRange.inv = 3)
+and the own keys' launch — so it equals the fused step's, bit for bit under the "pen" variant.  A second step on the SAME keys
+on rank 1 is pinned in test_second_step_exact.py.  Not pinned: the V-dependent logits of such a step, the zero rows' loss at
+V_dim = 0, l2's penalty term beside the drivers.
 """
 import numpy as np
 import pytest
@@ -146,7 +150,7 @@ def test_key_ranges_give_every_class_an_own_and_a_remote_key(V_dim, binary, push
     assert split_entries_expected(D["cnt"]) == 5 + 6
 
 
-@pytest.mark.parametrize("variant", ["l1_0", "Vl2_0", "beta"])
+@pytest.mark.parametrize("variant", ["l1_0", "Vl2_0", "beta", "pen"])
 def test_key_ranges_of_the_variant_designs(variant):
     """CPU: the same for the designs of the hyper-parameter variants (key_ranges raises where no ranges qualify)"""
     for V_dim in E.SWITCH_VDIMS:
@@ -238,6 +242,7 @@ def run_rank(capi, D, rows_all, r, off, options=(), plan=None, peer_grads=None):
         tb.import_(keys[lo:hi], D["scal"][lo:hi], D["has_V"][lo:hi], D["V"][lo:hi] if k else None)
         bt = capi.Batch(c, nrows, nnz + 64)
         objs.append(bt)
+        bt.set_option("compute_auc", 1)       # as the sharded learner sets it
         bt.load_host(D["offset"], D["index"], D["value"], D["label"])
         bt.localize()
         sh = capi.Shard(tb, comm, keys[[off[1], off[2]]])
@@ -250,7 +255,9 @@ def run_rank(capi, D, rows_all, r, off, options=(), plan=None, peer_grads=None):
             raise
         assert active and peers.finished(), "the step stopped after %d exchanges of %r" % (peers.pos, peers.plan)
         c.sync()
-        out = dict(pred=bt.pred().copy(), split_entries=bt.split_entries(), peers=peers)
+        reads = [bt.progress(reset=False), bt.progress(reset=False)]
+        out = dict(pred=bt.pred().copy(), split_entries=bt.split_entries(), peers=peers, progress=bt.progress(reset=True))
+        out["reads"] = reads + [bt.progress(reset=False)]
         tb.check()
         out["model"] = E.device_model(tb)
         assert tb.size() == len(out["model"][0])
@@ -303,6 +310,10 @@ def assert_worker_side(capi, got, D, want, r, off, what, split=True):
         assert not bits(g[:, 4 + k:]).any(), "%s: GRADS to rank %d, padding" % (what, p)
         same_bits(g, gwant[a:b], "%s: GRADS to rank %d" % (what, p))
     same_bits(got["pred"], want["pred"], "%s: logits against clip(exact)" % what)
+    # the rank's progress: loss, AUC and rows of its minibatch, the penalty of ALL its keys, own and pulled, each once — what the
+    # fused step returns for the same design
+    if "progress" in got:     # (a step out of a stream: its batch object's sums are asserted over the stream)
+        E.assert_step_progress(got, want["progress"], what)
     assert_shard(got["model"], keys[lo:hi], tuple(m[lo:hi] for m in want["model"]), k, what, D["cnt"][lo:hi])
     n = split_entries_expected(D["cnt"]) if split else 0
     assert got["split_entries"] == n and n in (0, 11), "%s: %d split entries" % (what, got["split_entries"])
@@ -358,7 +369,33 @@ SHARD_SWITCHES = {
 def test_every_switch_gives_the_same_bytes(capi, oracle, V_dim, push_cnt):
     """rank 1 of 3 under shard_mixed_update = 0, upd_kernel = 0, upd_split = 0, upd_hot_blocks = 1 and 8 and single_queue = 1:
     the default run's logits, gradient rows and shard, and each against the oracle"""
-    D = E.design(X.FULL_LENGTHS, V_dim, False, push_cnt)
+    _switch_matrix(capi, oracle, E.design(X.FULL_LENGTHS, V_dim, False, push_cnt))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim", E.SWITCH_VDIMS)
+@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
+def test_every_switch_gives_the_same_penalty(capi, oracle, V_dim, push_cnt):
+    """the same on the "pen" design, whose penalty has one right float: the MIXED update (own and remote keys in one launch),
+    shard_mixed_update = 0 (the gradient-row launch with KeyRange.inv = 3 for the pulled rows, then the own keys' launch: no key
+    counted by both, none by neither), upd_kernel = 0 (k_backward_all for both) and the others"""
+    _switch_matrix(capi, oracle, E.design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim", E.SWITCH_VDIMS)
+@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
+def test_worker_side_every_rank_penalty(capi, oracle, V_dim, push_cnt):
+    """ranks 0, 1 and 2 of the "pen" design: whichever third of the keys is the rank's own, the penalty is the fused step's"""
+    D = E.design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen")
+    want = E.expected(oracle, D)
+    off = key_ranges(D)
+    rows_all = pulled_rows(capi, D, want)
+    for r in range(W):
+        assert_worker_side(capi, run_rank(capi, D, rows_all, r, off), D, want, r, off, "rank %d, pen" % r)
+
+
+def _switch_matrix(capi, oracle, D):
     want = E.expected(oracle, D)
     off = key_ranges(D)
     rows_all = pulled_rows(capi, D, want)
@@ -434,6 +471,7 @@ def test_owner_side_inside_a_step_bit_exact(capi, oracle, V_dim, push_cnt, per_k
         same_bits(got["peers"].sent["ROWS"][p], rows_want[p], "%s: ROWS answered to rank %d" % (what, p))
     # the worker side of the same step is what it is without the peers' keys: their pushes come after it
     same_bits(got["pred"], want["pred"], "%s: logits" % what)
+    E.assert_step_progress(got, want["progress"], what)     # (the peers' keys are in no minibatch of this rank: not in its penalty)
     gwant = grad_rows_expected(capi, D, want)
     for p in (0, 2):
         same_bits(got["peers"].sent["GRADS"][p], gwant[off[p]:off[p + 1]], "%s: GRADS to rank %d" % (what, p))

@@ -30,8 +30,12 @@ stream behind the Localizer of the announced minibatch, queued on the main strea
 the third minibatch on COUNTS and KEYS carried the batch object's previous key list.  shard_step_overlap now waits for the
 main stream there (cs_behind_prep).
 
-Every comparison is on bit patterns: no tolerance, no mask, no skipped key.  Not pinned here: the loss and penalty sums, and a
-second step on the SAME keys.  (What no bit comparison can tell apart: a step whose fold is switched off takes k_uw_remote in
+Every comparison is on bit patterns: no tolerance, no mask, no skipped key.  The progress sums of every batch object — over the
+minibatches it took, the doubles added up before the cast — are held to the designs' exact_progress in every run (loss, AUC,
+rows), and the penalty on the "pen" streams (section f): the narrow range, the validation step with both k_penalty launches,
+every switch, read at the end and after every step.  A second step on the SAME keys is pinned in test_second_step_exact.py (the
+sync schedule, rank 1); not pinned: its V-dependent logits, the zero rows' loss at V_dim = 0, l2's penalty term beside the
+drivers.  (What no bit comparison can tell apart: a step whose fold is switched off takes k_uw_remote in
 F, which is built to leave the same row words — the degenerate case holds both ways to the same answer.)
 """
 import numpy as np
@@ -63,12 +67,12 @@ def capi():
 _SDESIGNS, _STREAMS = {}, {}
 
 
-def sdesign(V_dim, binary, push_cnt, seed):
+def sdesign(V_dim, binary, push_cnt, seed, variant="base"):
     if seed == 0:
-        return E.design(X.FULL_LENGTHS, V_dim, binary, push_cnt)     # shared with the one-step tests (and its expected())
-    key = (V_dim, binary, push_cnt, seed)
+        return E.design(X.FULL_LENGTHS, V_dim, binary, push_cnt, variant)     # shared with the one-step tests (and its expected())
+    key = (V_dim, binary, push_cnt, seed, variant)
     if key not in _SDESIGNS:
-        _SDESIGNS[key] = X.build(X.FULL_LENGTHS, V_dim, binary, push_cnt, seed=seed)
+        _SDESIGNS[key] = X.build(X.FULL_LENGTHS, V_dim, binary, push_cnt, variant, seed=seed)
     return _SDESIGNS[key]
 
 
@@ -97,13 +101,14 @@ def stream_ok(designs, offs):
     return all(0 < o[1] < o[2] < o[3] for o in offs) and all(a and b for a, b in rank1_classes(designs, offs))
 
 
-def make_stream(V_dim, push_cnt):
+def make_stream(V_dim, push_cnt, variant="base"):
     """-> dict(designs [A, B, C], union, splits u64 [2], offs, per_minibatch): the split keys nearest to thirds of the union of
-    the key lists that satisfy stream_ok and, where such a pair exists, split_ok of every minibatch on its own"""
-    key = (V_dim, push_cnt)
+    the key lists that satisfy stream_ok and, where such a pair exists, split_ok of every minibatch on its own.  (A variant
+    changes the hyper-parameters alone: the minibatches, keys and ranges are the base stream's)"""
+    key = (V_dim, push_cnt, variant)
     if key in _STREAMS:
         return _STREAMS[key]
-    designs = [sdesign(V_dim, BINARY[i], push_cnt, SEEDS[i]) for i in range(3)]
+    designs = [sdesign(V_dim, BINARY[i], push_cnt, SEEDS[i], variant) for i in range(3)]
     union = np.concatenate([D["keys"] for D in designs])
     assert len(np.unique(union)) == len(union), "the designs of a stream share a key"
     union = np.sort(union)
@@ -128,7 +133,7 @@ def make_stream(V_dim, push_cnt):
     a, b = found[per]
     splits = union[[a, b]]
     S = dict(V_dim=V_dim, push_cnt=push_cnt, designs=designs, union=union, splits=splits, offs=offs_of(designs, splits), per_minibatch=per,
-             at=(a, b))
+             at=(a, b), variant=variant)
     _STREAMS[key] = S
     return S
 
@@ -511,12 +516,14 @@ class _StepView:
         self.sent = {kind: v for (m, kind), v in sp.sent.items() if m == t}
 
 
-def run_stream(capi, S, exp, options=(), pipeline=False, schedule="overlap", end=False, snapshots=False, replay=None):
+def run_stream(capi, S, exp, options=(), pipeline=False, schedule="overlap", end=False, snapshots=False, replay=None, read_between=False):
     """rank exp["rank"] of W through the stream on a context of its own: the model of its range imported (the designs' keys and
     the peers' imported ones), two batch objects in rotation, every following minibatch announced before the step (overlap),
     the peers a StreamPeers script — or, replay = a finished script: the loop-back transport fed with what that script
     supplied, a batch object per minibatch and no read between the steps (the host waits for the counts alone).
-    -> dict(pred [t], split_entries [t], peers, model, snaps)"""
+    -> dict(pred [t], split_entries [t], peers, model, snaps, progress [j] = progress(reset=True) of batch object j once the
+    stream is through, steps_of [j] = the minibatches it took).  read_between: progress(reset=False) of the step's batch object
+    after every step, which adds the step's AUC slots up; without it the batch object's next step takes them up"""
     r = exp["rank"]
     k, push_cnt, designs, offs = S["V_dim"], S["push_cnt"], S["designs"], S["offs"]
     stride = capi.row_stride(k)
@@ -560,6 +567,8 @@ def run_stream(capi, S, exp, options=(), pipeline=False, schedule="overlap", end
         nbt = 2 if replay is None else 3       # the replay reloads no batch object: nothing makes the host wait between its steps
         bts = [capi.Batch(c, nrows, nnz + 64) for _ in range(nbt)]
         objs += bts
+        for b_ in bts:
+            b_.set_option("compute_auc", 1)       # as the sharded learner sets it
         sh = capi.Shard(tb, comm, S["splits"])
         objs.append(sh)
         if schedule == "overlap":
@@ -605,6 +614,8 @@ def run_stream(capi, S, exp, options=(), pipeline=False, schedule="overlap", end
             assert peers.done_steps(t + 1), "step %d stopped after %d exchanges of %r" % (t, peers.pos, peers.steps)
             c.sync()
             read(t)
+            if read_between and used[t] is not None:
+                used[t].progress(reset=False)
             if snapshots:
                 out["snaps"].append(E.device_model(tb))
         if end:
@@ -618,6 +629,10 @@ def run_stream(capi, S, exp, options=(), pipeline=False, schedule="overlap", end
             for t in range(3):
                 read(t)
             out["wire_us"] = comm.wire_time_us()
+        out["steps_of"] = [[t for t in range(3) if used[t] is bts[j]] for j in range(nbt)]
+        reads = [(b_.progress(reset=False), b_.progress(reset=False)) for b_ in bts]
+        out["progress"] = [b_.progress(reset=True) for b_ in bts]
+        out["reads"] = [reads[j] + (bts[j].progress(reset=False),) for j in range(nbt)]
         tb.check()
         out["model"] = E.device_model(tb)
         assert tb.size() == len(out["model"][0])
@@ -678,6 +693,18 @@ def assert_steps_sent(capi, oracle, got, S, exp, what, split=True, model=True):
             assert peers.counts.tolist() == [[off[p + 1] - off[p], 1] for p in range(W)] and "GRADS" not in peers.sent
             for p in peers.peers:
                 assert np.array_equal(peers.sent["KEYS"][p], D["keys"][off[p]:off[p + 1]])
+    assert_stream_progress(oracle, got, S, what)
+
+
+def assert_stream_progress(oracle, got, S, what):
+    """per batch object: the sums over the minibatches it took, as the API rounds them (the doubles added up, then the cast),
+    against the designs' exact_progress — a validation step's among them: the same loss, its penalty through k_penalty, once
+    for the pulled rows and once for the own keys"""
+    for j, steps in enumerate(got["steps_of"]):
+        want = X.accepted([E.expected(oracle, S["designs"][t])["progress"] for t in steps])
+        w = "%s, batch object %d (minibatches %r)" % (what, j, steps)
+        X.assert_progress(got["progress"][j], want, w)
+        E.assert_reads(dict(reads=got["reads"][j], progress=got["progress"][j]), w)
 
 
 def assert_owner_side(got, exp, k, what):
@@ -713,7 +740,7 @@ _EXP = {}
 
 
 def expectations(oracle, S, r=1, owner=True, order="overlap", train=(True, True, True), have=(True, True, True)):
-    key = (S["V_dim"], S["push_cnt"], tuple(S["splits"].tolist()), r, owner, order, train, have)
+    key = (S["V_dim"], S["push_cnt"], S["variant"], tuple(S["splits"].tolist()), r, owner, order, train, have)
     if key not in _EXP:
         _EXP[key] = walk(oracle, S, r, peer_plan(S) if owner else None, order, train, have)
     return _EXP[key]
@@ -883,3 +910,68 @@ def test_owner_side_stream_replayed_over_the_loopback_transport(capi, oracle, V_
     assert b["split_entries"] == a["split_entries"] == [11] * 3
     same_model(b["model"], a["model"], "replay: the final shard")
     T.assert_shard(b["model"], exp["shard_keys"], E.oracle_model(exp["so"], exp["shard_keys"], V_dim), V_dim, "replay")
+
+
+# ================================================================== f. the progress sums of a stream
+# Every run above asserts loss, AUC and row count per batch object (assert_steps_sent); the streams' hyper-parameters put the
+# penalty on no grid.  The "pen" streams are the same minibatches, keys and ranges under l1 = 2^-6, l2 = 0, V_l2 = 2^-5.
+@pytest.mark.parametrize("V_dim,push_cnt", STREAMS, ids=STREAM_IDS)
+def test_pen_streams_hold_the_progress_conditions(oracle, V_dim, push_cnt):
+    """CPU: every design of the "pen" streams passes check() and exact_progress's conditions (expected() runs both), the
+    stream's ranges are the base stream's, and the sum of A's and C's doubles — what batch object 0 returns — is accepted as
+    at most three floats"""
+    S, B = make_stream(V_dim, push_cnt, "pen"), make_stream(V_dim, push_cnt)
+    assert np.array_equal(S["splits"], B["splits"]) and S["offs"] == B["offs"]
+    P = [E.expected(oracle, D)["progress"] for D in S["designs"]]
+    assert all(p["penalty"] is not None for p in P)
+    for steps in ([0, 2], [1], [0], [2]):
+        acc = X.accepted([P[t] for t in steps])
+        assert 1 <= len(acc["penalty"]) <= 3 and 1 <= len(acc["loss"]) <= 3
+    if V_dim == 5 and push_cnt:
+        N = narrow_stream(S)
+        assert N["offs"][1][1] == N["offs"][1][2]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim,push_cnt", STREAMS, ids=STREAM_IDS)
+def test_stream_progress_sums_bit_exact(capi, oracle, V_dim, push_cnt):
+    """rank 1 through the "pen" stream, the peers' keys included: batch object 0's sums over A and C and batch object 1's over
+    B — loss, penalty (the MIXED update's, own and remote keys), AUC, rows — read only at the end, so that C's step takes up
+    A's AUC slots, and in a second run read after every step; the bytes sent and the shard as ever"""
+    S = make_stream(V_dim, push_cnt, "pen")
+    exp = expectations(oracle, S)
+    for rb in (False, True):
+        got = run_stream(capi, S, exp, read_between=rb)
+        what = "pen stream, read %s" % ("after every step" if rb else "at the end")
+        assert got["steps_of"] == [[0, 2], [1]]
+        assert_owner_side(got, exp, V_dim, what)
+        assert_steps_sent(capi, oracle, got, S, exp, what, model=False)
+
+
+@pytest.mark.gpu
+def test_stream_progress_sums_under_every_switch(capi, oracle):
+    """the "pen" stream of V_dim 5 with counts under shard_mixed_update = 0 (two launches: no key's penalty in both, none in
+    neither), upd_split = 0, upd_kernel = 0, single_queue = 1 and set_pipeline(1)"""
+    S = make_stream(5, True, "pen")
+    exp = expectations(oracle, S)
+    for name, sw in STREAM_SWITCHES.items():
+        got = run_stream(capi, S, exp, options=sw.get("options", ()), pipeline=sw.get("pipeline", False))
+        assert_owner_side(got, exp, 5, name)
+        assert_steps_sent(capi, oracle, got, S, exp, "pen stream, %s" % name, split=sw.get("split", True), model=False)
+
+
+@pytest.mark.gpu
+def test_stream_progress_sums_without_own_keys_and_in_validation(capi, oracle):
+    """the "pen" stream in the narrow range (B has no own key: its penalty is the pulled rows' alone), and with B a validation
+    step between two training steps (both k_penalty launches: the pulled rows', then the own keys'), under the mixed update
+    and under shard_mixed_update = 0"""
+    S = narrow_stream(make_stream(5, True, "pen"))
+    exp = expectations(oracle, S, 1, owner=False)
+    for opts in ((), (("shard_mixed_update", 0),)):
+        assert_steps_sent(capi, oracle, run_stream(capi, S, exp, options=opts), S, exp, "pen stream, narrow range %r" % (opts,))
+    S = make_stream(5, False, "pen")
+    exp = expectations(oracle, S, train=(True, False, True))
+    for opts in ((), (("shard_mixed_update", 0),)):
+        got = run_stream(capi, S, exp, options=opts, snapshots=True)
+        same_model(got["snaps"][1], got["snaps"][0], "the table after the validation step against the table before it")
+        assert_steps_sent(capi, oracle, got, S, exp, "pen stream, validation step %r" % (opts,), model=False)

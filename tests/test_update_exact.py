@@ -14,7 +14,17 @@ tolerance, no skipped key and no mask:
 The MIXED instantiation of k_update_fused is reached only through a communicator: test_sharded_exact.py pins it, with the
 mixed forward, the others' row words and the owner side inside a step, on the same designs against scripted peers, and
 test_sharded_overlap_exact.py pins the schedule that keeps two minibatches in flight on streams of three such designs with
-disjoint keys.  Still not pinned: a second step on the SAME keys, the steps' progress sums (loss, penalty) bit for bit.
+disjoint keys.  A second step on the SAME keys is pinned in test_second_step_exact.py.
+
+  progress sums     every step of a design here is also held to the one right Progress (exact_step_design.exact_progress): row
+                    count, the loss (the floats of the three values log1pf(1.0f) may take), AUC x n of the exact logits, and
+                    — under the "pen" variant, whose l1, l2 and V_l2 put every term on one grid — the penalty, bit for bit;
+                    the packed path counts none (+0), a validation step counts it through k_penalty.  Two reads give the same
+                    bits, a reset leaves zeros, and two steps in one batch object add up as doubles before the cast.
+
+Still not pinned: the V-dependent logits of a second step; the loss of the zero rows at V_dim = 0 (below the float's
+resolution there: the V_dim > 0 designs pin that term); l2's penalty term beside the drivers (pinned on the driverless copy
+exact_step_design.l2_copy alone); the penalty under the other variants' hyper-parameters, which are on no grid.
 """
 import numpy as np
 import pytest
@@ -502,10 +512,10 @@ def test_owner_side_forms_several_sources_bit_exact(capi, ctx, oracle, V_dim, mo
 _DESIGNS = {}
 
 
-def design(lengths, V_dim, binary, push_cnt, variant="base"):
-    key = (tuple(lengths), V_dim, binary, push_cnt, variant)
+def design(lengths, V_dim, binary, push_cnt, variant="base", seed=0):
+    key = (tuple(lengths), V_dim, binary, push_cnt, variant, seed)
     if key not in _DESIGNS:
-        _DESIGNS[key] = X.build(lengths, V_dim, binary, push_cnt, variant)
+        _DESIGNS[key] = X.build(lengths, V_dim, binary, push_cnt, variant, seed=seed)
     return _DESIGNS[key]
 
 
@@ -536,7 +546,8 @@ def expected(oracle, D):
     got = X.check(D, pulled, lengths=D["lengths"])
     so.push(D["keys"], ob.GRADIENT, X.ragged_gradient(got["gw"], got["gV"], lens, k), lens if k else None)
     assert so.size() == len(D["keys"])
-    out = dict(got, lens=lens, pulled=np.array(pulled[0], np.float32), model=oracle_model(so, D["keys"], k))
+    out = dict(got, lens=lens, pulled=np.array(pulled[0], np.float32), model=oracle_model(so, D["keys"], k),
+               progress=X.exact_progress(D, pulled))
     # what the design promises of the update: keys whose V the update initialises, keys that stay without although w left zero
     scal, has, V = out["model"]
     c = D["cls"]
@@ -553,7 +564,7 @@ def expected(oracle, D):
 
 STEP_VDIMS = [0, 1, 4, 5, 8, 64, 100, 128, 256]
 SWITCH_VDIMS = [0, 5, 64]
-VARIANT_CASES = [(V_dim, push_cnt, v) for V_dim in SWITCH_VDIMS for push_cnt in (False, True) for v in ("l1_0", "Vl2_0", "beta")]
+VARIANT_CASES = [(V_dim, push_cnt, v) for V_dim in SWITCH_VDIMS for push_cnt in (False, True) for v in ("l1_0", "Vl2_0", "beta", "pen")]
 
 
 @pytest.mark.parametrize("V_dim", STEP_VDIMS)
@@ -586,9 +597,11 @@ def _oracle_step_is_exact(oracle, D):
     assert so.size() == len(D["keys"])
 
 
-def _device_step(capi, D, path="device", options=()):
+def _device_step(capi, D, path="device", options=(), auc=True, is_train=True):
     """one step of the design from the imported model on a context of its own -> dict(pred, model = (scal, has_V, V),
-    split_entries, and for the packed path grads [U, stride], rows_after)"""
+    split_entries, progress = what progress(reset=True) returned after the step, reads = two progress(reset=False) before it
+    and one after it, and for the packed path grads [U, stride], rows_after).  auc: the batch option compute_auc, as the
+    learners set it; is_train = False: a validation step"""
     k = D["V_dim"]
     nrows, nnz, U = len(D["label"]), len(D["index"]), len(D["keys"])
     c = capi.Context(0)
@@ -601,6 +614,8 @@ def _device_step(capi, D, path="device", options=()):
         tb.import_(D["keys"], D["scal"], D["has_V"], D["V"] if k else None)
         bt = capi.Batch(c, nrows, nnz + 64)
         objs.append(bt)
+        if auc:
+            bt.set_option("compute_auc", 1)
         out = {}
         if path == "host_localized":
             bt.load_localized_host(D["offset"], D["cidx"], D["value"], D["label"], D["keys"], D["cnt"] if D["push_cnt"] else None)
@@ -627,7 +642,10 @@ def _device_step(capi, D, path="device", options=()):
             c.sync()
             out["rows_after"] = d_rows.to_numpy(np.float32, U * stride).reshape(U, stride)
         else:
-            bt.sgd_step(tb, is_train=True, push_cnt=D["push_cnt"])
+            bt.sgd_step(tb, is_train=is_train, push_cnt=D["push_cnt"] and is_train)    # (a validation step pushes no counts)
+        reads = [bt.progress(reset=False), bt.progress(reset=False)]
+        out["progress"] = bt.progress(reset=True)
+        out["reads"] = reads + [bt.progress(reset=False)]
         out["pred"] = bt.pred()
         out["split_entries"] = bt.split_entries()
         tb.check()
@@ -641,11 +659,46 @@ def _device_step(capi, D, path="device", options=()):
         c.close()
 
 
-def _assert_step(got, want, D, what, split=True):
-    k = D["V_dim"]
+PROGRESS_FIELDS = ("loss", "penalty", "auc", "nnz_w", "nrows")
+
+
+def progress_bits(p):
+    return tuple(X.f32bits(getattr(p, f)) for f in PROGRESS_FIELDS)
+
+
+def assert_reads(got, what):
+    """reading does not change the sums (two reads without reset and the one with it: the same bits); after the reset: zeros"""
+    a, b, z = got["reads"]
+    assert progress_bits(a) == progress_bits(b) == progress_bits(got["progress"]), "%s: two reads of the progress differ" % what
+    assert progress_bits(z) == (0, 0, 0, 0, 0), "%s: the progress after its reset: %r" % (what, progress_bits(z))
+
+
+def assert_step_progress(got, P, what, auc=True, penalty=True):
+    """the step's Progress against the design's one right answer P (X.exact_progress).  auc = False: a batch without
+    compute_auc leaves the AUC at +0; penalty = False: a path that counts none (Batch.forward / Batch.backward) leaves +0"""
+    P = dict(P)
+    if not auc:
+        P["auc"] = 0.0
+    if not penalty:
+        P["penalty"] = dict(exact=0.0, err=0.0)
+    X.assert_progress(got["progress"], X.accepted([P]), what)
+    assert_reads(got, what)
+
+
+def _assert_step(got, want, D, what, split=True, auc=True, penalty=True):
+    assert_step_progress(got, want["progress"], what, auc=auc, penalty=penalty)
     same_bits(got["pred"], want["pred"], "%s: logits against clip(exact)" % what)
-    scal, has, V = got["model"]
-    wscal, whas, wV = want["model"]
+    _assert_model(got["model"], want["model"], D, what)
+    if split is not None:
+        assert got["split_entries"] == (split_entries_expected(D["cnt"]) if split else 0), what
+    if split:
+        assert got["split_entries"] == 5 + 6      # 4 097 and 5 121 occurrences; 4 096 stays whole
+
+
+def _assert_model(model, wmodel, D, what):
+    k = D["V_dim"]
+    scal, has, V = model
+    wscal, whas, wV = wmodel
     assert np.array_equal(has != 0, whas != 0), "%s: has_V differs at keys of %r occurrences" % (what, D["cnt"][(has != 0) != (whas != 0)][:8])
     for j, name in enumerate(("fea_cnt", "w", "sqrt_g", "z")):
         bad = bits(scal[:, j]) != bits(wscal[:, j])
@@ -656,10 +709,6 @@ def _assert_step(got, want, D, what, split=True):
             bad = (bits(a) != bits(b)).any(1)
             assert not bad.any(), "%s: %s differ at %d keys; their occurrences %r, classes %r" % (
                 what, name, bad.sum(), np.unique(D["cnt"][bad]).astype(int).tolist(), np.unique(D["cls"][bad]).tolist())
-    if split is not None:
-        assert got["split_entries"] == (split_entries_expected(D["cnt"]) if split else 0), what
-    if split:
-        assert got["split_entries"] == 5 + 6      # 4 097 and 5 121 occurrences; 4 096 stays whole
 
 
 @pytest.mark.gpu
@@ -692,19 +741,47 @@ SWITCHES = {
 }
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("V_dim", SWITCH_VDIMS)
-@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
-def test_exact_step_every_switch_gives_one_model(capi, oracle, V_dim, push_cnt):
-    """the other ways through the step — host-localized load (k_seg_lists), upd_split = 0, upd_kernel = 0 (k_backward_all),
-    upd_hot_blocks = 1 and 8, single_queue = 1, and the packed path shard_pull -> Batch.forward -> Batch.backward ->
-    shard_push_grad — each against the oracle, and all of them one and the same model as the default path"""
-    D = design(X.FULL_LENGTHS, V_dim, False, push_cnt)
+# the routes of the minibatch's AUC into the progress block: riding in the update launch (the default), a launch of its own
+# behind the forward, and a batch that computes none
+AUC_ROUTES = {
+    "auc_in_update0": dict(options=(("auc_in_update", 0),)),
+    "no_auc": dict(auc=False),
+}
+PEN_VDIMS = [0, 1, 5, 64, 256]
+PEN_CASES = [(V_dim, push_cnt) for V_dim in PEN_VDIMS for push_cnt in (False, True)]
+# the l2 copy's total is small (an ulp of 5e-7): a C key's 24-bit V would put a rounding boundary inside the accepted interval,
+# so the copies that carry V are those without a count push (the l2 term is w's alone)
+L2_CASES = [(0, False), (0, True), (5, False), (64, False)]
+
+
+_VALIDATION = {}
+
+
+def validation_progress(D):
+    """the one right Progress of a validation step on the design's own model (no count push: a C key is still without V)"""
+    if id(D) not in _VALIDATION:
+        _VALIDATION[id(D)] = X.exact_progress(D)
+    return _VALIDATION[id(D)]
+
+
+def _assert_validation(got, D, what):
+    """a validation step: clip(exact) logits, loss and AUC of these, the penalty (k_penalty) of the model as imported, and the
+    model bit-identical to the import"""
+    same_bits(got["pred"], X.exact_pred(D), "%s: logits against clip(exact)" % what)
+    assert_step_progress(got, validation_progress(D), what)
+    scal, has, V = got["model"]
+    same_bits(scal, D["scal"], "%s: scalars against the import" % what)
+    assert np.array_equal(has != 0, D["has_V"] != 0), what
+    if D["V_dim"]:
+        same_bits(V, D["V"], "%s: V | acc against the import" % what)
+
+
+def _switch_matrix(capi, oracle, D):
     want = expected(oracle, D)
     k = D["V_dim"]
     runs = {"default": _device_step(capi, D)}
-    for name, sw in SWITCHES.items():
-        runs[name] = _device_step(capi, D, path=sw.get("path", "device"), options=sw.get("options", ()))
+    for name, sw in list(SWITCHES.items()) + list(AUC_ROUTES.items()):
+        runs[name] = _device_step(capi, D, path=sw.get("path", "device"), options=sw.get("options", ()), auc=sw.get("auc", True))
     runs["packed"] = _device_step(capi, D, path="packed")
     # -- all of them one and the same model and the same logits
     base = runs["default"]
@@ -713,9 +790,11 @@ def test_exact_step_every_switch_gives_one_model(capi, oracle, V_dim, push_cnt):
         assert np.array_equal(r["model"][1], base["model"][1]), name
         same_bits(r["model"][0], base["model"][0], "%s against the default path: scalars" % name)
         same_bits(r["model"][2], base["model"][2], "%s against the default path: V | acc" % name)
-    # -- each against the oracle
+    # -- each against the oracle; the progress sums: the packed path's forward leaves the loss and counts the rows, nothing
+    # there computes an AUC, and backward<false> without the penalty bit counts no penalty: exactly +0
     for name, r in runs.items():
-        _assert_step(r, want, D, name, split=None if name == "packed" else SWITCHES.get(name, {}).get("split", True))
+        _assert_step(r, want, D, name, split=None if name == "packed" else SWITCHES.get(name, {}).get("split", True),
+                     auc=name not in ("packed", "no_auc"), penalty=name != "packed")
     # -- the packed path's gradient rows: [gw, has_V as pulled, 0, 0 | gV], padded coordinates zero
     p = runs["packed"]
     stride = p["grads"].shape[1]
@@ -729,3 +808,196 @@ def test_exact_step_every_switch_gives_one_model(capi, oracle, V_dim, push_cnt):
     # -- padded coordinates (k <= d < kp) of the rows pulled after the step stay zero
     assert not bits(p["rows_after"][:, 4 + k:]).any() and not bits(p["rows_after"][:, 2:4]).any()
     same_bits(p["rows_after"][:, 0], want["model"][0][:, 1], "w as pulled after the step")
+    # -- a validation step on the same design
+    _assert_validation(_device_step(capi, D, is_train=False), D, "validation step")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim", SWITCH_VDIMS)
+@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
+def test_exact_step_every_switch_gives_one_model(capi, oracle, V_dim, push_cnt):
+    """the other ways through the step — host-localized load (k_seg_lists), upd_split = 0, upd_kernel = 0 (k_backward_all),
+    upd_hot_blocks = 1 and 8, single_queue = 1, auc_in_update = 0, a batch without compute_auc, and the packed path
+    shard_pull -> Batch.forward -> Batch.backward -> shard_push_grad — each against the oracle, and all of them one and the
+    same model as the default path; loss, AUC and row count of every one of them, and of a validation step, against
+    exact_progress (the penalty of these hyper-parameters is on no grid: the next test)"""
+    _switch_matrix(capi, oracle, design(X.FULL_LENGTHS, V_dim, False, push_cnt))
+
+
+# ================================================================== the progress sums
+@pytest.mark.parametrize("V_dim", STEP_VDIMS)
+@pytest.mark.parametrize("binary", [False, True], ids=["valued", "binary"])
+@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
+def test_loss_sums_are_exact_and_every_row_shows(oracle, V_dim, binary, push_cnt):
+    """CPU: for every design the GPU tests step, training (the weights after the count push) and validation (the model as
+    imported): the loss terms are on one grid and their double sum is exact in any order, one row of a class dropped or counted
+    twice changes the float, and the three candidates of log1pf(1.0f) give the accepted floats (exact_step_design.loss_of).  At
+    V_dim = 0 the zero rows are below the float's resolution (the total is about 2e7): their term is pinned by the V_dim > 0
+    designs — the forward's loss code does not depend on V_dim"""
+    D = design(X.FULL_LENGTHS, V_dim, binary, push_cnt)
+    for P in (expected(oracle, D)["progress"], validation_progress(D)):
+        acc = X.accepted([P])
+        assert P["nrows"] == len(D["label"]) and 1 <= len(acc["loss"]) <= 3 and acc["auc"] != 0
+        assert P["penalty"] is None       # l1 = 0.02, V_l2 = 0.02: no grid; the "pen" designs pin the penalty
+        if V_dim:
+            nz = int((D["row_class"] == "z").sum())
+            assert P["loss"][1] == 20.0 * int((D["row_class"] == "s").sum()) + nz * float(X.LN2)
+
+
+@pytest.mark.parametrize("V_dim,push_cnt", PEN_CASES)
+def test_penalty_sums_are_exact_and_every_key_shows(oracle, V_dim, push_cnt):
+    """CPU: the "pen" designs (l1 = 2^-6, l2 = 0, V_l2 = 2^-5) pass check() like the others, and exact_step_design.penalty_of
+    holds on the weights their training step and their validation step see: every term on one grid with fewer than 2^24 grid
+    steps in all (exact in any grouping of fp32 partials), a key's non-zero term at least 2 ulp of the float total, the C
+    keys' interval below half the smallest term.  The keys with w = 0 and no V have penalty 0: inherently invisible"""
+    D = design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen")
+    want = expected(oracle, D)
+    for P in (want["progress"], validation_progress(D)):
+        pen = P["penalty"]
+        assert pen is not None and pen["exact"] > 0 and pen["zero_keys"] == int(((D["cls"] == "Z") | (D["scal"][:, 1] == 0)).sum())
+        assert 1 <= len(X.accepted([P])["penalty"]) <= 3
+    train, valid = want["progress"]["penalty"], validation_progress(D)["penalty"]
+    if V_dim and push_cnt:      # the C keys' V is in the training step's penalty only
+        assert train["err"] > 0 and valid["err"] == 0 and train["exact"] > valid["exact"]
+    else:
+        assert train["err"] == 0 and train["exact"] == valid["exact"]
+
+
+def _l2_pulled(oracle, C, train):
+    """the weights a step of the l2 copy sees: its own model, after the count push where the training step makes one"""
+    from oracle import bindings as ob
+    if not (train and C["push_cnt"]):
+        return None
+    so = _poked_store(oracle, C)
+    so.push(C["keys"], ob.FEA_COUNT, C["cnt"])
+    return so.pull(C["keys"])
+
+
+@pytest.mark.parametrize("V_dim,push_cnt", L2_CASES)
+def test_l2_copy_penalty_is_exact_and_every_key_shows(oracle, V_dim, push_cnt):
+    """CPU: on the copy with the drivers at +-2 and l2 = 2^-3 penalty_of's conditions hold with the l2 term in the sum"""
+    C = X.l2_copy(design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen"))
+    for train in (True, False):
+        pen = X.penalty_of(C, _l2_pulled(oracle, C, train))
+        w = C["scal"][:, 1].astype(np.float64)
+        assert pen is not None and pen["exact"] > float(np.sum(2.0 ** -6 * np.abs(w))) and np.abs(w).max() == 2.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim,push_cnt", PEN_CASES)
+def test_exact_step_penalty_default_path(capi, oracle, V_dim, push_cnt):
+    """the "pen" design through the default step and a validation step: everything test_exact_step_default_path asserts, and
+    the penalty sum (upd_apply's fp32 lane partials through upd_flush_penalty; k_penalty) as bit patterns"""
+    D = design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen")
+    _assert_step(_device_step(capi, D), expected(oracle, D), D, "default path, pen")
+    _assert_validation(_device_step(capi, D, is_train=False), D, "validation step, pen")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim", SWITCH_VDIMS)
+@pytest.mark.parametrize("push_cnt", [False, True], ids=["nocnt", "cnt"])
+def test_exact_step_every_switch_gives_one_penalty(capi, oracle, V_dim, push_cnt):
+    """the switch matrix on the "pen" design: the penalty of upd_apply in every role (upd_split = 0: the hot role takes the
+    long keys), of finish_key and small_role_lean (upd_kernel = 0), under upd_hot_blocks = 1 and 8, the single queue and both
+    AUC routes: one float; the packed path: +0"""
+    _switch_matrix(capi, oracle, design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim,push_cnt", L2_CASES)
+def test_l2_penalty_term_on_the_driverless_copy(capi, oracle, V_dim, push_cnt):
+    """0.5 l2 w^2 in the penalty of upd_apply, finish_key (upd_kernel = 0) and k_penalty (a validation step): only penalty and
+    nrows are asserted on the copy — its rows are in no class, so its loss, logits and model have no one right answer"""
+    C = X.l2_copy(design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen"))
+    for name, kw, train in (("default", {}, True), ("upd_kernel0", dict(options=(("upd_kernel", 0),)), True), ("validation", dict(is_train=False), False)):
+        P = X.exact_progress(C, _l2_pulled(oracle, C, train), loss=False)
+        got = _device_step(capi, C, **kw)
+        X.assert_progress(got["progress"], X.accepted([P]), "l2 copy, %s" % name)
+        assert_reads(got, "l2 copy, %s" % name)
+
+
+def _two_minibatches_one_batch_object(capi, A, B, read_between, options=()):
+    """the designs A and B (disjoint keys, one set of hyper-parameters) imported into one table and stepped one after the
+    other through ONE batch object -> dict(between = progress(reset=False) after A's step | None, progress = progress(reset=True)
+    after B's, after = a read behind it, model = (keys, scal, has_V, V)).  Without the read between the steps B's lookup takes up
+    the AUC slots A's update launch left pending"""
+    k = A["V_dim"]
+    assert B["V_dim"] == k and A["hyper"] == B["hyper"] and not np.isin(A["keys"], B["keys"]).any()
+    c = capi.Context(0)
+    objs = []
+    try:
+        for name, v in options:
+            c.set_option(name, v)
+        tb = capi.Table(c, 4096, V_dim=k, init_mode=capi.INIT_HASH, **A["hyper"])
+        objs.append(tb)
+        keys = np.concatenate([A["keys"], B["keys"]])
+        o = np.argsort(keys)
+        tb.import_(keys[o], np.concatenate([A["scal"], B["scal"]])[o], np.concatenate([A["has_V"], B["has_V"]])[o],
+                   np.concatenate([A["V"], B["V"]])[o] if k else None)
+        bt = capi.Batch(c, max(len(A["label"]), len(B["label"])), max(len(A["index"]), len(B["index"])) + 64)
+        objs.append(bt)
+        bt.set_option("compute_auc", 1)
+        out = dict(between=None)
+        for i, D in enumerate((A, B)):
+            bt.load_host(D["offset"], D["index"], D["value"], D["label"])
+            bt.localize()
+            bt.sgd_step(tb, is_train=True, push_cnt=D["push_cnt"])
+            if i == 0 and read_between:
+                out["between"] = bt.progress(reset=False)
+        out["progress"] = bt.progress(reset=True)
+        out["after"] = bt.progress(reset=False)
+        tb.check()
+        out["model"] = device_model(tb)
+        return out
+    finally:
+        for o_ in objs[::-1]:
+            o_.close()
+        c.close()
+
+
+TWO_STEP_ROUTES = {"default": (), "auc_in_update0": (("auc_in_update", 0),), "upd_kernel0": (("upd_kernel", 0),), "single_queue": (("single_queue", 1),)}
+
+
+TWO_STEP_CASES = dict(argvalues=[(0, False), (5, True), (64, False)], ids=["V0-nocnt", "V5-cnt", "V64-nocnt"])
+
+
+@pytest.mark.parametrize("V_dim,push_cnt", **TWO_STEP_CASES)
+def test_two_step_designs_hold_their_conditions(oracle, V_dim, push_cnt):
+    """CPU: the second design of test_two_steps_in_one_batch_object_add_up (seed 1, binary, "pen") passes check() and
+    exact_progress's conditions, shares no key with the first, and the sum of the two steps' doubles is accepted as at most
+    three floats, none of them a single step's"""
+    A = design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen")
+    B = design(X.FULL_LENGTHS, V_dim, True, push_cnt, "pen", seed=1)
+    assert not np.isin(A["keys"], B["keys"]).any() and A["hyper"] == B["hyper"]
+    pa, pb = expected(oracle, A)["progress"], expected(oracle, B)["progress"]
+    both, one = X.accepted([pa, pb]), (X.accepted([pa]), X.accepted([pb]))
+    for f in ("loss", "penalty"):
+        assert 1 <= len(both[f]) <= 3 and not (both[f] & one[0][f]) and not (both[f] & one[1][f])
+    assert both["auc"] not in (one[0]["auc"], one[1]["auc"]) and both["nrows"] != one[0]["nrows"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V_dim,push_cnt", **TWO_STEP_CASES)
+def test_two_steps_in_one_batch_object_add_up(capi, oracle, V_dim, push_cnt):
+    """two "pen" designs with disjoint keys through one batch object: the progress after both is float(the doubles of the two
+    steps added up) — read between the steps and at the end, and read only at the end, where the first step's AUC reaches the
+    sum through the second step's lookup (auc_pending), not through a read; with the AUC in a launch of its own, k_backward_all
+    and the single queue as well.  Both designs' keys afterwards: their own expected models"""
+    A = design(X.FULL_LENGTHS, V_dim, False, push_cnt, "pen")
+    B = design(X.FULL_LENGTHS, V_dim, True, push_cnt, "pen", seed=1)
+    wa, wb = expected(oracle, A), expected(oracle, B)
+    both = X.accepted([wa["progress"], wb["progress"]])
+    assert both["auc"] not in (X.accepted([wa["progress"]])["auc"], X.accepted([wb["progress"]])["auc"])
+    for name, options in TWO_STEP_ROUTES.items():
+        for read_between in (False, True):
+            what = "%s, %s" % (name, "read between the steps" if read_between else "read at the end")
+            got = _two_minibatches_one_batch_object(capi, A, B, read_between, options)
+            if read_between:
+                X.assert_progress(got["between"], X.accepted([wa["progress"]]), what + ": after the first step")
+            X.assert_progress(got["progress"], both, what)
+            assert progress_bits(got["after"]) == (0, 0, 0, 0, 0), what
+            dk, scal, has, V = got["model"]
+            for D, w in ((A, wa), (B, wb)):
+                m = np.isin(dk, D["keys"])
+                assert m.sum() == len(D["keys"])
+                _assert_model((scal[m], has[m], V[m]), w["model"], D, what)
