@@ -43,6 +43,7 @@ SYMBOLS = [
     "dfh_bcd_epoch", "dfh_bcd_step", "dfh_bcd_get_model", "dfh_bcd_get_pred", "dfh_batch_split_entries",
     "dfh_bcd_create_sharded",
     "dfh_textchunk_create", "dfh_textchunk_destroy", "dfh_textchunk_parse_criteo", "dfh_textchunk_rows", "dfh_textchunk_ids",
+    "dfh_lz4_decompress", "dfh_textchunk_decode_crb",
     "dfh_rowbuf_load_slices",
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
     "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
@@ -193,6 +194,8 @@ def lib():
     L.dfh_textchunk_rows.argtypes = [vp, vp, vp]
     L.dfh_textchunk_ids.argtypes = [vp, vp]
     L.dfh_lz4_compress.argtypes = [vp, vp, sz, vp, sz, PP(sz)]
+    L.dfh_lz4_decompress.argtypes = [vp, vp, sz, vp, sz, PP(i32)]
+    L.dfh_textchunk_decode_crb.argtypes = [vp, vp, sz, PP(i32), PP(sz), PP(sz)]
     L.dfh_crb_create.argtypes = [vp, PP(vp)]
     L.dfh_crb_destroy.argtypes = [vp]
     L.dfh_crb_encode_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, PP(sz)]
@@ -661,6 +664,20 @@ class TextChunk:
         _ck(lib().dfh_textchunk_rows(self.h, _p(off), _p(lab)))
         return off, lab[:nrows.value], nnz.value
 
+    def decode_crb(self, record):
+        """one CompressedRowBlock record (bytes) decoded on the device (dfh_textchunk_decode_crb) -> None when the record is not
+        regular (the caller inflates it on the host), else (offset u32 [nrows + 1], label [nrows], nnz)"""
+        record = bytes(record)
+        buf = C.create_string_buffer(record, len(record)) if len(record) else C.create_string_buffer(1)
+        reg, nrows, nnz = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        _ck(lib().dfh_textchunk_decode_crb(self.h, buf, len(record), C.byref(reg), C.byref(nrows), C.byref(nnz)))
+        if not reg.value:
+            return None
+        off = np.zeros(nrows.value + 1, np.uint32)
+        lab = np.zeros(max(nrows.value, 1), np.float32)
+        _ck(lib().dfh_textchunk_rows(self.h, _p(off), _p(lab)))
+        return off, lab[:nrows.value], nnz.value
+
     def ids(self, nnz):
         out = np.zeros(max(nnz, 1), np.uint64)
         _ck(lib().dfh_textchunk_ids(self.h, _p(out)))
@@ -682,6 +699,18 @@ def lz4_compress(ctx, data):
     out = C.c_size_t(0)
     _ck(lib().dfh_lz4_compress(ctx.h, src, n, dst, cap, C.byref(out)))
     return dst.raw[:out.value]
+
+
+def lz4_decompress(ctx, block, expect, fill=0xA5):
+    """the LZ4 block `block` (bytes) decoded on the device (dfh_lz4_decompress) into a buffer of `expect` bytes that held `fill`
+    in every byte -> (ok, the buffer's bytes afterwards)"""
+    block = bytes(block)
+    n = len(block)
+    src = C.create_string_buffer(block, n) if n else C.create_string_buffer(1)
+    dst = C.create_string_buffer(bytes([fill]) * max(expect, 1), max(expect, 1))
+    ok = C.c_int(-1)
+    _ck(lib().dfh_lz4_decompress(ctx.h, src, n, dst, expect, C.byref(ok)))
+    return ok.value, dst.raw[:expect]
 
 
 class CrbEncoder:

@@ -2401,6 +2401,7 @@ int dfh_batch_destroy(dfh_batch* b) {
 
 #include "dfh_textparse.hip"   // the device text parse: chunks whose ids the feed's uploads take device to device
 #include "dfh_lz4enc.hip"   // the device LZ4 block encoder and the row-block records of task = convert
+#include "dfh_lz4dec.hip"   // the device LZ4 block decoder: .rec records decoded into chunks like the parsed ones
 #include "dfh_feed.hip"   // the device feed, and the staging helpers the load calls below share with it
 
 extern "C" {

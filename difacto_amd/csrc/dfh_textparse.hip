@@ -17,6 +17,10 @@
 //   k_tp_emit       (CityHash64(token) << 12) | slot at offset[row] + the field's rank among the row's non-empty fields
 // The text buffer is padded: a lane's 16-byte load and the five aligned words a token is assembled from (tokens start at
 // any byte; no unaligned load is issued) stay inside the allocation.
+struct dfh_lzd;   // the LZ4 decoder's arrays of a chunk that holds decoded records (dfh_lz4dec.hip)
+namespace {
+void lzd_free(dfh_lzd* z);
+}
 struct dfh_textchunk {
   dfh_ctx* ctx = nullptr;
   hipStream_t s = nullptr;   // the context's parse stream (one per context, not one per chunk: a process has 4 hardware queues)
@@ -35,6 +39,7 @@ struct dfh_textchunk {
   size_t h_rows_cap = 0;
   size_t nrows = 0, nnz = 0;
   bool valid = false;                                   // the last parse found a regular chunk
+  dfh_lzd* lzd = nullptr;                               // rec_decode = device: created by the first record
 };
 
 namespace {
@@ -241,6 +246,7 @@ int dfh_textchunk_destroy(dfh_textchunk* tc) {
     if (p) hipFree(p);
   if (tc->h_head) hipHostFree(tc->h_head);
   if (tc->h_rows) hipHostFree(tc->h_rows);
+  lzd_free(tc->lzd);
   delete tc;
   return DFH_OK;
 }

@@ -20,6 +20,7 @@
 #include <vector>
 #include "./batch_reader.h"
 #include "./device_context.h"
+#include "./device_rec_decode.h"
 #include "./device_text_parse.h"
 #include "./recordio_writer.h"
 #include "dmlc/parameter.h"
@@ -45,6 +46,9 @@ struct ConverterParam : public dmlc::Parameter<ConverterParam> {
   int part_size;
   /** \brief host (default) | device: where criteo text is parsed */
   std::string text_parse;
+  /** \brief host (default) | device: where the records of a data_format = rec input are inflated.  Without shuffle_rows / val_fraction the output has one record per input
+   *  record; through the row store the rows are re-cut into records of equal size */
+  std::string rec_decode;
   /** \brief 1: the rows of the whole input are written in a shuffled order (dfh_rowstore_order); 0 (default): in file order */
   int shuffle_rows;
   /** \brief the seed of that order */
@@ -65,6 +69,7 @@ struct ConverterParam : public dmlc::Parameter<ConverterParam> {
     DMLC_DECLARE_FIELD(part_size).set_default(-1);
     DMLC_DECLARE_FIELD(chunk_size).set_default(16);
     DMLC_DECLARE_FIELD(text_parse).set_default("host");
+    DMLC_DECLARE_FIELD(rec_decode).set_default("host");
   }
 };
 
@@ -83,6 +88,10 @@ class Converter {
         << "text_parse=" << param_.text_parse << " is not one of host (the default) and device";
     CHECK(param_.text_parse != "device" || param_.data_format == "criteo" || param_.data_format == "criteo_test")
         << "text_parse=device with data_format=" << param_.data_format << ": the device parses criteo and criteo_test text only";
+    CHECK(param_.rec_decode == "host" || param_.rec_decode == "device")
+        << "rec_decode=" << param_.rec_decode << " is not one of host (the default) and device";
+    CHECK(param_.rec_decode != "device" || param_.data_format == "rec")
+        << "rec_decode=device with data_format=" << param_.data_format << ": the device decodes the records of rec files only";
     CHECK_GT(param_.chunk_size, 0) << "chunk_size is a size in MB";
     CHECK(param_.shuffle_rows == 0 || param_.shuffle_rows == 1)
         << "shuffle_rows=" << param_.shuffle_rows << " is not one of 0 (file order, the default) and 1";
@@ -104,8 +113,11 @@ class Converter {
     DeviceTextParse text_parse;   // outlives the reader
     ParseHook hook;
     if (device_parse && rec) hook = text_parse.Hook(ctx, param_.data_format == "criteo" ? 1 : 0);
+    DeviceRecDecode rec_decode;   // the same for the records of a .rec input
+    const bool device_decode = param_.rec_decode == "device" && rec;
+    if (device_decode) hook = rec_decode.Hook(ctx);
     const size_t chunk_bytes = static_cast<size_t>(static_cast<double>(param_.chunk_size) * 1024 * 1024);
-    const int threads = hook && getenv("DIFACTO_PARSER_THREADS") == nullptr ? DeviceTextParse::kThreads : 0;
+    const int threads = !hook || getenv("DIFACTO_PARSER_THREADS") != nullptr ? 0 : (device_decode ? DeviceRecDecode::kThreads : DeviceTextParse::kThreads);
     Reader in(param_.data_in, param_.data_format, 0, 1, std::max<size_t>(chunk_bytes, 64), threads, hook);
     LOG(INFO) << "reading data from " << param_.data_in << " in " << param_.data_format << " format";
     // a small pool of encoders: the encode of chunk t + 1 runs while the record of chunk t is copied back and written
@@ -118,7 +130,8 @@ class Converter {
       for (auto e : pool) dfh_crb_destroy(e);
       Close();
       LOG(INFO) << "done. written " << nwrite_ << " bytes";
-      if (hook) text_parse.Log(param_.data_in);
+      if (device_parse && hook) text_parse.Log(param_.data_in);
+      if (device_decode) rec_decode.Log(param_.data_in);
       return;
     }
     std::deque<std::future<Encoded>> pending;   // in file order
@@ -141,7 +154,8 @@ class Converter {
     for (auto e : pool) dfh_crb_destroy(e);
     Close();
     LOG(INFO) << "done. written " << nwrite_ << " bytes";
-    if (hook) text_parse.Log(param_.data_in);
+    if (device_parse && hook) text_parse.Log(param_.data_in);
+    if (device_decode) rec_decode.Log(param_.data_in);
   }
 
  private:

@@ -89,6 +89,10 @@ int main(int argc, char* argv[]) {
     CHECK(!(kw.first == "text_parse" && kw.second == "device" && param.learner != "sgd" && param.task != "convert"))
         << "text_parse=device with learner=" << param.learner << ": only learner=sgd reads its training data through the device "
            "feed, whose text the device parses; leave text_parse out";
+  for (const auto& kw : kwargs_remain)
+    CHECK(!(kw.first == "rec_decode" && kw.second == "device" && param.learner != "sgd" && param.task != "convert"))
+        << "rec_decode=device with learner=" << param.learner << ": only learner=sgd reads its training data through the device "
+           "feed, whose records the device decodes; leave rec_decode out";
   if (param.task == "train") {
     Learner* learner = Learner::Create(param.learner);
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));

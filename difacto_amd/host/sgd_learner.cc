@@ -9,6 +9,7 @@
 #include <thread>
 #include <unistd.h>
 #include "./device_feed.h"
+#include "./device_rec_decode.h"
 #include "./device_text_parse.h"
 #include "./hip_fm_loss.h"
 #include "./host_localizer.h"
@@ -85,6 +86,25 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
     CHECK(param_.shuffle > 0 || param_.data_cache == "hbm" || param_.task == "predict")
         << "text_parse=device without a shuffle buffer: training data goes through the device feed only with shuffle > 0 or "
            "data_cache=hbm; set one of them, or leave text_parse out";
+  }
+  // rec_decode: the same conditions for the records of a .rec file
+  for (const auto& kv : remain) {
+    if (kv.first != "rec_decode") continue;
+    CHECK(kv.second == "host" || kv.second == "device")
+        << "rec_decode=" << kv.second << " is not one of host (the default) and device";
+    if (kv.second != "device") continue;
+    CHECK(param_.data_format == "rec")
+        << "rec_decode=device with data_format=" << param_.data_format << ": the device decodes the records of rec files only "
+           "(criteo text has text_parse=device, libsvm and adfea need the host's number parsing)";
+    CHECK(!IsDistributed()) << "rec_decode=device with a sharded store (DMLC_ROLE is set): the sharded worker loop does not read "
+                               "through the device feed; run one process, or leave rec_decode out";
+    for (const auto& kw : remain)
+      CHECK(!(kw.first == "device_path" && kw.second == "literal"))
+          << "rec_decode=device with device_path=literal: the literal loop hands host arrays to Store and Loss, only "
+             "device_path=fused reads its minibatches out of device row buffers";
+    CHECK(param_.shuffle > 0 || param_.data_cache == "hbm" || param_.task == "predict")
+        << "rec_decode=device without a shuffle buffer: training data goes through the device feed only with shuffle > 0 or "
+           "data_cache=hbm; set one of them, or leave rec_decode out";
   }
   auto updater = new DeviceSGDUpdater();
   remain = updater->Init(remain);
@@ -300,6 +320,9 @@ struct SGDLearner::FusedSource {
   // text_parse = device: the reader's parser threads hand every chunk of criteo text to the device, the ids stay in HBM with the
   // chunk's container.  A chunk that is not regular is left to the host parser (counted: logged at the end of the job)
   bool device_parse = false;
+  // rec_decode = device: the same for the records of a .rec file, whose LZ4 blocks the device decodes (a record with values or
+  // weights is left to the host decoder, counted)
+  bool device_decode = false;
   bool uploads() const { return device_feed && !cpart; }   // the feed uploads the reader's buffers (a cached part's are there)
 };
 
@@ -311,6 +334,7 @@ SGDLearner::FusedSource SGDLearner::SourceOf(const sgd::Job& job, const SgdLoopE
   s.device_feed = s.cpart || s.cache_fill || (job.type == sgd::Job::kTraining && param_.shuffle > 0 && !env.host_feed);
   const bool criteo = param_.data_format == "criteo" || param_.data_format == "criteo_test";
   s.device_parse = GetUpdater()->device_param().text_parse == "device" && s.uploads() && criteo;
+  s.device_decode = GetUpdater()->device_param().rec_decode == "device" && s.uploads() && param_.data_format == "rec";
   return s;
 }
 
@@ -318,7 +342,7 @@ SGDLearner::FusedSource SGDLearner::SourceOf(const sgd::Job& job, const SgdLoopE
 // overlap (sgd_learner.cc:196-224).  Device feed: buffers as slices of the parsed chunks (no host assembly), uploaded by the
 // thread that builds them
 BatchReader* SGDLearner::NewFusedReader(const sgd::Job& job, const FusedSource& src, const SgdLoopEnv& env, DeviceFeed* feed,
-                                        DeviceTextParse* text_parse) {
+                                        DeviceTextParse* text_parse, DeviceRecDecode* rec_decode) {
   const bool train = job.type == sgd::Job::kTraining;
   const bool permute = train && param_.shuffle > 0;
   const unsigned cache_buf_rows = static_cast<unsigned>(param_.batch_size) * static_cast<unsigned>(std::max(param_.shuffle, 1));
@@ -335,8 +359,12 @@ BatchReader* SGDLearner::NewFusedReader(const sgd::Job& job, const FusedSource& 
   }
   ParseHook parse_hook;
   if (src.device_parse) parse_hook = text_parse->Hook(DeviceContext::Get(), param_.data_format == "criteo" ? 1 : 0);
+  if (src.device_decode) parse_hook = rec_decode->Hook(DeviceContext::Get());
   // the device parses: the parser threads only upload and wait (DeviceTextParse::kThreads; DIFACTO_PARSER_THREADS overrides)
-  const int parser_threads = src.device_parse && !env.parser_threads_set ? DeviceTextParse::kThreads : 0;
+  const int parser_threads = env.parser_threads_set  ? 0
+                             : src.device_parse      ? DeviceTextParse::kThreads
+                             : src.device_decode     ? DeviceRecDecode::kThreads
+                                                     : 0;
   BatchReader* reader = new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
                                         src.cache_fill ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0), sampling,
                                         src.device_feed, upload, src.cache_fill ? permute : true, parse_hook, parser_threads);
@@ -358,6 +386,7 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
   // 53.6 -> 59.4 M rows/s by this loop's clock); bench.py, whose inputs are in HBM already, loses 5 % with two: it keeps one
   DFH_CALL(dfh_ctx_set_pipeline(ctx, env.prep_streams ? env.prep_streams : (src.device_feed ? 2 : 1)));
   DeviceTextParse text_parse;   // (outlives the reader, whose parser threads count into it)
+  DeviceRecDecode rec_decode;   // (the same)
   DeviceFeed feed(ctx, env);    // outlives the reader, whose thread uploads into it
   feed.cached = src.cpart;
   feed.retain = src.cache_fill;
@@ -366,11 +395,12 @@ void SGDLearner::IterateDataFused(const sgd::Job& job, sgd::Progress* progress) 
     feed.budget = cap > static_cast<double>(cache_.bytes) ? static_cast<size_t>(cap - static_cast<double>(cache_.bytes)) : 0;
   }
   // described minibatches are ~120 KB each: a deeper queue lets the loop ride out the reader's pause at a buffer boundary
-  PrefetchSource reader(NewFusedReader(job, src, env, &feed, &text_parse), src.device_feed ? BatchRing::kMax : 2);
+  PrefetchSource reader(NewFusedReader(job, src, env, &feed, &text_parse, &rec_decode), src.device_feed ? BatchRing::kMax : 2);
   RunFused(job, src, env, &reader, &feed, progress);
   uint64_t nkeys;
   DFH_CALL(dfh_table_size(GetUpdater()->table(), &nkeys));  // surfaces a full table as an error
   if (src.device_parse) text_parse.Log(JobData(job));
+  if (src.device_decode) rec_decode.Log(JobData(job));
   if (src.cache_on) CloseCachedJob(job, src, &feed);
 }
 

@@ -35,6 +35,7 @@
 namespace difacto {
 struct DeviceFeed;
 struct DeviceTextParse;
+struct DeviceRecDecode;
 
 class SGDLearner : public Learner {
  public:
@@ -71,7 +72,7 @@ class SGDLearner : public Learner {
   struct FusedSource;
   FusedSource SourceOf(const sgd::Job& job, const SgdLoopEnv& env);
   BatchReader* NewFusedReader(const sgd::Job& job, const FusedSource& src, const SgdLoopEnv& env, DeviceFeed* feed,
-                              DeviceTextParse* text_parse);
+                              DeviceTextParse* text_parse, DeviceRecDecode* rec_decode);
   void RunFused(const sgd::Job& job, const FusedSource& src, const SgdLoopEnv& env, BatchSource* reader, DeviceFeed* feed,
                 sgd::Progress* prog);
   void CloseCachedJob(const sgd::Job& job, const FusedSource& src, DeviceFeed* feed);

@@ -107,8 +107,13 @@ struct DeviceParam : public dmlc::Parameter<DeviceParam> {
    *  that is not made of regular rows alone is still parsed on the host).  SGDLearner::Init refuses "device" wherever the
    *  training data is not read through the device feed */
   std::string text_parse;
+  /*! \brief where the records of data_format = rec are inflated for the device feed of the fused SGD loop: "host" (default: the
+   *  parser threads, host/lz4_block.h) or "device" (csrc/dfh_lz4dec.hip: the compressed record is uploaded, the ids never visit
+   *  the host; a record with values or weights is still inflated on the host).  Refused where text_parse = device is */
+  std::string rec_decode;
   DMLC_DECLARE_PARAMETER(DeviceParam) {
     DMLC_DECLARE_FIELD(text_parse).set_default("host");
+    DMLC_DECLARE_FIELD(rec_decode).set_default("host");
     DMLC_DECLARE_FIELD(feed_ids_per_row).set_range(1, 1 << 20).set_default(48);
     DMLC_DECLARE_FIELD(shard_ranges).set_default("balanced");
     DMLC_DECLARE_FIELD(shard_exchange).set_default("overlap");

@@ -283,6 +283,21 @@ int dfh_textchunk_destroy(dfh_textchunk* tc);
 int dfh_textchunk_parse_criteo(dfh_textchunk* tc, const char* text, size_t len, int is_train, int* regular, size_t* nrows, size_t* nnz);
 int dfh_textchunk_rows(dfh_textchunk* tc, uint32_t* offset, float* label);
 int dfh_textchunk_ids(dfh_textchunk* tc, uint64_t* index);
+/* rec_decode = device (csrc/dfh_lz4dec.hip).  dfh_lz4_decompress is the counterpart of dfh_lz4_compress: the ONE LZ4 block of `n`
+ * bytes at `src` (host; they are uploaded) is decoded on the device.  *ok = 1 and dst[0 .. expect) is filled exactly when the host
+ * decoder (host/lz4_block.h: Lz4DecompressBlock(src, n, dst, expect)) returns `expect`; otherwise *ok = 0, the call returns DFH_OK
+ * and nothing is written to dst.  n = 0 is ok only with expect = 0; n or expect >= 2^31 - 2^25 is refused (DFH_ERR_ARG).
+ * The call is a test and tool entry, not a hot path: it creates its device arrays and frees them again on every call (the
+ * arrays that grow and are reused belong to a dfh_textchunk: dfh_textchunk_decode_crb).
+ * dfh_textchunk_decode_crb: one CompressedRowBlock record (the payload of a RecordIO record of a .rec file) becomes a chunk in
+ * the state dfh_textchunk_parse_criteo leaves a regular chunk in: ids in HBM, u32 offsets from 0 and labels on the host
+ * (dfh_textchunk_rows / _ids).  *regular = 1 only if the header is the one DecompressRowBlock accepts (host/batch_reader.h),
+ * nrows >= 1, the offset array is present, does not decrease and spans fewer than 2^31 nonzeros, the index array is present and
+ * inflates to exactly 8 nnz bytes, the label array is absent (labels are 0) or inflates to 4 nrows bytes, VALUE AND WEIGHT ARE
+ * ABSENT, and every present block is a valid LZ4 block.  *regular = 0 is not an error: nothing else is valid and the caller
+ * inflates the record on the host.  The host waits twice per record: for the blocks' sizes, and for the rows' 8 bytes each. */
+int dfh_lz4_decompress(dfh_ctx* c, const void* src, size_t n, void* dst, size_t expect, int* ok);
+int dfh_textchunk_decode_crb(dfh_textchunk* tc, const void* record, size_t len, int* regular, size_t* nrows, size_t* nnz);
 /* task = convert: .rec records written on the device (csrc/dfh_lz4enc.hip).  dfh_lz4_compress: `n` bytes at `src` (host; they are
  * uploaded) -> ONE LZ4 block at `dst` that a conforming decoder (LZ4_decompress_safe, host/lz4_block.h) inflates to exactly those
  * bytes: the last sequence is literals only, the last 5 bytes are literals, no match starts within the last 12 bytes, offsets are
