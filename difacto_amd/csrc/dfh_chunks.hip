@@ -26,10 +26,6 @@ inline int check_free(const char* who, const char* what, const char* tail, size_
   return DFH_OK;
 }
 
-inline hipError_t reset_prog(dfh_batch* b, hipStream_t s) {
-  return hipMemsetAsync(b->d_prog, 0, dfh_batch::kProgDoubles * sizeof(double), s);
-}
-
 inline void release(Resident& r) {
   if (r.b) dfh_batch_destroy(r.b);
   r.b = nullptr;

@@ -1,4 +1,4 @@
-// dfh_feed.hip — the device feed of the SGD worker loop (included in dfh_api.hip ahead of the dfh_batch_load_* calls, which
+// dfh_feed.hip — the device feed of the SGD worker loop (included in dfh_api.hip ahead of dfh_batch.hip, whose load calls
 // share its staging helpers).  The shuffle buffer of BatchReader (src/reader/batch_reader.cc:38-52) lives in HBM as a row
 // buffer (dfh_rowbuf); a minibatch is DESCRIBED by row numbers — the host sends 4 B per row instead of copying ~300 B per row
 // twice (batch_reader.cc:53-63) — in the batch object's page-locked staging block, which the device reads in place
@@ -29,8 +29,6 @@ struct dfh_rowbuf {
 };
 
 namespace {
-int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe);   // dfh_api.hip
-
 // DFH_PROFILE_PREP: host seconds by section of a call, added up in acc[]
 struct PrepLaps {
   double* acc;

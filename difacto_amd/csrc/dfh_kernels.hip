@@ -128,7 +128,7 @@ __device__ __forceinline__ uint32_t find_or_insert(const TableView& t, uint64_t 
   }
 }
 
-// growth of a table (dfh_api.hip table_grow): every {key, row} of the old index into the new, larger one.  Runs alone on
+// growth of a table (dfh_table.hip table_grow): every {key, row} of the old index into the new, larger one.  Runs alone on
 // the table (every stream drained); distinct keys only race for slots.
 __global__ void k_rehash(const HEntry* __restrict__ old_ht, uint64_t old_slots, HEntry* __restrict__ ht, uint64_t hmask) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(256) k_auc_finalize(AucFin f) { auc_finalize_b
 // INVARIANT (one owner): the list is empty when a training step's first listing launch starts.  The STEP keeps it.  A batch
 // object has TWO counters (d_U + 2, d_U + 3; both zero at creation): the listing launches of a step append to one (`n`) and
 // leave the OTHER at zero (split_other: one store by the launch's first thread), and the step that listed then swaps them
-// (split_out / main_end, dfh_api.hip) — so the next step, whenever it comes and whether or not a localize came between, starts
+// (split_out / main_end, dfh_phases.hip) — so the next step, whenever it comes and whether or not a localize came between, starts
 // from a counter that the previous step's launches zeroed, and this step's update reads the one just filled.  The reset
 // costs no launch of its own (a 4-byte memset node per step was measured at -3 % on the default benchmark line).  A step may
 // make two listing launches, the own keys' lookup and the others' row words (sharded store): both append to the same

@@ -67,7 +67,7 @@ constexpr int LOC_BIG_BUCKETS = 4096;   // round 4: the large size class (miniba
 constexpr int LOC_AVG_BUCKET = 384;    // target pairs per bucket
 constexpr int LOC_MIN_AVG = 48;        // stored splitters are reused while N / P stays in [MIN, MAX]
 constexpr int LOC_MAX_AVG = 700;
-// (tests/test_loc_sort_runs.py shapes its minibatches by these two, by DFH_LOC_SMALL_AVG of dfh_api.hip and by emit's splitters so
+// (tests/test_loc_sort_runs.py shapes its minibatches by these two, by DFH_LOC_SMALL_AVG of dfh_localize_api.hip and by emit's splitters so
 // that n = 1 .. 1 024 pairs land in ONE bucket; it asserts no bucket count, so a change here must revisit its primers.
 // tests/keyview_ref.py designs its minibatches by the same constants and by LOC_LDS_CAP, and asserts the bucket starts it
 // expects through dfh_batch_get_key_view: a change here shows there as a failed premise)

@@ -21,7 +21,7 @@
 //     P        owners: Push(kGradient) of the other sources, applied in ascending rank order in ONE launch
 // A key's pushes are applied owner first, then the other sources in ascending rank order — one legal
 // execution of the reference's asynchronous Push protocol, the same on every run.  With one rank
-// nothing is exchanged and nothing waits for the host.  L and F are step_lookup and step_math (dfh_api.hip), the two
+// nothing is exchanged and nothing waits for the host.  L and F are step_lookup and step_math (dfh_step.hip), the two
 // worker stages dfh_sgd_step is made of as well: with one rank both steps queue the same launches.
 // Every stage is one function of the minibatch's Flight (flight_L, flight_K, flight_R, flight_RW, flight_F, flight_G,
 // flight_P); the two exchange modes are two schedules over them: shard_step_sync (every stage on the context's stream, one
@@ -284,7 +284,7 @@ struct StageScope {
 // kernels, which run on the context's stream — and which events order the stages.  The events are the overlap schedule's:
 // a stage waits for the ones it is handed inside its timing bracket, before its work, and records `done` behind it; the
 // sync schedule hands none.
-// The list of the very hot keys' parts for the update's split role (split_out, dfh_api.hip) is filled by the launches of a
+// The list of the very hot keys' parts for the update's split role (split_out, dfh_phases.hip) is filled by the launches of a
 // training step that see the minibatch's keys — the own keys' lookup (L, ranks offset by own_lo) and the others' row words
 // (k_uw_remote in F, or folded into L), BOTH appending to the one counter the batch object's previous step left at zero (SplitOut).
 inline int wait_on(hipStream_t st, hipEvent_t e) {

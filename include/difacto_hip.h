@@ -88,7 +88,7 @@ int dfh_ctx_set_pipeline(dfh_ctx* ctx, int enable);
  *   "bwd_small_blocks"  1 .. 65536      cap on the short-segment blocks of the backward launch (default 2048)
  *   "prep_priority"     -1 | 0 | 1      stream priority of the preparation streams: lowest (default),
  *                                       normal, highest; before dfh_ctx_set_pipeline creates them
- *   "upd_kernel", "upd_*_blocks", "upd_interleave", "event_flags": see csrc/dfh_api.hip (measurement switches)
+ *   "upd_kernel", "upd_*_blocks", "upd_interleave", "event_flags": see csrc/dfh_ctx.hip (measurement switches)
  *   "grow_initial_rows" 16 .. 2^28      first allocation of a growing table (dfh_table_create, capacity_rows = 0; default 2^20)
  *   "auc_in_update"     0 | 1           BinClassMetric::AUC of a training step (batch option "compute_auc") as the first
  *                                       blocks of the update launch (default 1) or as a launch of its own

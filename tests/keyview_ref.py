@@ -14,7 +14,7 @@ does not depend on it beyond the order inside a key.
 import numpy as np
 
 SHIFT = 8                 # designed keys are (rank + 1) << SHIFT: the keys of a stale primer (below) fit in between
-SMALL_AVG = 192           # dfh_api.hip: pairs per bucket a first call with up to 65 536 pairs aims for
+SMALL_AVG = 192           # dfh_localize_api.hip: pairs per bucket a first call with up to 65 536 pairs aims for
 LDS_CAP = 1024            # dfh_localize.hip: LOC_LDS_CAP
 
 

@@ -5,7 +5,7 @@ One block sorts one bucket: every wave sorts 64 pairs of the bucket in registers
 pairs into ONE bucket — a lone pair, runs one short of / exactly / one over the 64 lanes, one and two full merge rounds, the LDS
 capacity of 1 024 pairs — and keys that exercise each word of the 96-bit compare on its own.
 
-How the pairs land in one bucket (dfh_api.hip: localize_impl; nothing here depends on it for its RESULT, only for its coverage):
+How the pairs land in one bucket (dfh_localize_api.hip: localize_impl; nothing here depends on it for its RESULT, only for its coverage):
   * a first call on a batch object with N <= 192 pairs takes P = 1 bucket: the cases up to 129 pairs are one cold call;
   * the stored splitters are kept while N / P stays within [48, 700]: after a first minibatch of 100 pairs (P = 1) a minibatch of
     511 .. 513 pairs is one bucket again;
@@ -14,7 +14,7 @@ How the pairs land in one bucket (dfh_api.hip: localize_impl; nothing here depen
 
 The one-bucket premise above is NOT asserted here (dfh_batch_get_key_view shows the bucket starts since; tests/test_key_view.py
 asserts the premises of its own designs through it): it holds for LOC_MIN_AVG = 48,
-LOC_MAX_AVG = 700 (dfh_localize.hip), DFH_LOC_SMALL_AVG = 192 (dfh_api.hip) and splitters = the previous minibatch's quantiles; a
+LOC_MAX_AVG = 700 (dfh_localize.hip), DFH_LOC_SMALL_AVG = 192 (dfh_localize_api.hip) and splitters = the previous minibatch's quantiles; a
 change to any of them turns the larger cases into ordinary multi-bucket sorts (still correct, no longer this file's subject).  A
 comment next to the constants points back here.
 

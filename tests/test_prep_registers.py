@@ -20,7 +20,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 
 BUDGET = 32
 
-# the preparation stream's kernels as the library instantiates them (dfh_api.hip: launch_loc_stage, the probe), C3's size class
+# the preparation stream's kernels as the library instantiates them (dfh_pending.hip: launch_loc_stage; dfh_localize_api.hip: the probe), C3's size class
 TU = r"""
 #include <hip/hip_runtime.h>
 #include "dfh_kernels.hip"

@@ -593,3 +593,102 @@ def test_literal_push_pull_on_the_sharded_store(tmp_path, oracle, WORLD):
             v, l = store.pull(reqs[r][c]["keys"])
             assert np.array_equal(got[r]["lens_after%d" % c], l)
             np.testing.assert_allclose(got[r]["after%d" % c], v, rtol=2e-6, atol=1e-7, err_msg="call %d rank %d" % (c, r))
+
+
+@pytest.mark.gpu
+def test_owner_side_store_calls_refuse_in_their_order():
+    """What the twelve device-pointer store calls refuse, and which refusal wins where two apply: a NULL pointer with keys, a
+    table without optimiser state (before the empty call returns), V_init other than hash for the calls on resolved rows (before
+    the empty call returns; in the `_multi` forms before seg is read, in dfh_shard_count_pull_multi only with counts), a bad seg.
+    Every refusal precedes the launch: the one device buffer passed as every pointer is never read."""
+    from difacto_amd import capi
+    ARG, STATE = 1, 4
+
+    def refused(code, text, f, *a, **kw):
+        with pytest.raises(capi.DfhError) as e:
+            f(*a, **kw)
+        assert e.value.code == code and text in str(e.value), (f.__name__, str(e.value))
+
+    ctx = capi.Context()
+    d = capi.DeviceBuffer(ctx, 4096).ptr
+    th = capi.Table(ctx, 64, V_dim=4)
+    tr = capi.Table(ctx, 64, V_dim=4, init_mode=capi.INIT_REFRAND)
+    tr0 = capi.Table(ctx, 64, V_dim=0, init_mode=capi.INIT_REFRAND)   # no V to initialise: as good as hash
+    seg, empty = [0, 2, 4], [0, 0, 0]
+    plain = [(th.shard_pull, (d, d)), (th.shard_push_count, (d, d)), (th.shard_push_grad, (d, d)), (th.shard_resolve, (d, d)),
+             (th.shard_pull_resolved, (d, d))]
+    keyed = [(th.shard_push_count_resolved, (d, d, d)), (th.shard_push_grad_resolved, (d, d, d))]
+    for t in (th, tr, tr0):
+        assert t.has_aux
+
+    # ---- NULL with n > 0 (every pointer in turn), nothing to do with n = 0
+    for f, ptrs in plain:
+        for miss in range(2):
+            a = [None if i == miss else d for i in range(2)]
+            refused(ARG, "dfh_%s: NULL argument" % f.__name__, f, a[0], 4, a[1])
+        f(None, 0, None)
+    for f, ptrs in keyed:
+        for miss in range(3):
+            a = [None if i == miss else d for i in range(3)]
+            refused(ARG, "dfh_%s: NULL argument" % f.__name__, f, a[0], a[1], 4, a[2])
+        f(None, None, 0, None)
+    refused(ARG, "dfh_shard_resolve_multi: NULL argument", th.shard_resolve_multi, None, seg, d)
+    refused(ARG, "dfh_shard_resolve_multi: NULL argument", th.shard_resolve_multi, d, seg, None)
+    th.shard_resolve_multi(None, empty, None)
+    for name in ("push_count_multi", "push_grad_multi", "push_grad_listed"):
+        f = getattr(th, "shard_" + name)
+        for miss in range(3):
+            a = [None if i == miss else d for i in range(3)]
+            refused(ARG, "dfh_shard_%s: NULL argument" % name, f, a[0], a[1], seg, a[2])
+        f(None, None, empty, None)
+    for a in ((None, d, seg, d, d), (d, None, seg, d, d), (d, d, seg, d, None), (d, None, seg, None, d)):
+        refused(ARG, "dfh_shard_count_pull_multi: NULL argument", th.shard_count_pull_multi, *a)
+    th.shard_count_pull_multi(None, None, empty, None, None)
+
+    # ---- a bad seg, in the checks' order
+    multi = lambda t: [(t.shard_resolve_multi, (d,), (d,)), (t.shard_push_count_multi, (d, d), (d,)), (t.shard_push_grad_multi, (d, d), (d,)),
+                       (t.shard_count_pull_multi, (d, d), (d, d)), (t.shard_count_pull_multi, (d, d), (None, d)),
+                       (t.shard_push_grad_listed, (d, d), (d,))]
+    for f, pre, post in multi(th):
+        refused(ARG, "seg must hold nsrc+1 offsets", f, *pre, [0], *post)
+        refused(ARG, "seg must hold nsrc+1 offsets", f, *pre, [0] * 34, *post)
+        refused(ARG, "mask_slot must be 0 or 1", f, *pre, seg, *post, mask_slot=2)
+        refused(ARG, "seg[0] must be 0", f, *pre, [1, 2, 4], *post)
+        refused(ARG, "seg must be ascending offsets below 2^27", f, *pre, [0, 3, 2], *post)
+        refused(ARG, "seg must be ascending offsets below 2^27", f, *pre, [0, 2, (1 << 27) - 1], *post)
+        f(*pre, empty, *post)   # nothing to do
+
+    # ---- V_init = refrand with V: the calls on resolved rows refuse, before n == 0 and before seg is read
+    for n in (4, 0):
+        refused(STATE, "resolved store calls need V_init = hash", tr.shard_push_count_resolved, d, d, n, d)
+        refused(STATE, "resolved store calls need V_init = hash", tr.shard_push_grad_resolved, d, d, n, d)
+    for bad in (seg, empty, [1, 2, 4]):
+        refused(STATE, "multi-source store calls need V_init = hash", tr.shard_push_count_multi, d, d, bad, d)
+        refused(STATE, "multi-source store calls need V_init = hash", tr.shard_push_grad_multi, d, d, bad, d)
+        refused(STATE, "multi-source store calls need V_init = hash", tr.shard_push_grad_listed, d, d, bad, d)
+        refused(STATE, "multi-source store calls need V_init = hash", tr.shard_count_pull_multi, d, d, bad, d, d)
+    refused(ARG, "seg[0] must be 0", tr.shard_count_pull_multi, d, d, [1, 2, 4], None, d)   # without counts: any V_init
+    tr.shard_count_pull_multi(d, d, empty, None, d)
+    tr.shard_resolve_multi(d, empty, d)
+    for f, pre, post in multi(tr0):   # V_dim = 0: nothing is initialised, every call goes through
+        f(*pre, empty, *post)
+    tr0.shard_push_count_resolved(d, d, 0, d)
+    tr0.shard_push_grad_resolved(d, d, 0, d)
+
+    # ---- no optimiser state: the gradient pushes refuse, before n == 0, before V_init and before seg
+    for t in (th, tr):
+        t.set_has_aux(False)
+        for n in (4, 0):
+            refused(STATE, "dfh_shard_push_grad: no aux data", t.shard_push_grad, d, n, d)
+            refused(STATE, "dfh_shard_push_grad_resolved: no aux data", t.shard_push_grad_resolved, d, d, n, d)
+        for bad in (seg, empty, [1, 2, 4]):
+            refused(STATE, "dfh_shard_push_grad_multi: no aux data", t.shard_push_grad_multi, d, d, bad, d)
+            refused(STATE, "dfh_shard_push_grad_listed: no aux data", t.shard_push_grad_listed, d, d, bad, d)
+    refused(ARG, "dfh_shard_push_grad: NULL argument", th.shard_push_grad, None, 4, d)   # ... but after the NULL check
+    th.shard_push_count(None, 0, None)   # the other calls do not ask for it
+    th.shard_pull_resolved(None, 0, None)
+    th.shard_push_count_multi(None, None, empty, None)
+    for t in (th, tr, tr0):
+        t.check()
+        t.close()
+    ctx.close()
