@@ -11,7 +11,8 @@
 #include <hip/hip_ext.h>
 #include <rocprim/rocprim.hpp>
 
-#include "dfh_kernels.hip"       // the views and kernels of table, step and store (dfh_internal.h: the error macros)
+#include "dfh_kernels.hip"       // the views and kernels of table and step, the update arithmetic (dfh_internal.h: the error macros)
+#include "dfh_owner.hip"         // the owner side of the sharded store, four forms: find_or_insert and the update arithmetic
 #include "dfh_localize.hip"      // the Localizer's kernels (dfh_feed_layout.h: the staging layout shared with the host side)
 #include "dfh_update.hip"        // k_update_fused: the views of dfh_kernels.hip
 #include "dfh_riders.hip"        // the rider forms of lookup, forward and update: the kernels of the three files above

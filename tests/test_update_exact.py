@@ -451,10 +451,19 @@ def test_owner_side_forms_one_source_bit_exact(capi, ctx, oracle, V_dim, mode, f
         tb.close()
 
 
+# G = 9: a key of all sources has m = 8 other entries (XS = 8), the one m at which the per-entry push leaves its register path
+# while the per-key count + pull still takes its own; G = 5: m = 4 = XS, the second read of four extras is masked.
+_SEVERAL_FORMS = [("plain", 3, "hash"), ("plain", 3, "refrand"), ("resolved", 3, "hash"), ("multi", 3, "hash"), ("listed", 3, "hash"),
+                  ("multi", 11, "hash"), ("listed", 11, "hash"), ("multi", 9, "hash"), ("listed", 9, "hash"), ("multi", 5, "hash"),
+                  ("listed", 5, "hash")]
+# V_dim 0, 5, 64: lane groups of 1, 2, 16 that all lie inside the row.  9 (kp = 12, 4 lanes: lane 3 beyond the row, lane 2 with a
+# tail of three zeroed elements) and 100 (32 lanes, 25 - 31 beyond the row): lanes beyond a non-empty row, in the lane-group forms
+_SEVERAL_CASES = ([(f, G, m, V) for f, G, m in _SEVERAL_FORMS for V in (0, 5, 64)]
+                  + [(f, 3, "hash", V) for f in ("resolved", "multi", "listed") for V in (9, 100)])
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("V_dim", [0, 5, 64])
-@pytest.mark.parametrize("form,G,mode", [("plain", 3, "hash"), ("plain", 3, "refrand"), ("resolved", 3, "hash"), ("multi", 3, "hash"),
-                                         ("listed", 3, "hash"), ("multi", 11, "hash"), ("listed", 11, "hash")])
+@pytest.mark.parametrize("form,G,mode,V_dim", _SEVERAL_CASES)
 def test_owner_side_forms_several_sources_bit_exact(capi, ctx, oracle, V_dim, mode, form, G):
     """several sources carrying the same keys in one step: the result equals the oracle's pushes applied in source order
     (each source's gradient with the has_V flags as pulled at the start of the step), by full export, bit for bit"""
