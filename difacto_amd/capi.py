@@ -47,6 +47,8 @@ SYMBOLS = [
     "dfh_rowbuf_load_slices",
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
     "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
+    "dfh_predtext_create", "dfh_predtext_destroy", "dfh_predtext_reset", "dfh_predtext_append_batch", "dfh_predtext_append_host",
+    "dfh_predtext_count", "dfh_predtext_values", "dfh_predtext_format", "dfh_predtext_read", "dfh_predtext_tile",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
@@ -216,6 +218,16 @@ def lib():
     L.dfh_eval_append_batch.argtypes = [vp, vp]
     L.dfh_eval_append_host.argtypes = [vp, vp, vp, sz]
     L.dfh_eval_finish.argtypes = [vp, PP(EvalResult)]
+    L.dfh_predtext_create.argtypes = [vp, sz, PP(vp)]
+    L.dfh_predtext_destroy.argtypes = [vp]
+    L.dfh_predtext_reset.argtypes = [vp]
+    L.dfh_predtext_append_batch.argtypes = [vp, vp]
+    L.dfh_predtext_append_host.argtypes = [vp, vp, sz]
+    L.dfh_predtext_count.argtypes = [vp, PP(C.c_uint64)]
+    L.dfh_predtext_values.argtypes = [vp, vp]
+    L.dfh_predtext_format.argtypes = [vp, PP(sz), PP(C.c_uint64)]
+    L.dfh_predtext_read.argtypes = [vp, vp]
+    L.dfh_predtext_tile.argtypes = []
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -846,6 +858,66 @@ class Eval:
     def close(self):
         if self.h:
             lib().dfh_eval_destroy(self.h)
+            self.h = None
+
+
+class _LibInt:
+    """a class attribute whose value the library exports as an int function of no arguments"""
+
+    def __init__(self, symbol):
+        self.symbol = symbol
+
+    def __get__(self, obj, cls):
+        return int(getattr(lib(), self.symbol)())
+
+
+class PredText:
+    """prediction text on the device (dfh_predtext): the bytes of fprintf("%.9g\\n", v) for the appended values"""
+
+    TILE = _LibInt("dfh_predtext_tile")   # the values a block of the format kernels takes
+
+    def __init__(self, ctx, capacity_hint=0):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _ck(lib().dfh_predtext_create(ctx.h, capacity_hint, C.byref(self.h)))
+
+    def reset(self):
+        _ck(lib().dfh_predtext_reset(self.h))
+
+    def append_batch(self, batch):
+        """the batch's predictions, queued behind its last step; does not wait"""
+        _ck(lib().dfh_predtext_append_batch(self.h, batch.h))
+
+    def append_host(self, v):
+        v = np.ascontiguousarray(v, np.float32)
+        assert v.ndim == 1
+        _ck(lib().dfh_predtext_append_host(self.h, _p(v), v.size))
+
+    def count(self):
+        n = C.c_uint64(0)
+        _ck(lib().dfh_predtext_count(self.h, C.byref(n)))
+        return n.value
+
+    def values(self):
+        """the appended floats (waits)"""
+        out = np.zeros(max(self.count(), 1), np.float32)
+        _ck(lib().dfh_predtext_values(self.h, _p(out)))
+        return out[:self.count()]
+
+    def format(self):
+        """-> (text bytes, irregular); everything appended since the last reset (waits; nothing is consumed).  The text is
+        valid when irregular == 0, else it is b'' and the caller formats values() itself"""
+        nb, irr = C.c_size_t(0), C.c_uint64(0)
+        _ck(lib().dfh_predtext_format(self.h, C.byref(nb), C.byref(irr)))
+        if irr.value or nb.value == 0:
+            return b"", irr.value
+        buf = C.create_string_buffer(nb.value)
+        _ck(lib().dfh_predtext_read(self.h, buf))
+        return buf.raw, irr.value
+
+    def close(self):
+        if self.h:
+            lib().dfh_predtext_destroy(self.h)
             self.h = None
 
 

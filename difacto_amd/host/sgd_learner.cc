@@ -27,6 +27,7 @@ DMLC_REGISTER_PARAMETER(FMLossParam);
 
 SGDLearner::~SGDLearner() {
   if (eval_) dfh_eval_destroy(eval_);
+  if (predtext_) dfh_predtext_destroy(predtext_);
   delete loss_;
   delete store_;
 }
@@ -66,6 +67,17 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
     CHECK(param_.task != "train" || param_.data_val.size())
         << "exact_metrics=1 with task=train and no data_val: there is nothing to evaluate; name a validation file with "
            "data_val=<file>, or leave exact_metrics out";
+  }
+  // pred_write: checked before anything touches the device, like data_cache
+  CHECK(param_.pred_write == "host" || param_.pred_write == "device")
+      << "pred_write=" << param_.pred_write << " is not one of host (the default) and device";
+  CHECK_GE(param_.pred_unit_rows, 1) << "pred_unit_rows=" << param_.pred_unit_rows << " is not a number of rows: a unit of "
+                                        "pred_write=device closes at 1 row or more (the default is 4194304)";
+  if (param_.pred_write == "device") {
+    CHECK(param_.task == "predict") << "pred_write=device with task=" << param_.task << ": nothing is predicted, the key says where "
+                                       "the text of task=predict is formatted; use task=predict, or leave pred_write out";
+    CHECK(!IsDistributed()) << "pred_write=device with a sharded store (DMLC_ROLE is set): the sharded worker loop writes its "
+                               "predictions on the host; run one process, or leave pred_write out";
   }
   // text_parse: checked before anything touches the device, like data_cache.  "device" is accepted only where the device feed
   // reads the training data (IterateDataFused); validation and prediction readers outside the feed keep the host parser
@@ -262,6 +274,55 @@ void SGDLearner::WritePredictions(dfh_batch* b) {
   }
 }
 
+void SGDLearner::WaitPredWrite() {
+  if (pred_write_.valid()) pred_write_.get();
+}
+
+// pred_write = device.  pred_prob = 1: the sigmoid stays the host's expression (the device's expf is not the C library's bit for
+// bit, and pred_out must not depend on the key): the unit's logits come down, the probabilities go back up to be formatted
+void SGDLearner::ClosePredUnit() {
+  dfh_predtext* pt = CHECK_NOTNULL(predtext_);
+  const size_t n = pred_unit_n_;
+  pred_unit_n_ = 0;
+  if (param_.pred_prob) {
+    pred_buf_.resize(n);
+    DFH_CALL(dfh_predtext_values(pt, pred_buf_.data()));
+    for (size_t i = 0; i < n; ++i) pred_buf_[i] = 1.0f / (1.0f + std::exp(-pred_buf_[i]));
+    DFH_CALL(dfh_predtext_reset(pt));
+    DFH_CALL(dfh_predtext_append_host(pt, pred_buf_.data(), n));
+  }
+  size_t nbytes = 0;
+  uint64_t irregular = 0;
+  DFH_CALL(dfh_predtext_format(pt, &nbytes, &irregular));
+  if (irregular == 0) {
+    // unit u - 1 may still be on its way to the file out of the other buffer: its write overlaps this download, and ends
+    // before this unit's write begins
+    std::vector<char>& text = pred_text_[pred_text_cur_];
+    pred_text_cur_ ^= 1;
+    text.resize(nbytes);
+    DFH_CALL(dfh_predtext_read(pt, text.data()));
+    WaitPredWrite();
+    FILE* f = CHECK_NOTNULL(pred_file_);
+    const std::string* name = &param_.pred_out;
+    pred_write_ = std::async(std::launch::async, [f, name, &text] {
+      CHECK_EQ(fwrite(text.data(), 1, text.size(), f), text.size()) << "cannot write " << *name;
+    });
+    pred_counts_.dev_rows += n;
+    ++pred_counts_.dev_units;
+  } else {   // a value the device does not format: the whole unit as pred_write = host writes it
+    if (!param_.pred_prob) {
+      pred_buf_.resize(n);
+      DFH_CALL(dfh_predtext_values(pt, pred_buf_.data()));
+    }
+    WaitPredWrite();
+    for (size_t i = 0; i < n; ++i)
+      CHECK_GT(fprintf(CHECK_NOTNULL(pred_file_), "%.9g\n", pred_buf_[i]), 0) << "cannot write " << param_.pred_out;
+    pred_counts_.host_rows += n;
+    ++pred_counts_.host_units;
+  }
+  DFH_CALL(dfh_predtext_reset(pt));
+}
+
 void SGDLearner::MergeAcrossRanks(sgd::Progress* prog) {
   auto* ss = dynamic_cast<ShardedDeviceStore*>(store_);
   if (!ss) return;
@@ -323,6 +384,10 @@ struct SGDLearner::FusedSource {
   // rec_decode = device: the same for the records of a .rec file, whose LZ4 blocks the device decodes (a record with values or
   // weights is left to the host decoder, counted)
   bool device_decode = false;
+  // pred_write = device: the prediction job reads through the device feed too, in file order as a cache_fill validation job does
+  // (buffers of batch_size x max(shuffle, 1) rows read through in order), without keeping the buffers
+  bool pred_feed = false;
+  bool in_order() const { return cache_fill || pred_feed; }
   bool uploads() const { return device_feed && !cpart; }   // the feed uploads the reader's buffers (a cached part's are there)
 };
 
@@ -331,7 +396,8 @@ SGDLearner::FusedSource SGDLearner::SourceOf(const sgd::Job& job, const SgdLoopE
   s.cache_on = param_.data_cache == "hbm" && job.type != sgd::Job::kPrediction;
   s.cpart = s.cache_on ? cache_.Find(job.type, job.part_idx) : nullptr;
   s.cache_fill = s.cache_on && !s.cpart && !cache_.refused.count(std::make_pair(job.type, job.part_idx));
-  s.device_feed = s.cpart || s.cache_fill || (job.type == sgd::Job::kTraining && param_.shuffle > 0 && !env.host_feed);
+  s.pred_feed = job.type == sgd::Job::kPrediction && param_.pred_write == "device";
+  s.device_feed = s.cpart || s.cache_fill || s.pred_feed || (job.type == sgd::Job::kTraining && param_.shuffle > 0 && !env.host_feed);
   const bool criteo = param_.data_format == "criteo" || param_.data_format == "criteo_test";
   s.device_parse = GetUpdater()->device_param().text_parse == "device" && s.uploads() && criteo;
   s.device_decode = GetUpdater()->device_param().rec_decode == "device" && s.uploads() && param_.data_format == "rec";
@@ -351,7 +417,7 @@ BatchReader* SGDLearner::NewFusedReader(const sgd::Job& job, const FusedSource& 
   BatchReader::SliceFn upload;
   if (src.uploads()) {
     // (a buffer that is kept gets an allocation of its own size: nothing is created ahead)
-    const size_t buf_rows = static_cast<size_t>(param_.batch_size) * param_.shuffle;
+    const size_t buf_rows = src.pred_feed ? cache_buf_rows : static_cast<size_t>(param_.batch_size) * param_.shuffle;
     feed->Start(src.cache_fill ? 0 : buf_rows, buf_rows * static_cast<size_t>(GetUpdater()->device_param().feed_ids_per_row));
     upload = [feed](const dmlc::RowBlock<feaid_t>& blk, const std::vector<BufSlice>& slices, uint64_t serial) {
       feed->Upload(blk, slices, serial);
@@ -366,8 +432,8 @@ BatchReader* SGDLearner::NewFusedReader(const sgd::Job& job, const FusedSource& 
                              : src.device_decode     ? DeviceRecDecode::kThreads
                                                      : 0;
   BatchReader* reader = new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
-                                        src.cache_fill ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0), sampling,
-                                        src.device_feed, upload, src.cache_fill ? permute : true, parse_hook, parser_threads);
+                                        src.in_order() ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0), sampling,
+                                        src.device_feed, upload, src.in_order() ? permute : true, parse_hook, parser_threads);
   if (src.uploads()) reader->DescribeSlices(nullptr);
   return reader;
 }
@@ -418,6 +484,12 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
   // and host-feed jobs have a prefetch depth of 2 and rotate three (six times the HBM and creation time for nothing)
   const int nrot = src.device_feed ? BatchRing::kMax : 3;
   const int ahead = env.single_queue ? 2 : 1;
+  if (src.pred_feed) {
+    if (!predtext_) DFH_CALL(dfh_predtext_create(ctx, 0, &predtext_));
+    DFH_CALL(dfh_predtext_reset(predtext_));
+    pred_unit_n_ = 0;
+    pred_counts_ = PredCounts();
+  }
   // DIFACTO_PROFILE=1: where the host thread of this loop spends its time (reader wait + batch assembly, staging + Localizer /
   // lookup queueing, step queueing; t_feed: inside the second, waiting for a buffer's upload), printed at the end of the job
   const bool prof = env.profile;
@@ -483,7 +555,15 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     dfh_batch* b = ring_[BatchRing::SlotOf(i, nrot)];
     DFH_CALL(dfh_sgd_step(table, b, train ? 1 : 0, push_cnt ? 1 : 0));
     if (eval_ && !train) DFH_CALL(dfh_eval_append_batch(eval_, b));  // exact_metrics = 1: queued behind the step
-    if (predict) WritePredictions(b);
+    if (predict && src.pred_feed) {   // pred_write = device: queued behind the step, nothing waits
+      DFH_CALL(dfh_predtext_append_batch(predtext_, b));
+      size_t nrows = 0;
+      DFH_CALL(dfh_batch_shape(b, &nrows, nullptr, nullptr));
+      pred_unit_n_ += nrows;
+      if (pred_unit_n_ >= static_cast<size_t>(param_.pred_unit_rows)) ClosePredUnit();
+    } else if (predict) {
+      WritePredictions(b);
+    }
     ++i;
   };
   auto prepare_next = [&] {
@@ -513,9 +593,19 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     step_one();
     lap(&t_step);
   }
+  if (src.pred_feed) {   // a unit closes at the end of every data part
+    if (pred_unit_n_) ClosePredUnit();
+    WaitPredWrite();
+    lap(&t_step);
+  }
   if (prof)
     LOG(INFO) << "host loop over " << i << " minibatches: reader " << t_read << " s, stage + localize + lookup " << t_prep
               << " s (" << t_feed << " s of it waiting for a buffer's upload), step " << t_step << " s";
+  if (src.pred_feed) {
+    LOG(INFO) << "pred_write=device: " << pred_counts_.dev_rows << " rows in " << pred_counts_.dev_units
+              << " units formatted on the device, " << pred_counts_.host_rows << " rows in " << pred_counts_.host_units
+              << " units on the host";
+  }
   ring_.Drain(progress);
 }
 

@@ -20,6 +20,7 @@
 #define DIFACTO_HOST_SGD_LEARNER_H_
 #include <cstdio>
 #include <functional>
+#include <future>
 #include <string>
 #include <vector>
 #include "./batch_ring.h"
@@ -62,6 +63,11 @@ class SGDLearner : public Learner {
   void RunPrediction();
   /*! \brief prediction jobs: the step's logits, one line per example, appended to the job's output file */
   void WritePredictions(dfh_batch* b);
+  /*! \brief pred_write = device: the unit's predictions become text on the device (or, a unit the device does not format, on
+   *  the host) and go to the job's output file, behind the unit before it; the unit starts empty again */
+  void ClosePredUnit();
+  /*! \brief pred_write = device: waits for the unit that is still being written */
+  void WaitPredWrite();
   /*! \brief exact_metrics = 1: the whole-set figures of the pass that has just ended, as one log line behind `what` */
   void LogExactMetrics(const char* what);
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
@@ -95,6 +101,14 @@ class SGDLearner : public Learner {
   FILE* pred_file_ = nullptr;       // open while a prediction job runs
   std::vector<float> pred_buf_;
   dfh_eval* eval_ = nullptr;        // exact_metrics = 1: the rows of the current validation / prediction pass
+  // pred_write = device: the open unit's predictions, two text buffers (unit u is written while unit u + 1 is stepped and
+  // downloaded), the write under way, and the job's counts for its log line
+  dfh_predtext* predtext_ = nullptr;
+  std::vector<char> pred_text_[2];
+  int pred_text_cur_ = 0;
+  std::future<void> pred_write_;
+  size_t pred_unit_n_ = 0;
+  struct PredCounts { size_t dev_rows = 0, dev_units = 0, host_rows = 0, host_units = 0; } pred_counts_;
 };
 
 }  // namespace difacto

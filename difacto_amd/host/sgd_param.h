@@ -31,6 +31,11 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   std::string task;          // "train" (default) | "predict": forward pass of model_in over data_val (else data_in)
   std::string pred_out;      // predict: one line per example, in file order (<pred_out>.part-<i> per data part of a sharded run)
   int pred_prob;             // predict: 0 writes the logit FMLoss::Predict returns (default), 1 writes 1 / (1 + exp(-logit))
+  // pred_write = device (keys of this build; one process, the fused loop): the prediction job reads through the device feed, its
+  // predictions stay on the device and are turned into the same text there (csrc/dfh_predtext.hip), a UNIT at a time; pred_out
+  // has the same bytes under both values.  A unit holding a value the device does not format is written by the host
+  std::string pred_write;    // predict: "host" (default: fprintf per value on the loop's thread) | "device"
+  int pred_unit_rows;        // predict, pred_write = device: a unit closes after the minibatch that brings it to this many rows (>= 1)
   // data_cache = hbm (a key of this build; the reference's lbfgs and bcd params have one of that name): the parsed rows of
   // every data part stay in device memory after the epoch that read them, later epochs open no file (sgd_data_cache.h)
   std::string data_cache;    // "" (default: every epoch reads its files) | "hbm"
@@ -42,6 +47,8 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
     DMLC_DECLARE_FIELD(pred_prob).set_default(0);
+    DMLC_DECLARE_FIELD(pred_write).set_default("host");
+    DMLC_DECLARE_FIELD(pred_unit_rows).set_default(4194304);
     DMLC_DECLARE_FIELD(data_cache).set_default("");
     DMLC_DECLARE_FIELD(data_cache_max_gb).set_default(0);
     DMLC_DECLARE_FIELD(exact_metrics).set_default(0);

@@ -849,6 +849,43 @@ int dfh_eval_append_batch(dfh_eval* e, dfh_batch* b);
 int dfh_eval_append_host(dfh_eval* e, const float* label, const float* pred, size_t n);
 int dfh_eval_finish(dfh_eval* e, dfh_eval_result* out);
 
+/* ------------------------------------------------ prediction text (pred_write = device) */
+/* A dfh_predtext keeps every value appended since the last reset in device memory (4 B per value; the array grows by doubling,
+ * earlier content survives) and turns them into the text fprintf("%.9g\n", v) writes for each, byte for byte, concatenated in
+ * order (csrc/dfh_predtext.hip; the arithmetic, exact and integer only: csrc/dfh_predtext_fmt.h).
+ *   - the device formats the REGULAR values: +0, -0 and the finite v with 2^-64 <= |v| < 2^32.  Every logit the FM forward
+ *     clamps to +-20 is regular unless it is nonzero and below 5.4e-20, and so is every sigmoid of one.  Anything else
+ *     (non-finite, tiny, huge, subnormal) is counted: dfh_predtext_format then reports irregular > 0, the text is not to be
+ *     used, and the caller formats that set itself from dfh_predtext_values
+ *   - a line has at most 16 bytes with its '\n'
+ * capacity_hint: the values of the first allocation (0: 65 536).  The object holds fewer than 2^32 - 16 values (DFH_ERR_ARG); a
+ * failed allocation is DFH_ERR_CAPACITY with the bytes needed in the message. */
+typedef struct dfh_predtext dfh_predtext;
+int dfh_predtext_create(dfh_ctx* ctx, size_t capacity_hint, dfh_predtext** out);
+int dfh_predtext_destroy(dfh_predtext* p);
+/* n = 0; the arrays stay */
+int dfh_predtext_reset(dfh_predtext* p);
+/* queues a copy of the batch's nrows predictions on the context's stream, behind the batch's last step (dfh_sgd_step), and does
+ * not wait for the device; call it before the next minibatch is loaded into the batch object (with pipelining on, that load
+ * waits for the copy: the call moves the object's `free` event behind it).  It may stand beside dfh_eval_append_batch on the
+ * same batch, in either order. */
+int dfh_predtext_append_batch(dfh_predtext* p, dfh_batch* b);
+/* copies a host array and returns when it is free */
+int dfh_predtext_append_host(dfh_predtext* p, const float* v, size_t n);
+/* the values appended since the last reset */
+int dfh_predtext_count(dfh_predtext* p, uint64_t* n);
+/* the appended floats into out [count]; synchronises */
+int dfh_predtext_values(dfh_predtext* p, float* out);
+/* formats everything appended since the last reset: two launches and a scan between them, then ONE host round trip for
+ * *nbytes (the text's length) and *irregular (the values the device does not format; > 0: the text is not valid).  It changes
+ * nothing: more may be appended, and a later format covers all of it. */
+int dfh_predtext_format(dfh_predtext* p, size_t* nbytes, uint64_t* irregular);
+/* the text of the last format into dst [nbytes] (downloaded into page-locked memory of the object's, then copied); valid when
+ * that format reported irregular == 0.  DFH_ERR_STATE when something was appended or reset since the last format. */
+int dfh_predtext_read(dfh_predtext* p, char* dst);
+/* the values a block of the format kernels takes: the text of a tile starts wherever the tile before it ends (for tests) */
+int dfh_predtext_tile(void);
+
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
 int dfh_free(dfh_ctx* ctx, void* dptr);
