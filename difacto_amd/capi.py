@@ -50,6 +50,7 @@ SYMBOLS = [
     "dfh_predtext_create", "dfh_predtext_destroy", "dfh_predtext_reset", "dfh_predtext_append_batch", "dfh_predtext_append_host",
     "dfh_predtext_count", "dfh_predtext_values", "dfh_predtext_format", "dfh_predtext_read", "dfh_predtext_tile",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
+    "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_tile",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
@@ -228,6 +229,13 @@ def lib():
     L.dfh_predtext_format.argtypes = [vp, PP(sz), PP(C.c_uint64)]
     L.dfh_predtext_read.argtypes = [vp, vp]
     L.dfh_predtext_tile.argtypes = []
+    L.dfh_dump_open.argtypes = [vp, i32, PP(vp), PP(C.c_uint64)]
+    L.dfh_dump_close.argtypes = [vp]
+    L.dfh_dump_shape.argtypes = [vp, PP(C.c_uint64), PP(C.c_uint64), PP(i32)]
+    L.dfh_dump_format.argtypes = [vp, C.c_uint64, sz, PP(sz), PP(C.c_uint64)]
+    L.dfh_dump_read.argtypes = [vp, vp]
+    L.dfh_dump_entries.argtypes = [vp, C.c_uint64, sz, vp, vp, vp, vp]
+    L.dfh_dump_tile.argtypes = [vp]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -918,6 +926,61 @@ class PredText:
     def close(self):
         if self.h:
             lib().dfh_predtext_destroy(self.h)
+            self.h = None
+
+
+DUMP_IDS_FEATURE, DUMP_IDS_KEY = 0, 1
+
+
+class ModelDump:
+    """a table's kept entries in ascending order of their printed id, and their text "<id>\\t<w>[\\t<V_j>]\\n" formatted on the
+    device (dfh_dump).  The table must stay open and unchanged while the dump is"""
+
+    def __init__(self, table, ids_mode=DUMP_IDS_FEATURE):
+        self.table = table
+        self.V_dim = table.V_dim
+        self.h = C.c_void_p()
+        n = C.c_uint64(0)
+        _ck(lib().dfh_dump_open(table.h, ids_mode, C.byref(self.h), C.byref(n)))
+        self.n = n.value
+
+    @property
+    def tile(self):
+        """the entries a block of the format kernels takes (by V_dim; tiles count from a unit's first entry)"""
+        return int(lib().dfh_dump_tile(self.h))
+
+    def shape(self):
+        """-> (kept entries, those with V, V_dim)"""
+        n, nv, k = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        _ck(lib().dfh_dump_shape(self.h, C.byref(n), C.byref(nv), C.byref(k)))
+        return n.value, nv.value, k.value
+
+    def format(self, first=0, count=None):
+        """-> (text bytes, irregular) of entries [first, first + count) (count None: to the end).  The text is valid when
+        irregular == 0, else it is b'' and the caller formats entries(first, count) itself"""
+        count = self.n - first if count is None else count
+        nb, irr = C.c_size_t(0), C.c_uint64(0)
+        _ck(lib().dfh_dump_format(self.h, first, count, C.byref(nb), C.byref(irr)))
+        if irr.value or nb.value == 0:
+            return b"", irr.value
+        buf = C.create_string_buffer(nb.value)
+        _ck(lib().dfh_dump_read(self.h, buf))
+        return buf.raw, irr.value
+
+    def entries(self, first=0, count=None):
+        """-> dict(ids, w, has_V, V [count x V_dim] or None) of the same entries"""
+        count = self.n - first if count is None else count
+        k = self.V_dim
+        ids = np.zeros(max(count, 1), np.uint64)
+        w = np.zeros(max(count, 1), np.float32)
+        has = np.zeros(max(count, 1), np.int32)
+        V = np.zeros(max(count * k, 1), np.float32)
+        _ck(lib().dfh_dump_entries(self.h, first, count, _p(ids), _p(w), _p(has), _p(V)))
+        return dict(ids=ids[:count], w=w[:count], has_V=has[:count], V=V[:count * k].reshape(count, k) if k else None)
+
+    def close(self):
+        if self.h:
+            lib().dfh_dump_close(self.h)
             self.h = None
 
 

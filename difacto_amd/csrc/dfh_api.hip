@@ -42,4 +42,5 @@ using namespace dfh;
 #include "dfh_bcd.hip"           // learner = bcd: the chunk set, the join, the communicator
 #include "dfh_eval.hip"          // whole-set evaluation, exact AUC, logloss and accuracy of the appended rows: the handles
 #include "dfh_predtext.hip"      // prediction text, the bytes of fprintf("%.9g\n") for the appended values: the handles
+#include "dfh_dumptext.hip"      // a model table as sorted text, "<id>\t<w>[\t<V_j>]" per kept entry: the table calls, dfh_predtext_fmt.h
 #include "dfh_rowstore.hip"      // a whole data set's rows in HBM and its shuffled blocks: the encoder, the parsed and decoded chunks

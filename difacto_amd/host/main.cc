@@ -9,6 +9,7 @@
 #include <fstream>
 #include <sstream>
 #include "./converter.h"
+#include "./model_dump.h"
 #include "difacto/learner.h"
 #include "dmlc/config.h"
 #include "dmlc/parameter.h"
@@ -16,7 +17,7 @@
 namespace difacto {
 
 struct DifactoParam : public dmlc::Parameter<DifactoParam> {
-  std::string task;     // train (default) | predict | convert
+  std::string task;     // train (default) | predict | convert | dump
   std::string learner;  // sgd
   DMLC_DECLARE_PARAMETER(DifactoParam) {
     DMLC_DECLARE_FIELD(learner).set_default("sgd");
@@ -25,6 +26,7 @@ struct DifactoParam : public dmlc::Parameter<DifactoParam> {
 };
 DMLC_REGISTER_PARAMETER(DifactoParam);
 DMLC_REGISTER_PARAMETER(ConverterParam);
+DMLC_REGISTER_PARAMETER(ModelDumpParam);
 
 /*! \brief collects argv tokens and config-file text, then parses them as one "k = v" stream */
 class ArgParser {
@@ -135,8 +137,13 @@ int main(int argc, char* argv[]) {
     Converter converter;
     WarnUnknownKWArgs(param, converter.Init(kwargs_remain));
     converter.Run();
+  } else if (param.task == "dump") {
+    // model_in -> dump_out: the model as sorted text, "<id>\t<w>[\t<V_j>]" per entry, formatted on the device
+    ModelDump dump;
+    WarnUnknownKWArgs(param, dump.Init(kwargs_remain));
+    dump.Run();
   } else {
-    LOG(FATAL) << "unknown task: " << param.task << " (this build provides train, predict and convert)";
+    LOG(FATAL) << "unknown task: " << param.task << " (this build provides train, predict, convert and dump)";
   }
   return 0;
 }

@@ -886,6 +886,40 @@ int dfh_predtext_read(dfh_predtext* p, char* dst);
 /* the values a block of the format kernels takes: the text of a tile starts wherever the tile before it ends (for tests) */
 int dfh_predtext_tile(void);
 
+/* ------------------------------------------------ a model as sorted text (task = dump) */
+/* A dfh_dump is a view of a table's KEPT entries (w != 0 || has_V: dfh_table_save's rule without aux) in ascending order of the
+ * id they are printed under, and a formatter of their text (csrc/dfh_dumptext.hip; the arithmetic: csrc/dfh_predtext_fmt.h and
+ * csrc/dfh_dumptext_fmt.h).  A line is "<id>\t<w>" and, when the entry has V, "\t<V_j>" for j = 0 .. V_dim - 1, then "\n": the
+ * id as %llu, every float as %.9g; at most 20 + 16 (1 + V_dim) + 1 bytes.  No header line, no optimiser state.
+ *   - ids_mode: DFH_DUMP_IDS_FEATURE prints reverse_bytes(key), the id as it stands in the user's data (the table stores the
+ *     Localizer's reversed ids); DFH_DUMP_IDS_KEY prints the stored key.  Keys are unique, so the order, and with it every byte,
+ *     is a function of the model alone: not of hash slots, capacity or import order
+ *   - dfh_dump_open selects and sorts once (12 B of device memory per kept entry, twice that and the sort's workspace during
+ *     the call); the rows are read in place afterwards.  The table must outlive the dump and stay unchanged while it is open
+ *   - the device formats the REGULAR floats (+-0 and 2^-64 <= |v| < 2^32, see dfh_predtext above); a unit with any other value
+ *     reports irregular > 0, its text is not to be used, and the caller formats the unit from dfh_dump_entries
+ * Errors: DFH_ERR_ARG for NULL arguments, another ids_mode and first + count beyond the entries; DFH_ERR_CAPACITY for a failed
+ * allocation, with the bytes needed in the message. */
+enum { DFH_DUMP_IDS_FEATURE = 0, DFH_DUMP_IDS_KEY = 1 };
+typedef struct dfh_dump dfh_dump;
+int dfh_dump_open(dfh_table* t, int ids_mode, dfh_dump** out, uint64_t* n_entries);
+int dfh_dump_close(dfh_dump* d);
+/* the kept entries, those of them that have V, the table's V_dim (any pointer may be NULL) */
+int dfh_dump_shape(dfh_dump* d, uint64_t* n_entries, uint64_t* n_with_V, int* V_dim);
+/* formats entries [first, first + count) of the sorted list: two launches and a scan between them, then ONE host round trip
+ * for *nbytes (the text's length) and *irregular (the values the device does not format; > 0: the text is not valid) */
+int dfh_dump_format(dfh_dump* d, uint64_t first, size_t count, size_t* nbytes, uint64_t* irregular);
+/* the text of the last format into dst [nbytes] (downloaded into page-locked memory of the object's, then copied); valid when
+ * that format reported irregular == 0.  DFH_ERR_STATE before the first format. */
+int dfh_dump_read(dfh_dump* d, char* dst);
+/* the same entries as arrays: ids [count] as printed, w [count], has_V [count], V [count x V_dim] (zeros where !has_V; may be
+ * NULL with V_dim = 0): for the host's formatting of a unit and for tests */
+int dfh_dump_entries(dfh_dump* d, uint64_t first, size_t count, uint64_t* ids, float* w, int* has_V, float* V);
+/* the entries a block of the format kernels takes, by the table's V_dim so that a tile's longest text fits the LDS image (for
+ * tests; tiles count from the unit's first entry).  0: V_dim is above 2045, dfh_dump_format refuses (DFH_ERR_ARG) and the
+ * entries are formatted on the host */
+int dfh_dump_tile(dfh_dump* d);
+
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
 int dfh_free(dfh_ctx* ctx, void* dptr);
