@@ -11,11 +11,18 @@
 #include <hip/hip_ext.h>
 #include <rocprim/rocprim.hpp>
 
-#include "dfh_kernels.hip"       // the views and kernels of table and step, the update arithmetic (dfh_internal.h: the error macros)
+#include "dfh_device.h"          // lane, wave and lane-group helpers, float4 loads and stores (dfh_internal.h: the views, the error macros)
+#include "dfh_updater.h"         // the update arithmetic per key, the values InitV writes: dfh_device.h
+#include "dfh_index.hip"         // the key index and the table as arrays: hash_init_value (dfh_updater.h)
+#include "dfh_auc.hip"           // a minibatch's AUC, by pairs and by sort: dfh_device.h
+#include "dfh_lookup.hip"        // the lookup passes and REFRAND: the key index, InitV, auc_finalize_block
+#include "dfh_forward.hip"       // k_forward, the progress slots, KeyRange, k_penalty: dfh_device.h
+#include "dfh_backward.hip"      // k_backward_all and k_seg_lists: the update arithmetic, the progress slots and KeyRange
 #include "dfh_owner.hip"         // the owner side of the sharded store, four forms: find_or_insert and the update arithmetic
-#include "dfh_localize.hip"      // the Localizer's kernels (dfh_feed_layout.h: the staging layout shared with the host side)
-#include "dfh_update.hip"        // k_update_fused: the views of dfh_kernels.hip
-#include "dfh_riders.hip"        // the rider forms of lookup, forward and update: the kernels of the three files above
+#include "dfh_localize.hip"      // the Localizer's kernels, sample sort and library sort, and the key ranges of its output: find_or_insert,
+                                 // BWD_* (dfh_feed_layout.h: the staging layout shared with the host side)
+#include "dfh_update.hip"        // k_update_fused: the update arithmetic, auc_pairs_block, KeyRange, BWD_*
+#include "dfh_riders.hip"        // the rider forms of lookup, forward and update: lookup_body, forward_body, the two files above
 
 using namespace dfh;
 
@@ -25,8 +32,9 @@ using namespace dfh;
 #include "dfh_ctx.hip"           // context calls and the option table: sync_all (dfh_phases.hip), flush_pending
 #include "dfh_table.hip"         // table growth and the table calls: sync_all, the grid and scratch helpers
 #include "dfh_store_calls.hip"   // owner-side and literal Store calls: table_reserve, require_aux, refrand_flush, dispatch_L
-#include "dfh_loss.hip"          // literal Loss calls: the scratch helpers
-#include "dfh_step.hip"          // the step's launches, its two stages, dfh_sgd_step: collect_riders, the phases, the table helpers
+#include "dfh_loss.hip"          // literal Loss calls and their kernels: the scratch helpers
+#include "dfh_auc_api.hip"       // the AUC's launches, either form, and dfh_auc_times_n: the handles, the scratch helpers
+#include "dfh_step.hip"          // the step's launches, its two stages, dfh_sgd_step: collect_riders, the phases, the table helpers, launch_auc
 #include "dfh_textparse.hip"     // the device text parse, chunks whose ids the feed's uploads take device to device: the handles
 #include "dfh_lz4enc.hip"        // the device LZ4 block encoder and the row-block records of task = convert: the parsed chunks
 #include "dfh_lz4dec.hip"        // the device LZ4 block decoder, .rec records decoded into chunks like the parsed ones: dfh_textparse.hip

@@ -1,5 +1,9 @@
 // dfh_ctx.hip — the context calls: create / destroy, preparation streams, the option table (measurement switches and launch
 // tuning), per-kernel timing, and the plain device memory calls.
+namespace dfh {
+__global__ void k_set_u32(uint32_t* p, uint32_t v) { *p = v; }
+}  // namespace dfh
+
 namespace {
 // the options of dfh_ctx_set_option that store an int of [lo, hi] and do nothing else (defaults and meaning: dfh_handles.h)
 struct IntOption { const char* name; int dfh_ctx::*field; int lo, hi; const char* msg; };

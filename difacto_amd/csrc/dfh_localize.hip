@@ -55,8 +55,9 @@
 // reference's outputs.  Everything is deterministic.
 #ifndef DFH_LOCALIZE_HIP_
 #define DFH_LOCALIZE_HIP_
-#include "dfh_internal.h"
-#include "dfh_feed_layout.h"   // LOC_TILE, LOC_GATHER_ROWS, LOC_GATHER_SEGS, LOC_DESC_ROWS: shared with the host side
+#include "dfh_index.hip"       // find_or_insert (the probing emit)
+#include "dfh_backward.hip"    // BWD_SMALL, BWD_MID: the lists emit fills are the ones k_seg_lists fills
+#include "dfh_feed_layout.h"  // LOC_TILE, LOC_GATHER_ROWS, LOC_GATHER_SEGS, LOC_DESC_ROWS: shared with the host side
 
 namespace dfh {
 
@@ -1042,6 +1043,105 @@ template <bool PROBE>
 __global__ void __launch_bounds__(LOC_EMIT_THREADS) k_loc_emit(LocView v, EmitOut o, TableView tab, uint32_t* __restrict__ urow) {
   __shared__ __attribute__((aligned(16))) char smem[loc_emit_smem()];
   loc_emit_block<PROBE>(v, o, tab, urow, blockIdx.x, gridDim.x, smem);
+}
+
+// ---------------------------------------------------------------------------
+// Device Localizer::Compact (src/data/localizer.cc:11-103) around a stable
+// radix sort of (key, position) pairs.
+// ---------------------------------------------------------------------------
+// keys[i] = ReverseBytes(id % max_index), pos[i] = i   (localizer.cc:22-26)
+__global__ void k_rdx_keys(const uint64_t* __restrict__ raw, uint32_t nnz, uint64_t max_index,
+                           uint64_t* __restrict__ keys, uint32_t* __restrict__ pos) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += gridDim.x * blockDim.x) {
+    keys[i] = reverse_bytes(raw[i] % max_index);
+    pos[i] = i;
+  }
+}
+
+// head flags of runs of equal keys (localizer.cc:35-48)
+__global__ void k_rdx_heads(const uint64_t* __restrict__ skeys, uint32_t nnz, uint32_t* __restrict__ head) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += gridDim.x * blockDim.x) {
+    head[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1u : 0u;
+  }
+}
+
+// uid = inclusive_scan(head) - 1.  Emits the dictionary, the segment starts,
+// the compact index per nnz (RemapIndex, localizer.cc:63-77) and the
+// key-ordered occurrence view (row, value) the backward pass walks.
+__global__ void k_rdx_emit(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ spos,
+                           const uint32_t* __restrict__ head, const uint32_t* __restrict__ uid_incl, uint32_t nnz,
+                           uint32_t nrows, const uint32_t* __restrict__ offset, const float* __restrict__ value,
+                           uint64_t* __restrict__ feaids, uint32_t* __restrict__ col_ptr, uint32_t* __restrict__ index,
+                           uint32_t* __restrict__ s_row, float* __restrict__ s_val, uint32_t* __restrict__ d_U) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += gridDim.x * blockDim.x) {
+    const uint32_t uid = uid_incl[i] - 1;
+    const uint32_t pos = spos[i];
+    if (head[i]) {
+      feaids[uid] = skeys[i];
+      col_ptr[uid] = i;
+    }
+    index[pos] = uid;
+    // row of nnz position pos: last r with offset[r] <= pos
+    uint32_t lo = 0, hi = nrows;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (offset[mid] <= pos) lo = mid; else hi = mid;
+    }
+    s_row[i] = lo;
+    if (value) s_val[i] = value[pos];
+    if (i == nnz - 1) {
+      *d_U = uid + 1;
+      col_ptr[uid + 1] = nnz;
+    }
+  }
+}
+
+// bounds[d] = first unique key of the batch owned by shard d (keys ascending; owner = key / span)
+__global__ void k_key_ranges(const uint64_t* __restrict__ feaids, const uint32_t* __restrict__ d_U, int nparts,
+                             uint64_t span, uint32_t* __restrict__ bounds) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > nparts) return;
+  const uint32_t U = *d_U;
+  if (d == nparts) {
+    bounds[d] = U;
+    return;
+  }
+  const uint64_t first = (uint64_t)d * span;  // d < nparts so this does not overflow
+  uint32_t lo = 0, hi = U;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (feaids[mid] < first) lo = mid + 1; else hi = mid;
+  }
+  bounds[d] = lo;
+}
+
+// the same bounds as int64 in caller-owned device memory (asynchronous sharded step)
+// splits != NULL: shard d (d >= 1) starts at key splits[d-1] (ascending) instead of d*span
+__global__ void k_key_ranges64(const uint64_t* __restrict__ feaids, const uint32_t* __restrict__ d_U, int nparts,
+                               uint64_t span, const uint64_t* __restrict__ splits, int64_t* __restrict__ bounds,
+                               uint32_t empty) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d > nparts) return;
+  const uint32_t U = empty ? 0u : *d_U;
+  if (d == nparts) {
+    bounds[d] = U;
+    return;
+  }
+  const uint64_t first = d == 0 ? 0ULL : (splits ? splits[d - 1] : (uint64_t)d * span);
+  uint32_t lo = 0, hi = U;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (feaids[mid] < first) lo = mid + 1; else hi = mid;
+  }
+  bounds[d] = lo;
+}
+
+// feacnt[u] = segment length (float), for reading the localizer's output back
+__global__ void k_loc_counts(const uint32_t* __restrict__ col_ptr, const uint32_t* __restrict__ d_U, float* __restrict__ cnt) {
+  const uint32_t U = *d_U;
+  for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < U; u += gridDim.x * blockDim.x) {
+    cnt[u] = (float)(col_ptr[u + 1] - col_ptr[u]);
+  }
 }
 
 }  // namespace dfh

@@ -1,5 +1,138 @@
 // dfh_loss.hip — the literal Loss calls on host pointers (FMLoss::Predict / CalcGrad, LogitLoss::Evaluate), staged through
-// the context's scratch block; to_u32_offsets also serves the host load calls of dfh_batch.hip.
+// the context's scratch block, with their three kernels; to_u32_offsets also serves the host load calls of dfh_batch.hip.
+namespace dfh {
+
+// ---------------------------------------------------------------------------
+// Literal Loss API kernels: arbitrary V_dim, arbitrary w_pos/V_pos into a
+// ragged weights array (host SArray semantics).  Sums run serially in the
+// reference's order per output element, so these agree with the CPU path to
+// rounding of FMA contraction only.
+// ---------------------------------------------------------------------------
+// one wave per example; lanes stride over the embedding dimension
+__global__ void __launch_bounds__(256) k_predict_generic(uint32_t nrows, const uint32_t* __restrict__ offset,
+                                                         const uint32_t* __restrict__ index, const float* __restrict__ value,
+                                                         const float* __restrict__ weights, const int* __restrict__ w_pos,
+                                                         const int* __restrict__ V_pos, int k, float* __restrict__ pred,
+                                                         float* __restrict__ xv_out, const float* __restrict__ label,
+                                                         const float* __restrict__ pred_in, float* __restrict__ slope_out) {
+  const int lane = lane_id();
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t i = wave; i < nrows; i += nwaves) {
+    const uint32_t beg = offset[i], end = offset[i + 1];
+    float wsum = 0.f;
+    if (pred && lane == 0) {
+      for (uint32_t j = beg; j < end; ++j) {  // SpMV::Times, spmv.h:119-132
+        const uint32_t u = index[j];
+        const int pj = w_pos ? w_pos[u] : (int)u;
+        if (pj < 0) continue;
+        const float xj = weights[pj];
+        if (xj == 0.f) continue;  // spmv.h:125
+        wsum += value ? xj * value[j] : xj;
+      }
+    }
+    float s = 0.f;
+    if (k > 0) {
+      for (int d = lane; d < k; d += 64) {
+        float a = 0.f, bb = 0.f;
+        for (uint32_t j = beg; j < end; ++j) {  // SpMM::Times x2, spmm.h:105-118
+          const int pj = V_pos[index[j]];
+          if (pj < 0) continue;
+          const float vv = weights[pj + d];
+          if (value) {
+            const float x = value[j];
+            a += vv * x;
+            bb += (vv * vv) * (x * x);
+          } else {
+            a += vv;
+            bb += vv * vv;
+          }
+        }
+        if (xv_out) xv_out[(size_t)i * k + d] = a;
+        s += a * a - bb;
+      }
+      s = wave_sum(s);
+    }
+    if (lane == 0) {
+      if (pred) {
+        float pr = pred[i] + wsum;  // pred is accumulated into
+        if (k > 0) {
+          pr += 0.5f * s;
+          pr = pr > 20.f ? 20.f : (pr < -20.f ? -20.f : pr);
+        }
+        pred[i] = pr;
+      }
+      if (slope_out) {
+        const float y = label[i] > 0 ? 1.0f : -1.0f;
+        slope_out[i] = -y / (1.0f + expf(y * pred_in[i]));
+      }
+    }
+  }
+}
+
+// one wave per column (unique key): grad[w_pos[u]] += X'p ; grad[V_pos[u]+d] += ...
+__global__ void __launch_bounds__(256) k_calcgrad_generic(uint32_t ncols, const uint32_t* __restrict__ col_ptr,
+                                                          const uint32_t* __restrict__ s_row, const float* __restrict__ s_val,
+                                                          const float* __restrict__ weights, const int* __restrict__ w_pos,
+                                                          const int* __restrict__ V_pos, int k, const float* __restrict__ slope,
+                                                          const float* __restrict__ xv, float* __restrict__ grad) {
+  const int lane = lane_id();
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t u = wave; u < ncols; u += nwaves) {
+    const uint32_t beg = col_ptr[u], end = col_ptr[u + 1];
+    const int pw = w_pos ? w_pos[u] : (int)u;
+    const int pv = (k > 0 && V_pos) ? V_pos[u] : -1;
+    if (lane == 0) {
+      float gw = 0.f;
+      for (uint32_t j = beg; j < end; ++j) {  // SpMV::TransTimes, spmv.h:152-168, ascending rows
+        const float p = slope[s_row[j]];
+        if (p == 0.f) continue;  // spmv.h:155
+        gw += s_val ? p * s_val[j] : p;
+      }
+      if (pw >= 0) grad[pw] += gw;
+    }
+    if (pv >= 0) {
+      float xxp = 0.f;
+      // every lane recomputes XXp serially (identical value, reference order)
+      for (uint32_t j = beg; j < end; ++j) {
+        const float p = slope[s_row[j]];
+        if (p == 0.f) continue;  // spmv.h:155
+        const float x = s_val ? s_val[j] : 1.0f;
+        xxp += p * (x * x);
+      }
+      for (int d = lane; d < k; d += 64) {
+        float g = grad[pv + d] - weights[pv + d] * xxp;  // fm_loss.h:181-188
+        for (uint32_t j = beg; j < end; ++j) {           // spmm.h:137-156, ascending rows
+          const uint32_t row = s_row[j];
+          const float a = xv[(size_t)row * k + d] * slope[row];
+          g += s_val ? a * s_val[j] : a;
+        }
+        grad[pv + d] = g;
+      }
+    }
+  }
+}
+
+// Loss::Evaluate over host-provided pred (literal API)
+__global__ void k_logloss(const float* __restrict__ label, const float* __restrict__ pred, uint32_t n, double* out) {
+  double acc = 0.0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float y = label[i] > 0 ? 1.0f : -1.0f;
+    acc += log(1.0 + exp((double)(-y * pred[i])));
+  }
+  __shared__ double sh[256];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = blockDim.x / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicAdd(out, sh[0]);
+}
+
+}  // namespace dfh
+
 namespace {
 int to_u32_offsets(const size_t* offset, size_t nrows, std::vector<uint32_t>* out) {
   out->resize(nrows + 1);

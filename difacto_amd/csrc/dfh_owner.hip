@@ -4,7 +4,7 @@
 //   per entry   k_resolve_multi / k_push_count_multi / k_pull_resolved / k_push_grad_multi (+ k_release_rows): the default
 //   per key     k_resolve_multi / k_count_pull_multi / k_push_grad_chunks                    (ctx option owner_per_key)
 // What they share stands once: LaneGroup, RowRegs (load, refuse, apply, store), sort8 / next_ascending, put_pull_row.  The
-// key index and the update arithmetic are dfh_kernels.hip's (find_or_insert, ftrl_update_w, adagrad_update_v, init_v_hash_*).
+// key index is dfh_index.hip's (find_or_insert), the update arithmetic dfh_updater.h's (ftrl_update_w, adagrad_update_v, init_v_hash_*).
 // ---------------------------------------------------------------------------
 // Owner side, one launch for ALL source ranks of a step.  The received keys are the
 // concatenation of nsrc ascending lists (SegOff).  k_resolve_multi resolves every entry to

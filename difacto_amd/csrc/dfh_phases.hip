@@ -69,7 +69,7 @@ int sync_all(dfh_ctx* c) {
   DFH_HIP(hipStreamSynchronize(c->stream));
   return DFH_OK;
 }
-// the list of the very hot keys' parts for the update's split role (SplitOut, dfh_kernels.hip): handed to the launches of a
+// the list of the very hot keys' parts for the update's split role (SplitOut, dfh_lookup.hip): handed to the launches of a
 // TRAINING step that see the minibatch's keys with their segments; u_base = rank of the first key such a launch sees
 inline bool split_listed(const dfh_ctx* c, const dfh_batch* b, int is_train) { return b && is_train && c->upd_kernel && c->upd_split; }
 // (every launch that takes it appends to the batch object's current counter and zeroes the other one; the step's main_end then

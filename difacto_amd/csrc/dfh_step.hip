@@ -1,5 +1,5 @@
-// dfh_step.hip — a training step on the main stream: the views of table and minibatch its launches take, forward, AUC,
-// update / backward, the two stages dfh_sgd_step and the sharded schedules (dfh_shard.hip) are built from, and the step calls.
+// dfh_step.hip — a training step on the main stream: the views of table and minibatch its launches take, forward,
+// update / backward (the AUC's own launches: dfh_auc_api.hip), the two stages dfh_sgd_step and the sharded schedules (dfh_shard.hip) are built from, and the step calls.
 namespace {
 RowSrc table_src(const dfh_table* t, const uint32_t* urow) {
   RowSrc s;
@@ -102,40 +102,6 @@ int launch_forward(dfh_batch* b, const RowSrc& src, int k, int kp, const uint2* 
 #undef DFH_FWD
   });
   if (rc) return rc;
-  DFH_HIP(hipGetLastError());
-  return DFH_OK;
-}
-
-// an AUC whose units have run (inside an update launch) but whose slots have not been added up yet
-AucFin auc_pending(dfh_batch* b) { return AucFin{b->d_auc_part, b->auc_pending_n, b->d_prog + PROG_AUC * PROG_SLOTS}; }
-int auc_flush_pending(dfh_batch* b) {
-  if (!b->auc_pending_n) return DFH_OK;
-  hipLaunchKernelGGL(k_auc_finalize, dim3(1), dim3(256), 0, b->ctx->stream, auc_pending(b));
-  b->auc_pending_n = 0;
-  DFH_HIP(hipGetLastError());
-  return DFH_OK;
-}
-
-// BinClassMetric::AUC of the batch's predictions, accumulated into the progress block
-int launch_auc(dfh_batch* b) {
-  hipStream_t s = b->ctx->stream;
-  const uint32_t n = (uint32_t)b->nrows;
-  if (n <= AUC_PAIRS_MAX_N) {
-    // minibatch-sized: pair counting (auc_pairs_block units), then one block adds the units' slots up
-    int rc = auc_flush_pending(b);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_auc_pairs, dim3(auc_units(n)), dim3(256), 0, s, b->d_pred, b->d_label, n, b->d_auc_part);
-    hipLaunchKernelGGL(k_auc_finalize, dim3(1), dim3(256), 0, s, AucFin{b->d_auc_part, n, b->d_prog + PROG_AUC * PROG_SLOTS});
-    DFH_HIP(hipGetLastError());
-    return DFH_OK;
-  }
-  hipLaunchKernelGGL(k_auc_keys, dim3(grid_for_threads(n, b->ctx)), dim3(256), 0, s, b->d_pred, b->d_label, n, b->d_auc_keys,
-                     b->d_auc_lab);
-  size_t tb = b->temp_bytes;
-  // NB: d_temp is shared with the localizer's library-sort path, which only runs on the prep stream of
-  // ANOTHER batch object; within one batch the step follows its own preparation
-  DFH_HIP(rocprim::radix_sort_pairs(b->d_temp, tb, b->d_auc_keys, b->d_auc_skeys, b->d_auc_lab, b->d_auc_slab, (size_t)n, 0, 32, s));
-  hipLaunchKernelGGL(k_auc_area, dim3(1), dim3(1024), 0, s, b->d_auc_slab, n, b->d_prog + PROG_AUC * PROG_SLOTS);
   DFH_HIP(hipGetLastError());
   return DFH_OK;
 }
@@ -501,49 +467,6 @@ int dfh_batch_backward(dfh_batch* b, int V_dim, const float* d_rows, float* d_gr
   int rc = launch_backward<false>(b, packed_src(d_rows, V_dim), dummy, d_grads, dfh_row_stride(V_dim), V_dim, kp, nullptr);
   if (rc) return rc;
   return main_end(b);
-}
-
-int dfh_auc_times_n(dfh_ctx* c, const float* label, const float* pred, size_t n, float* auc_n) {
-  DFH_ARG(c && auc_n, "NULL argument");
-  *auc_n = 1.0f;
-  if (n == 0) return DFH_OK;
-  DFH_ARG(label && pred && n < 0xFFFFFFF0ULL, "dfh_auc_times_n: bad argument");
-  DFH_HIP(hipSetDevice(c->device));
-  const bool pairs = n <= AUC_PAIRS_MAX_N;
-  size_t tb = 0;
-  if (!pairs)
-    rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 32,
-                              c->stream);
-  int rc = ensure_scratch(c, 2 * padded<float>(n) + (pairs ? 0 : 4 * padded<uint32_t>(n)) + tb + padded<uint32_t>(AUC_PART_WORDS) + 2048);
-  if (rc) return rc;
-  Carver cv(c->scratch);
-  float* d_l = cv.take<float>(n);
-  float* d_p = cv.take<float>(n);
-  double* d_o = cv.take<double>(1);
-  uint32_t* d_part = cv.take<uint32_t>(AUC_PART_WORDS);
-  hipStream_t s = c->stream;
-  DFH_HIP(hipMemcpyAsync(d_l, label, n * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipMemcpyAsync(d_p, pred, n * 4, hipMemcpyHostToDevice, s));
-  DFH_HIP(hipMemsetAsync(d_o, 0, sizeof(double), s));
-  if (pairs) {
-    hipLaunchKernelGGL(k_auc_pairs, dim3(auc_units((uint32_t)n)), dim3(256), 0, s, d_p, d_l, (uint32_t)n, d_part);
-    hipLaunchKernelGGL(k_auc_finalize, dim3(1), dim3(256), 0, s, AucFin{d_part, (uint32_t)n, d_o});
-  } else {
-    uint32_t* k0 = cv.take<uint32_t>(n);
-    uint32_t* k1 = cv.take<uint32_t>(n);
-    uint32_t* l0 = cv.take<uint32_t>(n);
-    uint32_t* l1 = cv.take<uint32_t>(n);
-    char* temp = cv.take<char>(tb + 16);
-    hipLaunchKernelGGL(k_auc_keys, dim3(grid_for_threads(n, c)), dim3(256), 0, s, d_p, d_l, (uint32_t)n, k0, l0);
-    DFH_HIP(rocprim::radix_sort_pairs(temp, tb, k0, k1, l0, l1, n, 0, 32, s));
-    hipLaunchKernelGGL(k_auc_area, dim3(1), dim3(1024), 0, s, l1, (uint32_t)n, d_o);
-  }
-  DFH_HIP(hipGetLastError());
-  double o = 0;
-  DFH_HIP(hipMemcpyAsync(&o, d_o, sizeof(double), hipMemcpyDeviceToHost, s));
-  DFH_HIP(hipStreamSynchronize(s));
-  *auc_n = (float)o;
-  return DFH_OK;
 }
 
 #ifdef DFH_BWD_TRACE

@@ -22,7 +22,7 @@
 // long-segment roles are chains of L2 round trips: depth, not occupancy, shortens them).  Every key is
 // updated by exactly one role, by one lane group: deterministic, no float atomics, nothing is
 // communicated between blocks.  V rows are read speculatively (a row without V holds zeros).
-// The update arithmetic is ftrl_update_w / adagrad_update_v of dfh_kernels.hip (operation for
+// The update arithmetic is ftrl_update_w / adagrad_update_v of dfh_updater.h (operation for
 // operation the reference's); the kernel is pinned to 8 waves per SIMD (64 registers) like
 // k_backward_all, for the same reason (co-residency with the preparation stream).
 #ifndef DFH_UPDATE_HIP_

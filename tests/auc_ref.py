@@ -1,5 +1,5 @@
 """The integer oracle of the minibatch AUC (k_auc_pairs / k_auc_finalize, the AUC role of k_update_fused, and the radix form
-k_auc_keys / k_auc_area in csrc/dfh_kernels.hip), the condition under which ONE miscounted pair changes the float the device
+k_auc_keys / k_auc_area in csrc/dfh_auc.hip), the condition under which ONE miscounted pair changes the float the device
 returns, and the designed cases tests/test_auc_exact.py runs.
 
 The device counts area = the (positive j, negative i) pairs with (pred_j, j) before (pred_i, i) — -0 equals +0, ties by

@@ -1,4 +1,4 @@
-"""Designed keys for the open-addressing key index (dfh_kernels.hip find_or_insert / find_or_insert_block / find_only /
+"""Designed keys for the open-addressing key index (dfh_index.hip find_or_insert / find_or_insert_block / find_only /
 k_rehash).  No GPU, no native library: plain Python integers and numpy.
 
 The index hashes a key with splitmix64 (dfh_internal.h) and masks the hash with H - 1.  splitmix64 is a bijection of the

@@ -420,7 +420,7 @@ def _resync_oracle(so, exp, keys):
 
 def _check_step_state(so, exp1, keys, kw, V_dim, gtol_w, gtol_V, what):
     """the model after ONE step from identical state: the device's entries of the step's keys against the oracle's.  The update
-    arithmetic is the reference's operation for operation (dfh_kernels.hip ftrl_update_w / adagrad_update_v), so the two sides
+    arithmetic is the reference's operation for operation (dfh_updater.h ftrl_update_w / adagrad_update_v), so the two sides
     can differ only by what the gradient tolerance gtol (rtol 1e-5 |g| + the summation floor of oracle/tolerance.py + the
     logit tolerance carried through the slope) lets through, times the sensitivity of each field to the gradient
     (sgd_updater.cc:104-138):  d sqrt_g <= dg;  dz <= (1 + |w| / lr) dg;  dw <= (lr + |w| + |w'|) / (lr_beta + sqrt_g') dg;

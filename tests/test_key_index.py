@@ -1,4 +1,4 @@
-"""The open-addressing key index (dfh_kernels.hip: find_or_insert, find_or_insert_block, find_only, k_rehash) on DESIGNED
+"""The open-addressing key index (dfh_index.hip: find_or_insert, find_or_insert_block, find_only, k_rehash) on DESIGNED
 probe chains.  Random 64-bit keys spread evenly over an index that is at most half full: chains of one to three slots, never
 past the last slot.  Here the keys are built through the exact inverse of splitmix64 (keyindex_testlib.py), so that a chain
 runs past slot H - 1 and goes on at slot 0, a whole launch contends for one chain, two clusters merge, a growth rebuilds a

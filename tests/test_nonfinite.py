@@ -14,7 +14,7 @@ CPU: the C restatement against the reference itself (oracle/_ref) on such inputs
 restatement: the same finite / non-finite pattern, and rtol 1e-5 (+ floor) where finite.  The device does not
 distinguish +-Inf from NaN in a sum that is non-finite on both sides (padding lanes multiply by 0), and it has one
 documented deviation: four consecutive V coordinates (one lane's 16 B slice) that are all exactly 0.0 inside an
-ALLOCATED row are treated like a key without V (dfh_kernels.hip k_forward) — NaN in the reference,
+ALLOCATED row are treated like a key without V (dfh_forward.hip k_forward) — NaN in the reference,
 neutral here.  Observable only when the WHOLE allocated row is zero (any nonzero slice meets the same value and makes
 Inf - Inf = NaN on both sides): constructed in test_allocated_all_zero_V_row_times_nonfinite_value, which asserts the
 documented outcome on both sides.

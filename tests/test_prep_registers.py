@@ -23,7 +23,7 @@ BUDGET = 32
 # the preparation stream's kernels as the library instantiates them (dfh_pending.hip: launch_loc_stage; dfh_localize_api.hip: the probe), C3's size class
 TU = r"""
 #include <hip/hip_runtime.h>
-#include "dfh_kernels.hip"
+#include "dfh_lookup.hip"
 #include "dfh_localize.hip"
 namespace dfh {
 template __global__ void k_loc_count<LOC_MAX_BUCKETS>(LocView);

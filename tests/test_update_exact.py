@@ -1,6 +1,6 @@
 """The update arithmetic, bit for bit.
 
-dfh_kernels.hip claims that ftrl_update_w / adagrad_update_v are the reference's SGDUpdater operation for operation, so that
+dfh_updater.h claims that ftrl_update_w / adagrad_update_v are the reference's SGDUpdater operation for operation, so that
 "given the same gradient the new V and accumulator are the reference's, bit for bit"; dfh_update.hip adds that every key is
 updated by exactly one role and that the result is deterministic.  Two families of tests hold the project to it, with no
 tolerance, no skipped key and no mask:
