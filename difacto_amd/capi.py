@@ -50,13 +50,13 @@ SYMBOLS = [
     "dfh_predtext_create", "dfh_predtext_destroy", "dfh_predtext_reset", "dfh_predtext_append_batch", "dfh_predtext_append_host",
     "dfh_predtext_count", "dfh_predtext_values", "dfh_predtext_format", "dfh_predtext_read", "dfh_predtext_tile",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
-    "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_tile",
+    "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_ids", "dfh_dump_tile", "dfh_dump_pairs",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
-K_COUNT = 8
+K_COUNT = 11
 K_LOCALIZE, K_LOOKUP, K_FORWARD, K_BACKWARD, K_PULL, K_PUSH, K_MISC, K_AUC = range(8)
 
 
@@ -235,7 +235,9 @@ def lib():
     L.dfh_dump_format.argtypes = [vp, C.c_uint64, sz, PP(sz), PP(C.c_uint64)]
     L.dfh_dump_read.argtypes = [vp, vp]
     L.dfh_dump_entries.argtypes = [vp, C.c_uint64, sz, vp, vp, vp, vp]
+    L.dfh_dump_ids.argtypes = [vp, C.c_uint64, sz, vp, vp]
     L.dfh_dump_tile.argtypes = [vp]
+    L.dfh_dump_pairs.argtypes = [vp, C.c_uint64, sz, i32, i32, vp, vp, vp, PP(C.c_uint64)]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -930,6 +932,7 @@ class PredText:
 
 
 DUMP_IDS_FEATURE, DUMP_IDS_KEY = 0, 1
+PAIRS_ABS, PAIRS_POS = 0, 1
 
 
 class ModelDump:
@@ -977,6 +980,25 @@ class ModelDump:
         V = np.zeros(max(count * k, 1), np.float32)
         _ck(lib().dfh_dump_entries(self.h, first, count, _p(ids), _p(w), _p(has), _p(V)))
         return dict(ids=ids[:count], w=w[:count], has_V=has[:count], V=V[:count * k].reshape(count, k) if k else None)
+
+    def ids(self, first=0, count=None):
+        """-> (ids, has_V) of the same entries, without their rows (dfh_dump_ids)"""
+        count = self.n - first if count is None else count
+        ids = np.zeros(max(count, 1), np.uint64)
+        has = np.zeros(max(count, 1), np.int32)
+        _ck(lib().dfh_dump_ids(self.h, first, count, _p(ids), _p(has)))
+        return ids[:count], has[:count]
+
+    def pairs(self, first=0, count=None, topk=10, by=PAIRS_ABS):
+        """-> dict(ids [count x topk], scores [count x topk], n [count], nonfinite): each entry's topk interaction partners among
+        the entries with V, by |s| (PAIRS_ABS) or s (PAIRS_POS), s(i, j) = V_i . V_j (dfh_dump_pairs); row e is valid up to n[e]"""
+        count = self.n - first if count is None else count
+        ids = np.zeros(max(count * topk, 1), np.uint64)
+        scores = np.zeros(max(count * topk, 1), np.float32)
+        n = np.zeros(max(count, 1), np.uint32)
+        nf = C.c_uint64(0)
+        _ck(lib().dfh_dump_pairs(self.h, first, count, topk, by, _p(ids), _p(scores), _p(n), C.byref(nf)))
+        return dict(ids=ids[:count * topk].reshape(count, topk), scores=scores[:count * topk].reshape(count, topk), n=n[:count], nonfinite=nf.value)
 
     def close(self):
         if self.h:

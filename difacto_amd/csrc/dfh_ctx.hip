@@ -21,6 +21,7 @@ const IntOption kIntOptions[] = {
     {"owner_per_key", &dfh_ctx::owner_per_key, 0, 1, "owner_per_key must be 0 (count push, Pull, gradient push per received entry) or 1 (per distinct key)"},
     {"upd_split", &dfh_ctx::upd_split, 0, 1, "upd_split must be 0 (one block per hot key, whatever its length) or 1 (a block per part of 1 024 occurrences)"},
     {"upd_interleave", &dfh_ctx::upd_interleave, 0, 64, "upd_interleave must be in [0, 64]"},
+    {"pairs_split", &dfh_ctx::pairs_split, 0, 64, "pairs_split must be in [0, 64] (0: chosen from the grid)"},
     {"event_flags", &dfh_ctx::event_flags, 0, 1, "event_flags must be 0 (default events) or 1 (no system-scope fence); set before batches are created"},
 };
 }  // namespace
@@ -269,7 +270,7 @@ int dfh_ctx_get_timing(dfh_ctx* c, int reset, double* total_ms, uint64_t* calls)
 }
 
 const char* dfh_kernel_name(int id) {
-  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc"};
+  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc", "pairs_pack", "pairs_sweep", "pairs_merge"};
   return (id >= 0 && id < DFH_K_COUNT) ? names[id] : "?";
 }
 

@@ -47,9 +47,24 @@ struct dfh_dump {
   char* d_ent = nullptr;          // dfh_dump_entries' arrays
   size_t ent_cap = 0;
   bool formatted = false;
+  // dfh_dump_pairs' (dfh_pairs.hip): built by its first call, kept
+  struct Pairs {
+    bool built = false;
+    uint32_t kd = 0;              // floats per packed row
+    uint64_t rows = 0;            // packed rows, the padding included
+    float* P = nullptr;           // [rows][kd] the has-V entries' V, in position order
+    uint32_t* epos = nullptr;     // [n + 1] entry -> position (the entries with V before it)
+    uint32_t* map = nullptr;      // [n_with_V] position -> entry
+    unsigned long long* part = nullptr;   // the splits' partial lists of the last call
+    size_t part_cap = 0;
+    char* out = nullptr;          // a call's lists before their download
+    size_t out_cap = 0;
+    unsigned long long* d_nf = nullptr;
+  } pr;
 };
 
 namespace {
+void pairs_release(dfh_dump* p);   // dfh_pairs.hip
 constexpr uint32_t DT_IMG = 32768, DT_TILE_MAX = 1024;   // the LDS image of a tile's text (and 16 B for its shift); entries per tile at most
 
 // a lane per slot (the index has a multiple of 64 slots: a wave's lanes are in the loop together)
@@ -235,6 +250,7 @@ int dfh_dump_close(dfh_dump* p) {
   if (p->d_tmp) (void)hipFree(p->d_tmp);
   if (p->d_cnt) (void)hipFree(p->d_cnt);
   if (p->d_ent) (void)hipFree(p->d_ent);
+  pairs_release(p);
   if (p->h_head) (void)hipHostFree(p->h_head);
   if (p->h_text) (void)hipHostFree(p->h_text);
   delete p;
@@ -426,6 +442,21 @@ int dfh_dump_entries(dfh_dump* p, uint64_t first, size_t count, uint64_t* ids, f
   DFH_HIP(hipMemcpyAsync(has_V, o_has, count * sizeof(int), hipMemcpyDeviceToHost, s));
   if (k) DFH_HIP(hipMemcpyAsync(V, o_V, count * k * sizeof(float), hipMemcpyDeviceToHost, s));
   DFH_HIP(hipStreamSynchronize(s));
+  return DFH_OK;
+}
+
+int dfh_dump_ids(dfh_dump* p, uint64_t first, size_t count, uint64_t* ids, int* has_V) {
+  DFH_ARG(p, "dfh_dump_ids: NULL argument");
+  DFH_ARG(first <= p->n && count <= p->n - first, "dfh_dump_ids: first + count exceeds the dump's entries");
+  if (count == 0) return DFH_OK;
+  DFH_ARG(ids && has_V, "dfh_dump_ids: NULL argument");
+  hipStream_t s = p->ctx->stream;
+  DFH_HIP(hipSetDevice(p->ctx->device));
+  static_assert(sizeof(int) == sizeof(uint32_t), "the row words land in has_V");
+  DFH_HIP(hipMemcpyAsync(ids, p->d_id + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  DFH_HIP(hipMemcpyAsync(has_V, p->d_row + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  DFH_HIP(hipStreamSynchronize(s));
+  for (size_t i = 0; i < count; ++i) has_V[i] = ((uint32_t)has_V[i] & kHasV) ? 1 : 0;
   return DFH_OK;
 }
 

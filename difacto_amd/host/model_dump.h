@@ -7,6 +7,12 @@
  * format (non-finite, subnormal, |v| < 2^-64, |v| >= 2^32) is written by the host's fprintf from dfh_dump_entries, so the file
  * is exact on any model; dump_write = host takes that path for every unit (the yardstick, and the way out).  The host holds
  * two units at a time: one on its way to the file on a thread of its own while the next is formatted.
+ *
+ * pairs_out = <file> writes a second file in the same run, unit by unit in the same loop: one line
+ * "<id>\t<id_1>:<s_1>\t ... \t<id_m>:<s_m>\n" per entry that has V, its pairs_topk strongest interaction partners among the
+ * entries with V — s(i, j) = sum_d V_i[d] V_j[d], the model's weight on x_i x_j, by |s| (pairs_by = abs) or s (pos), ties by
+ * ascending id; ids under dump_ids' rule, scores as %.9g.  The scores and the selection are the device's (dfh_dump_pairs,
+ * csrc/dfh_pairs.hip); the host formats the at most pairs_topk values of an entry.  Without pairs_out nothing changes.
  */
 #ifndef DIFACTO_HOST_MODEL_DUMP_H_
 #define DIFACTO_HOST_MODEL_DUMP_H_
@@ -34,12 +40,21 @@ struct ModelDumpParam : public dmlc::Parameter<ModelDumpParam> {
   std::string dump_write;
   /** \brief entries per unit: one format call, one download, one write */
   int dump_unit_rows;
+  /** \brief empty (default): off; else the text file of every has-V entry's top interaction partners */
+  std::string pairs_out;
+  /** \brief partners per entry, 1 .. 32 */
+  int pairs_topk;
+  /** \brief abs (default): the largest |s|; pos: the largest s */
+  std::string pairs_by;
   DMLC_DECLARE_PARAMETER(ModelDumpParam) {
     DMLC_DECLARE_FIELD(model_in).set_default("");
     DMLC_DECLARE_FIELD(dump_out).set_default("");
     DMLC_DECLARE_FIELD(dump_ids).set_default("feature");
     DMLC_DECLARE_FIELD(dump_write).set_default("device");
     DMLC_DECLARE_FIELD(dump_unit_rows).set_default(65536);
+    DMLC_DECLARE_FIELD(pairs_out).set_default("");
+    DMLC_DECLARE_FIELD(pairs_topk).set_default(10);
+    DMLC_DECLARE_FIELD(pairs_by).set_default("abs");
   }
 };
 
@@ -57,6 +72,9 @@ class ModelDump {
     CHECK(param_.dump_write == "device" || param_.dump_write == "host")
         << "dump_write=" << param_.dump_write << " is not one of device (the default) and host";
     CHECK_GE(param_.dump_unit_rows, 1) << "dump_unit_rows=" << param_.dump_unit_rows << ": a unit has 1 entry or more";
+    CHECK(param_.pairs_topk >= 1 && param_.pairs_topk <= 32) << "pairs_topk=" << param_.pairs_topk << ": a list has 1 to 32 partners";
+    CHECK(param_.pairs_by == "abs" || param_.pairs_by == "pos")
+        << "pairs_by=" << param_.pairs_by << " is not one of abs (the default: the largest |s|) and pos (the largest s)";
     files_ = ModelInFiles(param_.model_in);   // fatal with the path when nothing is readable
     for (size_t i = 0; i < files_.size(); ++i) {
       int k = 0;
@@ -92,6 +110,12 @@ class ModelDump {
     CHECK(f != nullptr) << "cannot open " << tmp << " for writing";
     std::vector<char> iobuf(1 << 22);
     setvbuf(f, iobuf.data(), _IOFBF, iobuf.size());
+    const bool pairs = !param_.pairs_out.empty();
+    const std::string ptmp = param_.pairs_out + ".tmp";
+    FILE* pf = pairs ? fopen(ptmp.c_str(), "wb") : nullptr;
+    CHECK(!pairs || pf != nullptr) << "cannot open " << ptmp << " for writing";
+    const int K = param_.pairs_topk;
+    uint64_t nonfinite = 0;
     const size_t unit = static_cast<size_t>(param_.dump_unit_rows);
     std::future<void> write;   // unit u - 1 on its way to the file, out of the other buffer
     int cur = 0;
@@ -115,18 +139,42 @@ class ModelDump {
         u->has_V.resize(u->count);
         u->V.resize(std::max<size_t>(u->count * static_cast<size_t>(V_dim_), 1));
         DFH_CALL(dfh_dump_entries(d, at, u->count, u->ids.data(), u->w.data(), u->has_V.data(), u->V.data()));
+      } else if (pairs) {   // the pairs' lines need the unit's ids and has-V flags, and no more
+        u->ids.resize(u->count);
+        u->has_V.resize(u->count);
+        DFH_CALL(dfh_dump_ids(d, at, u->count, u->ids.data(), u->has_V.data()));
+      }
+      if (pairs) {
+        u->p_ids.resize(u->count * static_cast<size_t>(K));
+        u->p_scores.resize(u->count * static_cast<size_t>(K));
+        u->p_n.resize(u->count);
+        uint64_t nf = 0;
+        DFH_CALL(dfh_dump_pairs(d, at, u->count, K, param_.pairs_by == "pos" ? DFH_PAIRS_POS : DFH_PAIRS_ABS, u->p_ids.data(),
+                                u->p_scores.data(), u->p_n.data(), &nf));
+        nonfinite += nf;
       }
       (u->host ? host_units_ : dev_units_) += 1;
       (u->host ? host_entries_ : dev_entries_) += u->count;
       if (write.valid()) write.get();
       const int k = V_dim_;
       const std::string* name = &tmp;
-      write = std::async(std::launch::async, [u, f, k, name] { WriteUnit(*u, f, k, *name); });
+      const std::string* pname = &ptmp;
+      write = std::async(std::launch::async, [u, f, k, name, pf, K, pname] {
+        WriteUnit(*u, f, k, *name);
+        if (pf) WritePairs(*u, pf, K, *pname);
+      });
     }
     if (write.valid()) write.get();
     const long bytes = ftell(f);
     CHECK_EQ(fclose(f), 0) << "closing " << tmp << " failed";
     CHECK_EQ(rename(tmp.c_str(), param_.dump_out.c_str()), 0) << "cannot move " << tmp << " to " << param_.dump_out;
+    if (pairs) {
+      CHECK_EQ(fclose(pf), 0) << "closing " << ptmp << " failed";
+      CHECK_EQ(rename(ptmp.c_str(), param_.pairs_out.c_str()), 0) << "cannot move " << ptmp << " to " << param_.pairs_out;
+      if (nonfinite)
+        LOG(WARNING) << nonfinite << " pairs have a score that is not finite: they are in no list of " << param_.pairs_out;
+      LOG(INFO) << "pairs_out: the " << K << " partners by " << param_.pairs_by << " of " << n_with_V << " entries with V to " << param_.pairs_out;
+    }
     DFH_CALL(dfh_dump_close(d));
     DFH_CALL(dfh_table_destroy(t));
     const double t2 = Now();
@@ -145,8 +193,23 @@ class ModelDump {
     std::vector<uint64_t> ids;    // or the entries, for the host's fprintf
     std::vector<float> w, V;
     std::vector<int> has_V;
+    std::vector<uint64_t> p_ids;  // pairs_out: dfh_dump_pairs' arrays
+    std::vector<float> p_scores;
+    std::vector<uint32_t> p_n;
   };
   static double Now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  static void WritePairs(const Unit& u, FILE* f, int K, const std::string& name) {
+    bool ok = true;
+    for (size_t i = 0; i < u.count; ++i) {
+      if (!u.has_V[i]) continue;
+      ok = ok && fprintf(f, "%llu", static_cast<unsigned long long>(u.ids[i])) > 0;
+      for (uint32_t j = 0; j < u.p_n[i]; ++j)
+        ok = ok && fprintf(f, "\t%llu:%.9g", static_cast<unsigned long long>(u.p_ids[i * static_cast<size_t>(K) + j]),
+                           u.p_scores[i * static_cast<size_t>(K) + j]) > 0;
+      ok = ok && fputc('\n', f) != EOF;
+    }
+    CHECK(ok) << "cannot write " << name;
+  }
   static void WriteUnit(const Unit& u, FILE* f, int k, const std::string& name) {
     if (!u.host) {
       CHECK_EQ(fwrite(u.text.data(), 1, u.text.size(), f), u.text.size()) << "cannot write " << name;

@@ -103,13 +103,17 @@ int dfh_ctx_set_pipeline(dfh_ctx* ctx, int enable);
  *                                       parts of 1 024, a block per part (default 1; 0 = one block walks the whole segment)
  *   "owner_per_key"     0 | 1           dfh_shard_step's owner side per distinct key (dfh_shard_count_pull_multi +
  *                                       dfh_shard_push_grad_listed) instead of per received entry; same results, not faster
- *                                       (default 0; measurement switch) */
+ *                                       (default 0; measurement switch)
+ *   "pairs_split"       0 .. 64         dfh_dump_pairs: the candidate splits of the sweep's grid; 0 (default) = chosen so that a
+ *                                       small model still fills the chip.  No bit of the output depends on it (tests, measuring) */
 int dfh_ctx_set_option(dfh_ctx* ctx, const char* name, int value);
 
 /* optional per-kernel timing with HIP events recorded on the context's stream
  * (what bench.py's roofline block reads); ids index total_ms[]/calls[] */
 enum {
-  DFH_K_LOCALIZE = 0, DFH_K_LOOKUP, DFH_K_FORWARD, DFH_K_BACKWARD, DFH_K_PULL, DFH_K_PUSH, DFH_K_MISC, DFH_K_AUC, DFH_K_COUNT
+  DFH_K_LOCALIZE = 0, DFH_K_LOOKUP, DFH_K_FORWARD, DFH_K_BACKWARD, DFH_K_PULL, DFH_K_PUSH, DFH_K_MISC, DFH_K_AUC,
+  DFH_K_PAIRS_PACK, DFH_K_PAIRS_SWEEP, DFH_K_PAIRS_MERGE,   /* dfh_dump_pairs' three stages */
+  DFH_K_COUNT
 };
 int dfh_ctx_set_timing(dfh_ctx* ctx, int enable);
 /* time only the kernels whose bit (1u << DFH_K_*) is set.  Single-launch kernels (forward,
@@ -915,10 +919,29 @@ int dfh_dump_read(dfh_dump* d, char* dst);
 /* the same entries as arrays: ids [count] as printed, w [count], has_V [count], V [count x V_dim] (zeros where !has_V; may be
  * NULL with V_dim = 0): for the host's formatting of a unit and for tests */
 int dfh_dump_entries(dfh_dump* d, uint64_t first, size_t count, uint64_t* ids, float* w, int* has_V, float* V);
+/* the ids and has_V of dfh_dump_entries alone: 12 bytes per entry over the bus and no launch, for a caller that has the unit's
+ * text from the device and needs only these (pairs_out's lines) */
+int dfh_dump_ids(dfh_dump* d, uint64_t first, size_t count, uint64_t* ids, int* has_V);
 /* the entries a block of the format kernels takes, by the table's V_dim so that a tile's longest text fits the LDS image (for
  * tests; tiles count from the unit's first entry).  0: V_dim is above 2045, dfh_dump_format refuses (DFH_ERR_ARG) and the
  * entries are formatted on the host */
 int dfh_dump_tile(dfh_dump* d);
+/* Each entry's strongest FM interaction partners (csrc/dfh_pairs.hip, whose header comment has the full definition).  The
+ * CANDIDATES are the dump's entries with V; s(i, j) = sum_d V_i[d] V_j[d] in fp32 is the model's weight on x_i x_j.  Query entry
+ * e of [first, first + count) gets the topk (1 .. 32) candidates j != e with the largest |s| (by = DFH_PAIRS_ABS) or s
+ * (DFH_PAIRS_POS); key descending, equal keys by ascending printed id; fewer when there are fewer candidates, none when e has
+ * no V.  Row e - first of partner_ids / scores [count x topk] holds npartners[e - first] pairs (printed ids, s itself) and
+ * zeros behind them.  Pairs whose score is not finite enter no list; *nonfinite counts the (query, candidate) pairs of this
+ * call's queries that were left out for it.  The output is a function of the model alone: "pairs_split" changes no bit.
+ *   - the first call packs the candidates' V rows and keeps them with the dfh_dump:
+ *     4 * roundup(V_dim, 8) * (roundup(n_with_V, 128) + 128) + 4 * n_with_V + 4 * (n_entries + 1) bytes of device memory
+ *   - a call adds count * (12 topk + 4) bytes and 1024 * topk bytes per block of the sweep, kept for the next call
+ *   - a model without V, or V_dim = 0: no launch, every list is empty
+ * Errors: DFH_ERR_ARG for NULL arguments, first + count beyond the entries, another topk or by; DFH_ERR_CAPACITY for a failed
+ * allocation, with the bytes needed in the message. */
+enum { DFH_PAIRS_ABS = 0, DFH_PAIRS_POS = 1 };
+int dfh_dump_pairs(dfh_dump* d, uint64_t first, size_t count, int topk, int by, uint64_t* partner_ids /*[count*topk]*/,
+                   float* scores /*[count*topk]*/, uint32_t* npartners /*[count]*/, uint64_t* nonfinite);
 
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
