@@ -51,12 +51,14 @@ SYMBOLS = [
     "dfh_predtext_count", "dfh_predtext_values", "dfh_predtext_format", "dfh_predtext_read", "dfh_predtext_tile",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
     "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_ids", "dfh_dump_tile", "dfh_dump_pairs",
+    "dfh_explain_create", "dfh_explain_destroy", "dfh_explain_reset", "dfh_explain_append_batch", "dfh_explain_count", "dfh_explain_read",
+    "dfh_explain_read_positions",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
-K_COUNT = 11
+K_COUNT = 12
 K_LOCALIZE, K_LOOKUP, K_FORWARD, K_BACKWARD, K_PULL, K_PUSH, K_MISC, K_AUC = range(8)
 
 
@@ -238,6 +240,13 @@ def lib():
     L.dfh_dump_ids.argtypes = [vp, C.c_uint64, sz, vp, vp]
     L.dfh_dump_tile.argtypes = [vp]
     L.dfh_dump_pairs.argtypes = [vp, C.c_uint64, sz, i32, i32, vp, vp, vp, PP(C.c_uint64)]
+    L.dfh_explain_create.argtypes = [vp, i32, i32, sz, PP(vp)]
+    L.dfh_explain_destroy.argtypes = [vp]
+    L.dfh_explain_reset.argtypes = [vp]
+    L.dfh_explain_append_batch.argtypes = [vp, vp, vp]
+    L.dfh_explain_count.argtypes = [vp, PP(C.c_uint64)]
+    L.dfh_explain_read.argtypes = [vp, vp, vp, vp, vp, vp, PP(C.c_uint64)]
+    L.dfh_explain_read_positions.argtypes = [vp, vp, vp]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -1003,6 +1012,50 @@ class ModelDump:
     def close(self):
         if self.h:
             lib().dfh_dump_close(self.h)
+            self.h = None
+
+
+class Explain:
+    """each appended row's topk strongest FM interaction pairs c_ij = x_i x_j <V_i, V_j> over its positions with V, and the sum
+    of all of them (dfh_explain); by |c| (PAIRS_ABS) or c (PAIRS_POS)"""
+
+    def __init__(self, ctx, topk=10, by=PAIRS_ABS, capacity_hint=0):
+        self.ctx = ctx
+        self.topk = topk
+        self.h = C.c_void_p()
+        _ck(lib().dfh_explain_create(ctx.h, topk, by, capacity_hint, C.byref(self.h)))
+
+    def reset(self):
+        _ck(lib().dfh_explain_reset(self.h))
+
+    def append_batch(self, batch, table):
+        """the batch's rows, queued behind its last step (sgd_step on `table`); does not wait"""
+        _ck(lib().dfh_explain_append_batch(self.h, batch.h, table.h))
+
+    def count(self):
+        n = C.c_uint64(0)
+        _ck(lib().dfh_explain_count(self.h, C.byref(n)))
+        return n.value
+
+    def read(self):
+        """-> dict(n [rows], ids_i, ids_j, c, pos_i, pos_j [rows x topk], inter [rows], nonfinite) of everything appended since
+        the last reset, in append order (waits; nothing is consumed); row r is valid up to n[r]"""
+        rows, K = self.count(), self.topk
+        n = np.zeros(max(rows, 1), np.uint32)
+        inter = np.zeros(max(rows, 1), np.float32)
+        ids_i, ids_j = np.zeros(max(rows * K, 1), np.uint64), np.zeros(max(rows * K, 1), np.uint64)
+        pos_i, pos_j = np.zeros(max(rows * K, 1), np.uint32), np.zeros(max(rows * K, 1), np.uint32)
+        c = np.zeros(max(rows * K, 1), np.float32)
+        nf = C.c_uint64(0)
+        _ck(lib().dfh_explain_read(self.h, _p(n), _p(ids_i), _p(ids_j), _p(c), _p(inter), C.byref(nf)))
+        _ck(lib().dfh_explain_read_positions(self.h, _p(pos_i), _p(pos_j)))
+        sq = lambda a: a[:rows * K].reshape(rows, K)
+        return dict(n=n[:rows], ids_i=sq(ids_i), ids_j=sq(ids_j), c=sq(c), pos_i=sq(pos_i), pos_j=sq(pos_j), inter=inter[:rows],
+                    nonfinite=nf.value)
+
+    def close(self):
+        if self.h:
+            lib().dfh_explain_destroy(self.h)
             self.h = None
 
 

@@ -352,6 +352,7 @@ int dfh_batch_load_localized_host(dfh_batch* b, size_t nrows, const size_t* offs
   if (rc) return rc;
   hipStream_t s = prep_of(b);
   b->looked_up = nullptr;
+  b->stepped = nullptr;
   uint32_t U32 = (uint32_t)U;
   DFH_HIP(hipMemcpyAsync(b->d_offset, off32.data(), (nrows + 1) * 4, hipMemcpyHostToDevice, s));
   if (nnz) {

@@ -270,7 +270,7 @@ int dfh_ctx_get_timing(dfh_ctx* c, int reset, double* total_ms, uint64_t* calls)
 }
 
 const char* dfh_kernel_name(int id) {
-  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc", "pairs_pack", "pairs_sweep", "pairs_merge"};
+  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc", "pairs_pack", "pairs_sweep", "pairs_merge", "explain"};
   return (id >= 0 && id < DFH_K_COUNT) ? names[id] : "?";
 }
 

@@ -92,6 +92,7 @@ void batch_loaded(dfh_batch* b, size_t nrows, size_t nnz, bool has_value) {
   b->has_cnt = false;
   b->localized = false;
   b->looked_up = nullptr;
+  b->stepped = nullptr;
 }
 
 __global__ void k_fill_f32(float* __restrict__ p, size_t n, float v) {

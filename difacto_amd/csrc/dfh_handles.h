@@ -205,6 +205,7 @@ struct dfh_batch {
   bool force_radix = false;        // tests: take the library-sort path of dfh_localize
   bool force_sort_fallback = false;  // tests: k_ss_sort's global-memory path for every bucket
   dfh_table* looked_up = nullptr;  // dfh_batch_lookup already resolved urow against this table
+  dfh_table* stepped = nullptr;    // the last step on the loaded minibatch was dfh_sgd_step on this table: d_uw holds its row words (dfh_explain)
   // device feed: a minibatch DESCRIBED by dfh_batch_prepare_rows whose rows are still in their row buffers: gathered by the
   // Localizer's count pass itself (k_loc_count_gather) or, where that pass cannot (first call of a size class, the large size
   // class, the library sort, a tile spanning too many rows, more than four buffers), by k_gather_rows_staged first

@@ -16,6 +16,7 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
   }
   hipStream_t s = prep_of(b);
   b->looked_up = nullptr;
+  b->stepped = nullptr;
   if (b->pend_stage < RID_STAGES) {  // localized twice without a step in between
     int rc = flush_pending(b);
     if (rc) return rc;

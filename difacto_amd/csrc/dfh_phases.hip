@@ -52,6 +52,7 @@ int main_begin(dfh_batch* b) {
 }
 int main_end(dfh_batch* b) {
   dfh_ctx* c = b->ctx;
+  b->stepped = nullptr;  // (dfh_sgd_step sets it behind this call)
   if (b->split_listing) {  // this step's launches filled one counter of the split list and zeroed the other: the next step's
     b->split_listing = false;
     b->split_last = b->split_sel;

@@ -416,7 +416,9 @@ int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt) {
     rc = launch_forward(b, src, k, kp, nullptr, nullptr, true);
     if (rc) return rc;
     collect_riders(c, 2, false, 0, &none);
-    return main_end(b);
+    rc = main_end(b);
+    if (!rc) b->stepped = t;
+    return rc;
   }
   const bool refrand = t->v.p.init_mode == DFH_INIT_REFRAND && k > 0;
   const uint32_t Nb = (uint32_t)b->nnz;  // upper bound of U for grids
@@ -443,7 +445,9 @@ int dfh_sgd_step(dfh_table* t, dfh_batch* b, int is_train, int push_cnt) {
     rc = refrand_flush(t, b->d_feaids, b->d_U, Nb, b->d_urow, b->d_need, b->d_rank, b->d_total);
     if (rc) return rc;
   }
-  return main_end(b);
+  rc = main_end(b);
+  if (!rc) b->stepped = t;
+  return rc;
 }
 
 int dfh_batch_forward(dfh_batch* b, int V_dim, const float* d_rows) {

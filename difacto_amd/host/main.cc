@@ -95,6 +95,14 @@ int main(int argc, char* argv[]) {
     CHECK(!(kw.first == "rec_decode" && kw.second == "device" && param.learner != "sgd" && param.task != "convert"))
         << "rec_decode=device with learner=" << param.learner << ": only learner=sgd reads its training data through the device "
            "feed, whose records the device decodes; leave rec_decode out";
+  // explain_out is a key of learner = sgd's prediction loop: elsewhere it would only draw a warning about an unknown key
+  for (const auto& kw : kwargs_remain) {
+    if (kw.first != "explain_out" || kw.second.empty()) continue;
+    CHECK(param.task == "predict") << "explain_out with task=" << param.task << ": the pairs are those of the rows task=predict "
+                                      "scores; use task=predict with model_in, or leave explain_out out";
+    CHECK(param.learner == "sgd") << "explain_out with learner=" << param.learner << ": only learner=sgd has the prediction loop "
+                                     "that computes them (an lbfgs model is scored with learner=sgd model_in=<it>); leave explain_out out";
+  }
   if (param.task == "train") {
     Learner* learner = Learner::Create(param.learner);
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));

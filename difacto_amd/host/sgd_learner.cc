@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <memory>
 #include <thread>
 #include <unistd.h>
@@ -28,6 +29,7 @@ DMLC_REGISTER_PARAMETER(FMLossParam);
 SGDLearner::~SGDLearner() {
   if (eval_) dfh_eval_destroy(eval_);
   if (predtext_) dfh_predtext_destroy(predtext_);
+  if (explain_) dfh_explain_destroy(explain_);
   delete loss_;
   delete store_;
 }
@@ -78,6 +80,24 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
                                        "the text of task=predict is formatted; use task=predict, or leave pred_write out";
     CHECK(!IsDistributed()) << "pred_write=device with a sharded store (DMLC_ROLE is set): the sharded worker loop writes its "
                                "predictions on the host; run one process, or leave pred_write out";
+  }
+  // explain_out: checked before anything touches the device, like data_cache
+  if (param_.explain_out.size()) {
+    CHECK(param_.task == "predict") << "explain_out with task=" << param_.task << ": the pairs are those of the rows task=predict "
+                                       "scores; use task=predict with model_in, or leave explain_out out";
+    CHECK(!IsDistributed()) << "explain_out with a sharded store (DMLC_ROLE is set): a sharded step leaves the rows of other owners "
+                               "outside this rank's table, where the pairs are not computed; run one process, or leave explain_out out";
+    CHECK(param_.explain_topk >= 1 && param_.explain_topk <= 32)
+        << "explain_topk=" << param_.explain_topk << " is not a number of pairs per row between 1 and 32";
+    CHECK(param_.explain_by == "abs" || param_.explain_by == "pos")
+        << "explain_by=" << param_.explain_by << " is not one of abs (the default: by |c|) and pos (by c)";
+    for (const auto& kv : remain) {
+      CHECK(!(kv.first == "device_path" && kv.second == "literal"))
+          << "explain_out with device_path=literal: the literal loop hands host arrays to Store and Loss, only device_path=fused "
+             "leaves a stepped minibatch on the device; use device_path=fused, or leave explain_out out";
+      CHECK(!(kv.first == "V_dim" && atoi(kv.second.c_str()) == 0))
+          << "explain_out with V_dim=0: a linear model has no interaction pairs; leave explain_out out";
+    }
   }
   // text_parse: checked before anything touches the device, like data_cache.  "device" is accepted only where the device feed
   // reads the training data (IterateDataFused); validation and prediction readers outside the feed keep the host parser
@@ -323,6 +343,33 @@ void SGDLearner::ClosePredUnit() {
   DFH_CALL(dfh_predtext_reset(pt));
 }
 
+// explain_out: one line per row of the unit, "<inter>" then "\t<id_i>:<id_j>:<c>" per pair, behind the lines of the units before
+void SGDLearner::CloseExplainUnit() {
+  dfh_explain* e = CHECK_NOTNULL(explain_);
+  const size_t n = explain_unit_n_, K = static_cast<size_t>(param_.explain_topk);
+  explain_unit_n_ = 0;
+  std::vector<uint32_t> cnt(n);
+  std::vector<uint64_t> ids_i(n * K), ids_j(n * K);
+  std::vector<float> c(n * K), inter(n);
+  uint64_t nonfinite = 0;
+  DFH_CALL(dfh_explain_read(e, cnt.data(), ids_i.data(), ids_j.data(), c.data(), inter.data(), &nonfinite));
+  if (nonfinite)
+    LOG(WARNING) << "explain_out: " << nonfinite << " pairs of this unit have a contribution that is not finite; they are in no "
+                    "line and in no total";
+  std::string text;
+  text.reserve(n * (16 + K * 60));
+  char buf[96];
+  for (size_t r = 0; r < n; ++r) {
+    text.append(buf, snprintf(buf, sizeof(buf), "%.9g", inter[r]));
+    for (size_t j = 0; j < cnt[r]; ++j)
+      text.append(buf, snprintf(buf, sizeof(buf), "\t%llu:%llu:%.9g", static_cast<unsigned long long>(ids_i[r * K + j]),
+                                static_cast<unsigned long long>(ids_j[r * K + j]), c[r * K + j]));
+    text.push_back('\n');
+  }
+  CHECK_EQ(fwrite(text.data(), 1, text.size(), CHECK_NOTNULL(explain_file_)), text.size()) << "cannot write " << param_.explain_out;
+  DFH_CALL(dfh_explain_reset(e));
+}
+
 void SGDLearner::MergeAcrossRanks(sgd::Progress* prog) {
   auto* ss = dynamic_cast<ShardedDeviceStore*>(store_);
   if (!ss) return;
@@ -347,9 +394,17 @@ void SGDLearner::Process(const std::string& args, std::string* rets) {
     const std::string path = sharded ? param_.pred_out + ".part-" + std::to_string(job.part_idx) : param_.pred_out;
     pred_file_ = fopen(path.c_str(), (sharded || job.part_idx == 0) ? "w" : "a");
     CHECK(pred_file_) << "cannot open " << path;
+    if (param_.explain_out.size()) {
+      explain_file_ = fopen(param_.explain_out.c_str(), job.part_idx == 0 ? "w" : "a");
+      CHECK(explain_file_) << "cannot open " << param_.explain_out;
+    }
     IterateData(job, &prog);
     CHECK_EQ(fclose(pred_file_), 0) << "cannot write " << path;
     pred_file_ = nullptr;
+    if (explain_file_) {
+      CHECK_EQ(fclose(explain_file_), 0) << "cannot write " << param_.explain_out;
+      explain_file_ = nullptr;
+    }
   }
   prog.SerializeToString(rets);
 }
@@ -490,6 +545,13 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     pred_unit_n_ = 0;
     pred_counts_ = PredCounts();
   }
+  const bool explain = predict && param_.explain_out.size();
+  if (explain) {
+    if (!explain_)
+      DFH_CALL(dfh_explain_create(ctx, param_.explain_topk, param_.explain_by == "pos" ? DFH_PAIRS_POS : DFH_PAIRS_ABS, 0, &explain_));
+    DFH_CALL(dfh_explain_reset(explain_));
+    explain_unit_n_ = 0;
+  }
   // DIFACTO_PROFILE=1: where the host thread of this loop spends its time (reader wait + batch assembly, staging + Localizer /
   // lookup queueing, step queueing; t_feed: inside the second, waiting for a buffer's upload), printed at the end of the job
   const bool prof = env.profile;
@@ -555,6 +617,13 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     dfh_batch* b = ring_[BatchRing::SlotOf(i, nrot)];
     DFH_CALL(dfh_sgd_step(table, b, train ? 1 : 0, push_cnt ? 1 : 0));
     if (eval_ && !train) DFH_CALL(dfh_eval_append_batch(eval_, b));  // exact_metrics = 1: queued behind the step
+    if (explain) {   // explain_out: queued behind the step, nothing waits
+      DFH_CALL(dfh_explain_append_batch(explain_, b, table));
+      size_t nrows = 0;
+      DFH_CALL(dfh_batch_shape(b, &nrows, nullptr, nullptr));
+      explain_unit_n_ += nrows;
+      if (explain_unit_n_ >= static_cast<size_t>(param_.pred_unit_rows)) CloseExplainUnit();
+    }
     if (predict && src.pred_feed) {   // pred_write = device: queued behind the step, nothing waits
       DFH_CALL(dfh_predtext_append_batch(predtext_, b));
       size_t nrows = 0;
@@ -593,6 +662,7 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     step_one();
     lap(&t_step);
   }
+  if (explain && explain_unit_n_) CloseExplainUnit();
   if (src.pred_feed) {   // a unit closes at the end of every data part
     if (pred_unit_n_) ClosePredUnit();
     WaitPredWrite();

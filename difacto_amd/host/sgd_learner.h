@@ -68,6 +68,8 @@ class SGDLearner : public Learner {
   void ClosePredUnit();
   /*! \brief pred_write = device: waits for the unit that is still being written */
   void WaitPredWrite();
+  /*! \brief explain_out: the unit's rows come down and go to the file as one line each, formatted here; the unit starts empty again */
+  void CloseExplainUnit();
   /*! \brief exact_metrics = 1: the whole-set figures of the pass that has just ended, as one log line behind `what` */
   void LogExactMetrics(const char* what);
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
@@ -108,6 +110,10 @@ class SGDLearner : public Learner {
   int pred_text_cur_ = 0;
   std::future<void> pred_write_;
   size_t pred_unit_n_ = 0;
+  // explain_out: the open unit's rows (they close at pred_unit_rows like the units of pred_write = device, and with a data part)
+  dfh_explain* explain_ = nullptr;
+  FILE* explain_file_ = nullptr;
+  size_t explain_unit_n_ = 0;
   struct PredCounts { size_t dev_rows = 0, dev_units = 0, host_rows = 0, host_units = 0; } pred_counts_;
 };
 

@@ -43,6 +43,13 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   // exact_metrics = 1 (a key of this build): validation epochs and task = predict keep every prediction and label on the device
   // and report the exact AUC, logloss and accuracy of the whole set in one more log line (dfh_eval); nothing else changes
   int exact_metrics;         // 0 (default) | 1
+  // explain_out (keys of this build; task = predict, one process, the fused loop, V_dim > 0): one more line per data row, in
+  // file order like pred_out: "<inter>" and "\t<id_i>:<id_j>:<c>" per pair — the explain_topk pairs of the row's features with
+  // the largest contribution c = x_i x_j <V_i, V_j> to its logit, and inter = the sum over all of its pairs
+  // (csrc/dfh_explain.hip); every float as %.9g, the ids as task = dump prints them.  pred_out keeps its bytes
+  std::string explain_out;   // predict: "" (default: nothing new runs) | the file
+  int explain_topk;          // 1 .. 32 pairs per row
+  std::string explain_by;    // "abs" (default: by |c|) | "pos" (by c)
   DMLC_DECLARE_PARAMETER(SGDLearnerParam) {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
@@ -52,6 +59,9 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
     DMLC_DECLARE_FIELD(data_cache).set_default("");
     DMLC_DECLARE_FIELD(data_cache_max_gb).set_default(0);
     DMLC_DECLARE_FIELD(exact_metrics).set_default(0);
+    DMLC_DECLARE_FIELD(explain_out).set_default("");
+    DMLC_DECLARE_FIELD(explain_topk).set_default(10);
+    DMLC_DECLARE_FIELD(explain_by).set_default("abs");
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_in);
     DMLC_DECLARE_FIELD(data_val).set_default("");

@@ -113,6 +113,7 @@ int dfh_ctx_set_option(dfh_ctx* ctx, const char* name, int value);
 enum {
   DFH_K_LOCALIZE = 0, DFH_K_LOOKUP, DFH_K_FORWARD, DFH_K_BACKWARD, DFH_K_PULL, DFH_K_PUSH, DFH_K_MISC, DFH_K_AUC,
   DFH_K_PAIRS_PACK, DFH_K_PAIRS_SWEEP, DFH_K_PAIRS_MERGE,   /* dfh_dump_pairs' three stages */
+  DFH_K_EXPLAIN,                                            /* dfh_explain_append_batch's kernel */
   DFH_K_COUNT
 };
 int dfh_ctx_set_timing(dfh_ctx* ctx, int enable);
@@ -942,6 +943,39 @@ int dfh_dump_tile(dfh_dump* d);
 enum { DFH_PAIRS_ABS = 0, DFH_PAIRS_POS = 1 };
 int dfh_dump_pairs(dfh_dump* d, uint64_t first, size_t count, int topk, int by, uint64_t* partner_ids /*[count*topk]*/,
                    float* scores /*[count*topk]*/, uint32_t* npartners /*[count]*/, uint64_t* nonfinite);
+
+/* ------------------------------------------------ each row's strongest interaction pairs (explain_out of task = predict) */
+/* A dfh_explain keeps, for every row appended since the last reset, the topk (1 .. 32) pairs of positions i < j of the row with
+ * the largest contribution c_ij = x_i x_j <V_i, V_j> to the row's logit, and inter = the sum of c_ij over ALL pairs of the row
+ * (csrc/dfh_explain.hip, whose header comment has the full definition).  Only positions whose key has V take part; a pair is
+ * formed between positions, so a key that occurs twice in a row pairs with itself.  by = DFH_PAIRS_ABS ranks by |c|,
+ * DFH_PAIRS_POS by c; key descending, equal keys by ascending (i, j); c and inter are fp32 sums of fp32 products.  A pair whose
+ * c is not finite enters no list and no inter, and is counted.  Device memory: 28 topk + 8 bytes per row (the arrays grow by
+ * doubling, earlier rows survive; capacity_hint: the rows of the first allocation, 0: 16 384) and 4 bytes per nonzero of the
+ * largest minibatch appended.
+ * Errors: DFH_ERR_ARG for NULL arguments, topk outside [1, 32], another by; DFH_ERR_STATE when the batch's last step was not
+ * dfh_sgd_step on this table (not stepped, or stepped through the sharded store); DFH_ERR_CAPACITY for a failed allocation, with
+ * the bytes needed in the message. */
+typedef struct dfh_explain dfh_explain;
+int dfh_explain_create(dfh_ctx* ctx, int topk, int by, size_t capacity_hint, dfh_explain** out);
+int dfh_explain_destroy(dfh_explain* e);
+/* n = 0, the non-finite count back to 0; the arrays stay */
+int dfh_explain_reset(dfh_explain* e);
+/* queues k_explain over the batch's rows on the context's stream, behind the batch's last step (dfh_sgd_step on `table`: the
+ * kernel reads the row words that step's lookup left and the table's V rows as they are now), and does not wait for the device;
+ * call it before the next minibatch is loaded into the batch object (with pipelining on, that load waits for the kernel: the
+ * call moves the object's `free` event behind it).  It may stand beside the eval and predtext appends, in any order.  A table
+ * with V_dim = 0: nothing is launched, the rows get empty lists. */
+int dfh_explain_append_batch(dfh_explain* e, dfh_batch* batch, dfh_table* table);
+/* the rows appended since the last reset */
+int dfh_explain_count(dfh_explain* e, uint64_t* n);
+/* everything appended since the last reset, in append order; synchronises once.  Row r: n[r] pairs in ids_i / ids_j / c
+ * [r * topk ..] (the ids as task = dump dump_ids = feature prints them; zeros behind n[r]), inter[r].  *nonfinite: the pairs
+ * left out since the last reset because their c was not finite. */
+int dfh_explain_read(dfh_explain* e, uint32_t* n /*[count]*/, uint64_t* ids_i /*[count*topk]*/, uint64_t* ids_j /*[count*topk]*/,
+                     float* c /*[count*topk]*/, float* inter /*[count]*/, uint64_t* nonfinite);
+/* the same pairs as positions inside their rows (0-based, i < j), for a caller that holds the rows; synchronises */
+int dfh_explain_read_positions(dfh_explain* e, uint32_t* pos_i /*[count*topk]*/, uint32_t* pos_j /*[count*topk]*/);
 
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
