@@ -53,12 +53,14 @@ SYMBOLS = [
     "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_ids", "dfh_dump_tile", "dfh_dump_pairs",
     "dfh_explain_create", "dfh_explain_destroy", "dfh_explain_reset", "dfh_explain_append_batch", "dfh_explain_count", "dfh_explain_read",
     "dfh_explain_read_positions",
+    "dfh_recommend_create", "dfh_recommend_destroy", "dfh_recommend_reset", "dfh_recommend_add_items", "dfh_recommend_item_count",
+    "dfh_recommend_append_batch", "dfh_recommend_count", "dfh_recommend_read",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
 XCHG_COUNTS, XCHG_KEYS, XCHG_CNT, XCHG_ROWS, XCHG_GRADS, XCHG_OTHER = range(6)
 SHARD_STAGES = ("counts", "L", "K", "R", "RW", "F", "G", "P")
-K_COUNT = 12
+K_COUNT = 15
 K_LOCALIZE, K_LOOKUP, K_FORWARD, K_BACKWARD, K_PULL, K_PUSH, K_MISC, K_AUC = range(8)
 
 
@@ -247,6 +249,14 @@ def lib():
     L.dfh_explain_count.argtypes = [vp, PP(C.c_uint64)]
     L.dfh_explain_read.argtypes = [vp, vp, vp, vp, vp, vp, PP(C.c_uint64)]
     L.dfh_explain_read_positions.argtypes = [vp, vp, vp]
+    L.dfh_recommend_create.argtypes = [vp, i32, sz, PP(vp)]
+    L.dfh_recommend_destroy.argtypes = [vp]
+    L.dfh_recommend_reset.argtypes = [vp]
+    L.dfh_recommend_add_items.argtypes = [vp, vp, vp]
+    L.dfh_recommend_item_count.argtypes = [vp, PP(C.c_uint64)]
+    L.dfh_recommend_append_batch.argtypes = [vp, vp, vp]
+    L.dfh_recommend_count.argtypes = [vp, PP(C.c_uint64)]
+    L.dfh_recommend_read.argtypes = [vp, vp, vp, vp, PP(C.c_uint64)]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -1056,6 +1066,55 @@ class Explain:
     def close(self):
         if self.h:
             lib().dfh_explain_destroy(self.h)
+            self.h = None
+
+
+class Recommend:
+    """a catalogue of item rows and, per appended query row, the topk items with the largest b_i + <S_q, S_i>, handed out with
+    the logit of the concatenated row (dfh_recommend)"""
+
+    def __init__(self, ctx, topk=10, capacity_hint=0):
+        self.ctx = ctx
+        self.topk = topk
+        self.h = C.c_void_p()
+        _ck(lib().dfh_recommend_create(ctx.h, topk, capacity_hint, C.byref(self.h)))
+
+    def reset(self):
+        """drops the queries; the catalogue stays"""
+        _ck(lib().dfh_recommend_reset(self.h))
+
+    def add_items(self, batch, table):
+        """the batch's rows (last stepped by sgd_step on `table`) become the next items of the catalogue; does not wait"""
+        _ck(lib().dfh_recommend_add_items(self.h, batch.h, table.h))
+
+    def item_count(self):
+        m = C.c_uint64(0)
+        _ck(lib().dfh_recommend_item_count(self.h, C.byref(m)))
+        return m.value
+
+    def append_batch(self, batch, table):
+        """the batch's rows as queries, queued behind its last step (sgd_step on `table`); does not wait"""
+        _ck(lib().dfh_recommend_append_batch(self.h, batch.h, table.h))
+
+    def count(self):
+        n = C.c_uint64(0)
+        _ck(lib().dfh_recommend_count(self.h, C.byref(n)))
+        return n.value
+
+    def read(self):
+        """-> dict(n [rows], items, logits [rows x topk], nonfinite) of the queries appended since the last reset, in append
+        order (waits; nothing is consumed); row q is valid up to n[q]"""
+        rows, K = self.count(), self.topk
+        n = np.zeros(max(rows, 1), np.uint32)
+        items, logits = np.zeros(max(rows * K, 1), np.uint32), np.zeros(max(rows * K, 1), np.float32)
+        nf = C.c_uint64(0)
+        _ck(lib().dfh_recommend_read(self.h, _p(n), _p(items), _p(logits), C.byref(nf)))
+        sq = lambda a: a[:rows * K].reshape(rows, K)
+        return dict(n=n[:rows], items=sq(items), logits=sq(logits), nonfinite=nf.value)
+
+    def close(self):
+        if self.h:
+            lib().dfh_recommend_destroy(self.h)
             self.h = None
 
 

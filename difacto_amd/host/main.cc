@@ -103,6 +103,14 @@ int main(int argc, char* argv[]) {
     CHECK(param.learner == "sgd") << "explain_out with learner=" << param.learner << ": only learner=sgd has the prediction loop "
                                      "that computes them (an lbfgs model is scored with learner=sgd model_in=<it>); leave explain_out out";
   }
+  // recommend_out and items_in too
+  for (const auto& kw : kwargs_remain) {
+    if ((kw.first != "recommend_out" && kw.first != "items_in") || kw.second.empty()) continue;
+    CHECK(param.task == "predict") << kw.first << " with task=" << param.task << ": the items are ranked for the rows task=predict "
+                                      "scores; use task=predict with model_in, or leave " << kw.first << " out";
+    CHECK(param.learner == "sgd") << kw.first << " with learner=" << param.learner << ": only learner=sgd has the prediction loop "
+                                     "that ranks them (an lbfgs model is scored with learner=sgd model_in=<it>); leave " << kw.first << " out";
+  }
   if (param.task == "train") {
     Learner* learner = Learner::Create(param.learner);
     WarnUnknownKWArgs(param, learner->Init(kwargs_remain));

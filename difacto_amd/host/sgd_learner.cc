@@ -30,6 +30,7 @@ SGDLearner::~SGDLearner() {
   if (eval_) dfh_eval_destroy(eval_);
   if (predtext_) dfh_predtext_destroy(predtext_);
   if (explain_) dfh_explain_destroy(explain_);
+  if (recommend_) dfh_recommend_destroy(recommend_);
   delete loss_;
   delete store_;
 }
@@ -98,6 +99,26 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
       CHECK(!(kv.first == "V_dim" && atoi(kv.second.c_str()) == 0))
           << "explain_out with V_dim=0: a linear model has no interaction pairs; leave explain_out out";
     }
+  }
+  // recommend_out / items_in: the same
+  CHECK(param_.recommend_out.empty() || param_.items_in.size())
+      << "recommend_out without items_in: there is no catalogue to rank; name the item rows with items_in=<file>, or leave "
+         "recommend_out out";
+  CHECK(param_.items_in.empty() || param_.recommend_out.size())
+      << "items_in without recommend_out: the ranked items have nowhere to go; name the file with recommend_out=<file>, or leave "
+         "items_in out";
+  if (param_.recommend_out.size()) {
+    CHECK(param_.task == "predict") << "recommend_out with task=" << param_.task << ": the items are ranked for the rows "
+                                       "task=predict scores; use task=predict with model_in, or leave recommend_out out";
+    CHECK(!IsDistributed()) << "recommend_out with a sharded store (DMLC_ROLE is set): a sharded step leaves the rows of other "
+                               "owners outside this rank's table, where the items are not ranked; run one process, or leave "
+                               "recommend_out out";
+    CHECK(param_.recommend_topk >= 1 && param_.recommend_topk <= 32)
+        << "recommend_topk=" << param_.recommend_topk << " is not a number of items per row between 1 and 32";
+    for (const auto& kv : remain)
+      CHECK(!(kv.first == "device_path" && kv.second == "literal"))
+          << "recommend_out with device_path=literal: the literal loop hands host arrays to Store and Loss, only device_path=fused "
+             "leaves a stepped minibatch on the device; use device_path=fused, or leave recommend_out out";
   }
   // text_parse: checked before anything touches the device, like data_cache.  "device" is accepted only where the device feed
   // reads the training data (IterateDataFused); validation and prediction readers outside the feed keep the host parser
@@ -276,7 +297,12 @@ void SGDLearner::RunPrediction() {
             << " -> " << param_.pred_out << " (against their labels: " << prog.TextString() << ")";
 }
 
+const std::string& SGDLearner::JobFormat() const {
+  return catalogue_pass_ && param_.items_in_format.size() ? param_.items_in_format : param_.data_format;
+}
+
 const std::string& SGDLearner::JobData(const sgd::Job& job) const {
+  if (catalogue_pass_) return param_.items_in;
   if (job.type == sgd::Job::kTraining) return param_.data_in;
   if (job.type == sgd::Job::kPrediction) return param_.data_val.size() ? param_.data_val : param_.data_in;
   return param_.data_val;
@@ -370,6 +396,47 @@ void SGDLearner::CloseExplainUnit() {
   DFH_CALL(dfh_explain_reset(e));
 }
 
+// recommend_out: one line per row of the unit, "<item>:<logit>" joined by tabs, behind the lines of the units before
+void SGDLearner::CloseRecommendUnit() {
+  dfh_recommend* r = CHECK_NOTNULL(recommend_);
+  const size_t n = recommend_unit_n_, K = static_cast<size_t>(param_.recommend_topk);
+  recommend_unit_n_ = 0;
+  std::vector<uint32_t> cnt(n), items(n * K);
+  std::vector<float> logits(n * K);
+  uint64_t nonfinite = 0;
+  DFH_CALL(dfh_recommend_read(r, cnt.data(), items.data(), logits.data(), &nonfinite));
+  if (nonfinite)
+    LOG(WARNING) << "recommend_out: " << nonfinite << " (row, item) pairs of this unit have a score that is not finite; they are in "
+                    "no line";
+  std::string text;
+  text.reserve(n * (1 + K * 24));
+  char buf[64];
+  for (size_t q = 0; q < n; ++q) {
+    for (size_t j = 0; j < cnt[q]; ++j)
+      text.append(buf, snprintf(buf, sizeof(buf), "%s%u:%.9g", j ? "\t" : "", items[q * K + j], logits[q * K + j]));
+    text.push_back('\n');
+  }
+  CHECK_EQ(fwrite(text.data(), 1, text.size(), CHECK_NOTNULL(recommend_file_)), text.size()) << "cannot write " << param_.recommend_out;
+  DFH_CALL(dfh_recommend_reset(r));
+}
+
+// recommend_out: the catalogue pass.  The job's loop runs over items_in as one part, in file order; the model is untouched, as
+// in any prediction job
+void SGDLearner::ReadCatalogue(const sgd::Job& job) {
+  if (!recommend_) DFH_CALL(dfh_recommend_create(DeviceContext::Get(), param_.recommend_topk, 0, &recommend_));
+  sgd::Job cj = job;
+  cj.part_idx = 0;
+  cj.num_parts = 1;
+  sgd::Progress none;
+  catalogue_pass_ = true;
+  IterateData(cj, &none);
+  catalogue_pass_ = false;
+  uint64_t m = 0;
+  DFH_CALL(dfh_recommend_item_count(recommend_, &m));
+  CHECK(m) << "items_in=" << param_.items_in << " holds no row: there is no catalogue to rank";
+  LOG(INFO) << "recommend_out: a catalogue of " << m << " items from " << param_.items_in;
+}
+
 void SGDLearner::MergeAcrossRanks(sgd::Progress* prog) {
   auto* ss = dynamic_cast<ShardedDeviceStore*>(store_);
   if (!ss) return;
@@ -398,9 +465,18 @@ void SGDLearner::Process(const std::string& args, std::string* rets) {
       explain_file_ = fopen(param_.explain_out.c_str(), job.part_idx == 0 ? "w" : "a");
       CHECK(explain_file_) << "cannot open " << param_.explain_out;
     }
+    if (param_.recommend_out.size()) {
+      if (job.part_idx == 0) ReadCatalogue(job);
+      recommend_file_ = fopen(param_.recommend_out.c_str(), job.part_idx == 0 ? "w" : "a");
+      CHECK(recommend_file_) << "cannot open " << param_.recommend_out;
+    }
     IterateData(job, &prog);
     CHECK_EQ(fclose(pred_file_), 0) << "cannot write " << path;
     pred_file_ = nullptr;
+    if (recommend_file_) {
+      CHECK_EQ(fclose(recommend_file_), 0) << "cannot write " << param_.recommend_out;
+      recommend_file_ = nullptr;
+    }
     if (explain_file_) {
       CHECK_EQ(fclose(explain_file_), 0) << "cannot write " << param_.explain_out;
       explain_file_ = nullptr;
@@ -453,9 +529,9 @@ SGDLearner::FusedSource SGDLearner::SourceOf(const sgd::Job& job, const SgdLoopE
   s.cache_fill = s.cache_on && !s.cpart && !cache_.refused.count(std::make_pair(job.type, job.part_idx));
   s.pred_feed = job.type == sgd::Job::kPrediction && param_.pred_write == "device";
   s.device_feed = s.cpart || s.cache_fill || s.pred_feed || (job.type == sgd::Job::kTraining && param_.shuffle > 0 && !env.host_feed);
-  const bool criteo = param_.data_format == "criteo" || param_.data_format == "criteo_test";
+  const bool criteo = JobFormat() == "criteo" || JobFormat() == "criteo_test";
   s.device_parse = GetUpdater()->device_param().text_parse == "device" && s.uploads() && criteo;
-  s.device_decode = GetUpdater()->device_param().rec_decode == "device" && s.uploads() && param_.data_format == "rec";
+  s.device_decode = GetUpdater()->device_param().rec_decode == "device" && s.uploads() && JobFormat() == "rec";
   return s;
 }
 
@@ -479,14 +555,14 @@ BatchReader* SGDLearner::NewFusedReader(const sgd::Job& job, const FusedSource& 
     };
   }
   ParseHook parse_hook;
-  if (src.device_parse) parse_hook = text_parse->Hook(DeviceContext::Get(), param_.data_format == "criteo" ? 1 : 0);
+  if (src.device_parse) parse_hook = text_parse->Hook(DeviceContext::Get(), JobFormat() == "criteo" ? 1 : 0);
   if (src.device_decode) parse_hook = rec_decode->Hook(DeviceContext::Get());
   // the device parses: the parser threads only upload and wait (DeviceTextParse::kThreads; DIFACTO_PARSER_THREADS overrides)
   const int parser_threads = env.parser_threads_set  ? 0
                              : src.device_parse      ? DeviceTextParse::kThreads
                              : src.device_decode     ? DeviceRecDecode::kThreads
                                                      : 0;
-  BatchReader* reader = new BatchReader(JobData(job), param_.data_format, job.part_idx, job.num_parts, param_.batch_size,
+  BatchReader* reader = new BatchReader(JobData(job), JobFormat(), job.part_idx, job.num_parts, param_.batch_size,
                                         src.in_order() ? cache_buf_rows : (train ? param_.batch_size * param_.shuffle : 0), sampling,
                                         src.device_feed, upload, src.in_order() ? permute : true, parse_hook, parser_threads);
   if (src.uploads()) reader->DescribeSlices(nullptr);
@@ -545,7 +621,13 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     pred_unit_n_ = 0;
     pred_counts_ = PredCounts();
   }
-  const bool explain = predict && param_.explain_out.size();
+  const bool catalogue = catalogue_pass_;   // recommend_out: this job reads items_in; its minibatches become items, nothing is written
+  const bool explain = predict && !catalogue && param_.explain_out.size();
+  const bool recommend = predict && !catalogue && param_.recommend_out.size();
+  if (recommend) {
+    DFH_CALL(dfh_recommend_reset(CHECK_NOTNULL(recommend_)));
+    recommend_unit_n_ = 0;
+  }
   if (explain) {
     if (!explain_)
       DFH_CALL(dfh_explain_create(ctx, param_.explain_topk, param_.explain_by == "pos" ? DFH_PAIRS_POS : DFH_PAIRS_ABS, 0, &explain_));
@@ -616,6 +698,11 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
   auto step_one = [&] {
     dfh_batch* b = ring_[BatchRing::SlotOf(i, nrot)];
     DFH_CALL(dfh_sgd_step(table, b, train ? 1 : 0, push_cnt ? 1 : 0));
+    if (catalogue) {
+      DFH_CALL(dfh_recommend_add_items(recommend_, b, table));
+      ++i;
+      return;
+    }
     if (eval_ && !train) DFH_CALL(dfh_eval_append_batch(eval_, b));  // exact_metrics = 1: queued behind the step
     if (explain) {   // explain_out: queued behind the step, nothing waits
       DFH_CALL(dfh_explain_append_batch(explain_, b, table));
@@ -623,6 +710,13 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
       DFH_CALL(dfh_batch_shape(b, &nrows, nullptr, nullptr));
       explain_unit_n_ += nrows;
       if (explain_unit_n_ >= static_cast<size_t>(param_.pred_unit_rows)) CloseExplainUnit();
+    }
+    if (recommend) {   // recommend_out: queued behind the step, nothing waits
+      DFH_CALL(dfh_recommend_append_batch(recommend_, b, table));
+      size_t nrows = 0;
+      DFH_CALL(dfh_batch_shape(b, &nrows, nullptr, nullptr));
+      recommend_unit_n_ += nrows;
+      if (recommend_unit_n_ >= static_cast<size_t>(param_.pred_unit_rows)) CloseRecommendUnit();
     }
     if (predict && src.pred_feed) {   // pred_write = device: queued behind the step, nothing waits
       DFH_CALL(dfh_predtext_append_batch(predtext_, b));
@@ -663,6 +757,7 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     lap(&t_step);
   }
   if (explain && explain_unit_n_) CloseExplainUnit();
+  if (recommend && recommend_unit_n_) CloseRecommendUnit();
   if (src.pred_feed) {   // a unit closes at the end of every data part
     if (pred_unit_n_) ClosePredUnit();
     WaitPredWrite();
@@ -671,7 +766,7 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
   if (prof)
     LOG(INFO) << "host loop over " << i << " minibatches: reader " << t_read << " s, stage + localize + lookup " << t_prep
               << " s (" << t_feed << " s of it waiting for a buffer's upload), step " << t_step << " s";
-  if (src.pred_feed) {
+  if (src.pred_feed && !catalogue) {
     LOG(INFO) << "pred_write=device: " << pred_counts_.dev_rows << " rows in " << pred_counts_.dev_units
               << " units formatted on the device, " << pred_counts_.host_rows << " rows in " << pred_counts_.host_units
               << " units on the host";

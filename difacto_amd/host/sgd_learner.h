@@ -70,6 +70,12 @@ class SGDLearner : public Learner {
   void WaitPredWrite();
   /*! \brief explain_out: the unit's rows come down and go to the file as one line each, formatted here; the unit starts empty again */
   void CloseExplainUnit();
+  /*! \brief recommend_out: the unit's rows come down and go to the file as one line each; the unit starts empty again */
+  void CloseRecommendUnit();
+  /*! \brief recommend_out: items_in through the prediction loop once, every minibatch appended to the catalogue */
+  void ReadCatalogue(const sgd::Job& job);
+  /*! \brief the format of JobData(job): items_in_format for the catalogue pass, else data_format */
+  const std::string& JobFormat() const;
   /*! \brief exact_metrics = 1: the whole-set figures of the pass that has just ended, as one log line behind `what` */
   void LogExactMetrics(const char* what);
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
@@ -114,6 +120,12 @@ class SGDLearner : public Learner {
   dfh_explain* explain_ = nullptr;
   FILE* explain_file_ = nullptr;
   size_t explain_unit_n_ = 0;
+  // recommend_out: the catalogue and the open unit's rows (units close like explain_out's); catalogue_pass_: the loop is reading
+  // items_in, its minibatches become items and nothing is written
+  dfh_recommend* recommend_ = nullptr;
+  FILE* recommend_file_ = nullptr;
+  size_t recommend_unit_n_ = 0;
+  bool catalogue_pass_ = false;
   struct PredCounts { size_t dev_rows = 0, dev_units = 0, host_rows = 0, host_units = 0; } pred_counts_;
 };
 

@@ -50,6 +50,14 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   std::string explain_out;   // predict: "" (default: nothing new runs) | the file
   int explain_topk;          // 1 .. 32 pairs per row
   std::string explain_by;    // "abs" (default: by |c|) | "pos" (by c)
+  // recommend_out (keys of this build; task = predict, one process, the fused loop): items_in is a CATALOGUE of item rows, read
+  // once before the data through the same feed and step; recommend_out gets one line per data row, in file order like pred_out:
+  // "<item>:<logit>" joined by tabs — the recommend_topk items (numbered 0 .. M - 1 in items_in's order) whose concatenation with
+  // the row scores highest, with that logit (csrc/dfh_recommend.hip); every float as %.9g.  pred_out keeps its bytes
+  std::string items_in;         // predict: "" | the catalogue
+  std::string items_in_format;  // "" (default: data_format)
+  std::string recommend_out;    // predict: "" (default: nothing new runs) | the file
+  int recommend_topk;           // 1 .. 32 items per row
   DMLC_DECLARE_PARAMETER(SGDLearnerParam) {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
@@ -62,6 +70,10 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
     DMLC_DECLARE_FIELD(explain_out).set_default("");
     DMLC_DECLARE_FIELD(explain_topk).set_default(10);
     DMLC_DECLARE_FIELD(explain_by).set_default("abs");
+    DMLC_DECLARE_FIELD(items_in).set_default("");
+    DMLC_DECLARE_FIELD(items_in_format).set_default("");
+    DMLC_DECLARE_FIELD(recommend_out).set_default("");
+    DMLC_DECLARE_FIELD(recommend_topk).set_default(10);
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_in);
     DMLC_DECLARE_FIELD(data_val).set_default("");

@@ -105,7 +105,8 @@ int dfh_ctx_set_pipeline(dfh_ctx* ctx, int enable);
  *                                       dfh_shard_push_grad_listed) instead of per received entry; same results, not faster
  *                                       (default 0; measurement switch)
  *   "pairs_split"       0 .. 64         dfh_dump_pairs: the candidate splits of the sweep's grid; 0 (default) = chosen so that a
- *                                       small model still fills the chip.  No bit of the output depends on it (tests, measuring) */
+ *                                       small model still fills the chip.  No bit of the output depends on it (tests, measuring)
+ *   "rec_split"         0 .. 64         dfh_recommend_append_batch: the item splits of the sweep's grid, with the same meaning */
 int dfh_ctx_set_option(dfh_ctx* ctx, const char* name, int value);
 
 /* optional per-kernel timing with HIP events recorded on the context's stream
@@ -114,6 +115,7 @@ enum {
   DFH_K_LOCALIZE = 0, DFH_K_LOOKUP, DFH_K_FORWARD, DFH_K_BACKWARD, DFH_K_PULL, DFH_K_PUSH, DFH_K_MISC, DFH_K_AUC,
   DFH_K_PAIRS_PACK, DFH_K_PAIRS_SWEEP, DFH_K_PAIRS_MERGE,   /* dfh_dump_pairs' three stages */
   DFH_K_EXPLAIN,                                            /* dfh_explain_append_batch's kernel */
+  DFH_K_REC_EMBED, DFH_K_REC_SWEEP, DFH_K_REC_MERGE,        /* dfh_recommend_*'s three kernels */
   DFH_K_COUNT
 };
 int dfh_ctx_set_timing(dfh_ctx* ctx, int enable);
@@ -976,6 +978,38 @@ int dfh_explain_read(dfh_explain* e, uint32_t* n /*[count]*/, uint64_t* ids_i /*
                      float* c /*[count*topk]*/, float* inter /*[count]*/, uint64_t* nonfinite);
 /* the same pairs as positions inside their rows (0-based, i < j), for a caller that holds the rows; synchronises */
 int dfh_explain_read_positions(dfh_explain* e, uint32_t* pos_i /*[count*topk]*/, uint32_t* pos_j /*[count*topk]*/);
+
+/* ------------------------------------------------ each row's best catalogue items (recommend_out of task = predict) */
+/* A dfh_recommend holds a CATALOGUE of item rows and, for every query row appended since the last reset, the topk (1 .. 32)
+ * items i with the largest s(q, i) = b_i + <S_q, S_i>, where S_r = sum_j x_j V_j over the row's positions whose key has V and
+ * b_r is the row's own (unclamped) FM logit; the value handed out is a_q + s(q, i) = the logit of the concatenated row q u i
+ * (csrc/dfh_recommend.hip, whose header comment has the full definition; a key shared by query and item counts as two
+ * positions).  Items are numbered 0 .. M - 1 in the order they were added; s descending, equal s by ascending item number; all
+ * M items when M < topk.  Everything is fp32; the R x M scores are one GEMM on MFMA that is never stored.  An item whose s is
+ * not finite enters no list; such (query, item) pairs are counted.  No bit of the output depends on how the catalogue was cut
+ * into batches or on "rec_split" (dfh_ctx_set_option, 0 .. 64: the item splits of the sweep's grid, 0 = chosen from the grid).
+ * Device memory: 4 roundup(V_dim + 1, 8) bytes per item (the array grows by doubling; capacity_hint: the items of the first
+ * allocation) and 8 topk + 4 bytes per query row.
+ * Errors: DFH_ERR_ARG for NULL arguments, topk outside [1, 32], a table other than the catalogue's; DFH_ERR_STATE when the
+ * batch's last step was not dfh_sgd_step on this table, for a query while the catalogue is empty and for an item while queries
+ * are held; DFH_ERR_CAPACITY for a failed allocation, with the bytes needed in the message. */
+typedef struct dfh_recommend dfh_recommend;
+int dfh_recommend_create(dfh_ctx* ctx, int topk, size_t capacity_hint, dfh_recommend** out);
+int dfh_recommend_destroy(dfh_recommend* r);
+/* appends the stepped batch's rows to the catalogue (k_rec_embed, queued behind the step; does not wait) */
+int dfh_recommend_add_items(dfh_recommend* r, dfh_batch* batch, dfh_table* table);
+int dfh_recommend_item_count(dfh_recommend* r, uint64_t* m);
+/* the stepped batch's rows as queries against the catalogue as it stands: k_rec_embed, k_rec_topk, k_rec_merge queued behind
+ * the step; does not wait.  Call it before the next minibatch is loaded into the batch object, like dfh_explain_append_batch */
+int dfh_recommend_append_batch(dfh_recommend* r, dfh_batch* batch, dfh_table* table);
+/* the query rows appended since the last reset */
+int dfh_recommend_count(dfh_recommend* r, uint64_t* n);
+/* everything appended since the last reset, in append order; synchronises once.  Row q: n[q] entries in items / logits
+ * [q * topk ..], zeros behind n[q].  *nonfinite: the (query, item) pairs left out since the last reset */
+int dfh_recommend_read(dfh_recommend* r, uint32_t* n /*[count]*/, uint32_t* items /*[count*topk]*/, float* logits /*[count*topk]*/,
+                       uint64_t* nonfinite);
+/* drops the queries and the non-finite count; the catalogue stays */
+int dfh_recommend_reset(dfh_recommend* r);
 
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
