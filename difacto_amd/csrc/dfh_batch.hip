@@ -94,7 +94,6 @@ static int batch_create_impl(dfh_ctx* c, size_t max_rows, size_t max_nnz, dfh_ba
   DFH_ALLOC(b->d_smp_rank, LOC_BIG_BUCKETS * LOC_OVERSAMPLE, uint32_t);
   DFH_ALLOC(b->d_first_key, LOC_BIG_BUCKETS, uint64_t);
   DFH_ALLOC(b->d_last_key, LOC_BIG_BUCKETS, uint64_t);
-  DFH_ALLOC(b->d_packed, N, uint32_t);
   DFH_ALLOC(b->d_run_off, b->max_tiles * LOC_BIG_BUCKETS, uint32_t);
   DFH_ALLOC(b->d_bstart, LOC_BIG_BUCKETS + 1, uint32_t);
   DFH_ALLOC(b->d_btotal, LOC_XCDS * LOC_BIG_BUCKETS, uint32_t);

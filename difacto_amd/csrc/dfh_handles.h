@@ -155,14 +155,14 @@ struct dfh_batch {
   bool defer_ready = false;        // inside a combined preparation call: the intermediate phases do not record ev_ready
   // localizer workspace
   uint64_t *d_keys = nullptr, *d_skeys = nullptr;   // bucket-major / sorted keys
-  uint32_t *d_pos = nullptr, *d_spos = nullptr;     // row of every nnz position (d_pos) / sorted positions
+  uint32_t *d_pos = nullptr, *d_spos = nullptr;     // positions as the library sort's values (d_pos) / sorted positions or tags
   uint32_t *d_bpos = nullptr;                       // bucket-major positions
   uint32_t *d_head = nullptr, *d_uid = nullptr;     // library-sort path only
   void* d_temp = nullptr;
   size_t temp_bytes = 0;
   // sample-sort localizer: bootstrap samples, persistent splitters, per-call bucket bookkeeping
   uint64_t *d_smp_key = nullptr, *d_spl_key = nullptr, *d_first_key = nullptr, *d_last_key = nullptr;
-  uint32_t *d_smp_rank = nullptr, *d_smp_pos = nullptr, *d_spl_pos = nullptr, *d_packed = nullptr, *d_run_off = nullptr,
+  uint32_t *d_smp_rank = nullptr, *d_smp_pos = nullptr, *d_spl_pos = nullptr, *d_run_off = nullptr,
            *d_bstart = nullptr, *d_btotal = nullptr, *d_nheads = nullptr, *d_lh = nullptr;
   size_t max_tiles = 0;
   int spl_P = 0;                   // number of buckets the stored splitters partition into (0: none yet)

@@ -9,13 +9,20 @@
 // design minimises dependent passes.  Steady state = FOUR launches:
 //
 //   k_loc_count    per tile of 2048 pairs: bucket of every pair (binary search over <= 1023
-//                  splitters in LDS) + LDS histogram, whose atomic's return value is the pair's
-//                  rank inside (tile, bucket); one global atomic per (tile, bucket) reserves the
+//                  splitters in LDS) + LDS histogram; one global atomic per (tile, bucket) reserves the
 //                  run's place inside its bucket — no scan pass: the order of the runs inside a
-//                  bucket is irrelevant, the bucket is sorted next.  Side job: row of every nnz.
+//                  bucket is irrelevant, the bucket is sorted next.  The runs' offsets (run_off) are all it hands on.
 //   k_loc_scatter  bucket starts (block scan of the 1024 totals) + pairs -> bucket-major order.  From here on a pair is
 //                  (key, TAG), tag = pos << tb | row mod 2^tb: tags order like positions, and emit gets the row of a
 //                  pair back from the tag and the CSR offsets instead of gathering it from a 1.5 MB array (LocView::tb).
+//                  Nothing per pair crosses the launch boundary: the bucket comes from count's search run again (same
+//                  splitters, same comparison), the slot inside the (tile, bucket) run from an LDS cursor (any order: the
+//                  bucket is sorted next on the unique (key, tag)), the row from the CSR offsets of the rows that cover the
+//                  tile, staged in LDS.  Until then count wrote bucket << 16 | rank and the row of every position (3 MB, the
+//                  rows as 156 B-strided runs of stores) for scatter to read back: 70 k of the two launches' 245 k
+//                  memory-side requests (profiles/loc_rederive_*).  Measured and not kept: the splitters loaded at the top of
+//                  scatter into LDS of their own (20 KB), beside the scan instead of behind the search of the rows: C3
+//                  87.9-88.1 M against 88.3-88.4 M.
 //                  A bucket's area is filled XCD group by XCD group (LocView::btotal), so that the short runs of the
 //                  tiles running on one XCD merge into whole lines in that XCD's L2.
 //   k_loc_sort     one block per bucket: merge sort by (key, pos) (64-wide runs sorted in registers by a bitonic network over
@@ -73,6 +80,7 @@ constexpr int LOC_MAX_AVG = 700;
 // tests/keyview_ref.py designs its minibatches by the same constants and by LOC_LDS_CAP, and asserts the bucket starts it
 // expects through dfh_batch_get_key_view: a change here shows there as a failed premise)
 constexpr int LOC_LDS_CAP = 1024;      // pairs a bucket may hold to be sorted in LDS
+constexpr int LOC_SCATTER_ROWS = 1024; // rows of a tile whose offsets k_loc_scatter stages in LDS (a tile of more rows searches `offset` itself)
 #ifndef DFH_LOC_TILE_THREADS
 #define DFH_LOC_TILE_THREADS 1024
 #endif
@@ -91,12 +99,11 @@ struct LocView {
   int force_global;       // tests: sort every bucket through the global-memory path
   // The 32-bit tie-break carried through the sort is a TAG: pos << tb | (row of pos) mod 2^tb, tb = clz(N - 1) capped
   // at 16.  Tags order like positions (pos is unique and sits in the high bits), and k_loc_emit gets the row back from the
-  // tag and `offset` (the rows congruent to the low bits: 2 candidates at C3 size) instead of gathering rowid[pos] from
+  // tag and `offset` (the rows congruent to the low bits: 2 candidates at C3 size) instead of gathering the row of pos from
   // a 1.5 MB array that every XCD's L2 fetches for itself (12.5 MB of fabric reads per minibatch).
   int tb;
   uint32_t nrows;
-  const uint32_t* offset; // [nrows + 1] the minibatch's CSR offsets
-  const uint32_t* rowid;  // [N] row of every position: written by k_loc_count, read (coalesced) by k_loc_scatter
+  const uint32_t* offset; // [nrows + 1] the minibatch's CSR offsets: k_loc_scatter finds the row of every position in them
   // bootstrap
   uint64_t* smp_key;      // [P * LOC_OVERSAMPLE] jittered samples of the composite (key, pos)
   uint32_t* smp_pos;
@@ -105,7 +112,6 @@ struct LocView {
   uint64_t* spl_key;      // [P - 1] splitters: bucket b holds composites in [spl[b-1], spl[b])
   uint32_t* spl_pos;
   // per call
-  uint32_t* packed;       // [N] bucket << 16 | rank-in-(tile, bucket)
   uint32_t* run_off;      // [ntiles * P] offset of every (tile, bucket) run inside its bucket
   // [LOC_XCDS][LOC_MAX_BUCKETS] pairs per (XCD group of tiles, bucket); zero between calls (k_loc_sort resets it).
   // A bucket's area is filled XCD group by XCD group: the ~2-pair runs of the tiles that run on one XCD land next to each
@@ -261,7 +267,7 @@ __global__ void __launch_bounds__(256) k_loc_splitters(LocView v) {
 }
 
 // ---------------------------------------------------------------------------------------
-// count: bucket + rank-in-(tile, bucket) of every pair; the tile's runs reserve their places
+// count: the pairs of every (tile, bucket); the tile's runs reserve their places
 // ---------------------------------------------------------------------------------------
 // Device feed (dfh_batch_prepare_rows): the minibatch is DESCRIBED — row numbers into device-resident row buffers (the shuffle
 // buffers of BatchReader, src/reader/batch_reader.cc:29-78), its own offsets and labels, all in page-locked host memory the
@@ -302,7 +308,7 @@ __device__ __forceinline__ T loc_sel(const T (&a)[LOC_GATHER_SEGS], uint32_t sg)
 template <int MAXB>
 constexpr size_t loc_count_smem() { return (size_t)MAXB * 16; }
 template <int MAXB, int THREADS>
-constexpr size_t loc_scatter_smem() { return (size_t)MAXB * 4 + (THREADS / 64) * 4; }
+constexpr size_t loc_scatter_smem() { return (size_t)MAXB * 16; }  // count's tables: the search is count's
 constexpr size_t loc_sort_smem() { return (size_t)LOC_LDS_CAP * 24 + 2 * (LOC_SORT_THREADS / 64) * 4; }
 constexpr size_t loc_emit_smem() { return (2 * (LOC_EMIT_THREADS / 64) + 4) * 4; }
 
@@ -369,23 +375,15 @@ __device__ __forceinline__ void loc_count_block(const LocView& v, const uint32_t
       key[e] = i < v.n ? make_key(v.raw[i], v.max_index) : ~0ULL;
     }
   }
-  // side job, independent of the sort until k_loc_emit: rowid[pos] = row of nnz position pos,
-  // this block's share of the rows
-  {
-    uint32_t* __restrict__ rowid = const_cast<uint32_t*>(v.rowid);
-    // (gathering: the minibatch's offsets and labels arrive in HBM by this pass too — another block's share, so they are read
-    // where the host wrote them)
-    const uint32_t* __restrict__ offset = GATHER ? gp->h_off : v.offset;
+  if (GATHER) {
+    // the minibatch's offsets and labels arrive in HBM by this pass too, this block's share of the rows — another block's
+    // tile, so they are read where the host wrote them
     const uint32_t rpb = (v.nrows + nblk - 1) / nblk;
     const uint32_t r0 = bid * rpb, r1 = min(v.nrows, r0 + rpb);
     for (uint32_t r = r0 + threadIdx.x; r < r1; r += THREADS) {
-      const uint32_t b0 = offset[r], e = offset[r + 1];
-      if (GATHER) {
-        gp->dst_off[r] = b0;
-        gp->dst_lab[r] = gp->h_lab[r];
-        if (r + 1 == v.nrows) gp->dst_off[r + 1] = e;
-      }
-      for (uint32_t j = b0; j < e; ++j) rowid[j] = r;
+      gp->dst_off[r] = gp->h_off[r];
+      gp->dst_lab[r] = gp->h_lab[r];
+      if (r + 1 == v.nrows) gp->dst_off[r + 1] = gp->h_off[r + 1];
     }
   }
   __syncthreads();
@@ -399,8 +397,8 @@ __device__ __forceinline__ void loc_count_block(const LocView& v, const uint32_t
       if (lo[e] < hi[e]) {
         const uint32_t i = base + e * THREADS + threadIdx.x;
         const int mid = (lo[e] + hi[e]) >> 1;
-        // the pair's own row bits are not known here (another block writes rowid[i]); they only matter for the pair
-        // that IS a splitter, and that one may fall on either side of it
+        // the tag without its row bits: they only matter for the pair that IS a splitter, and that one may fall on either
+        // side of it — k_loc_scatter repeats this very comparison, so both passes put it on the same side
         if (comp_less(key[e], i << v.tb, sk[mid], sp[mid])) hi[e] = mid; else lo[e] = mid + 1;
       }
     }
@@ -408,10 +406,7 @@ __device__ __forceinline__ void loc_count_block(const LocView& v, const uint32_t
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     const uint32_t i = base + e * THREADS + threadIdx.x;
-    if (i < v.n) {
-      const uint32_t r = atomicAdd(&hist[lo[e]], 1u);
-      v.packed[i] = ((uint32_t)lo[e] << 16) | r;
-    }
+    if (i < v.n) atomicAdd(&hist[lo[e]], 1u);
   }
   __syncthreads();
   // one global atomic per non-empty (tile, bucket) run: its offset inside the bucket.  The order in
@@ -450,7 +445,7 @@ __global__ void __launch_bounds__(LOC_TILE_THREADS) k_loc_count_gather(LocView v
 // Binary values: whether the minibatch gets a value array is decided as for a described minibatch — it has one iff one of
 // the buffers it names has one (dfh_rowbuf::has_value, fixed when the buffer was uploaded); rows of a buffer without values
 // are gathered as ones.  Nothing of that depends on this kernel.
-// Registers: 13 VGPRs, 26 SGPRs, no scratch, 16 B of LDS (the count pass: 18 VGPRs, 20 when it gathers).
+// Registers: 13 VGPRs, 26 SGPRs, no scratch, 16 B of LDS (the count pass: 18 VGPRs, gathering or not).
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(LOC_DESC_ROWS) k_loc_describe(const uint32_t* __restrict__ src_off, const float* __restrict__ src_lab,
                                                                 const uint32_t* __restrict__ h_rows, const uint32_t* __restrict__ h_base,
@@ -479,11 +474,33 @@ __device__ __forceinline__ void loc_scatter_block(const LocView& v, const uint32
   constexpr int PER = LOC_TILE / THREADS;
   constexpr int LOC_BPT = MAXB / THREADS;  // buckets per thread in the scan of the bucket totals
   static_assert(LOC_BPT * THREADS == MAXB, "the scan of the bucket totals gives every thread the same number of buckets");
-  uint32_t* off = reinterpret_cast<uint32_t*>(smem);
-  uint32_t* wsum = off + MAXB;
+  static_assert((size_t)(THREADS / 64 + 1 + LOC_SCATTER_ROWS) * 4 <= (size_t)MAXB * 12, "the rows' offsets fit where the splitters go");
+  // LDS: splitters (keys, tags) and the write cursor of every bucket.  The scan's wave sums and the offsets of the tile's rows
+  // are done with before the splitters are loaded and lie in their place (the large size class fills its 64 KB with the three
+  // tables alone)
+  uint64_t* sk = reinterpret_cast<uint64_t*>(smem);
+  uint32_t* sp = reinterpret_cast<uint32_t*>(smem + (size_t)MAXB * 8);
+  uint32_t* off = sp + MAXB;
+  uint32_t* wsum = reinterpret_cast<uint32_t*>(smem);
+  uint32_t* nr_s = wsum + THREADS / 64;  // rows staged for the tile (0: more than the staging area holds)
+  uint32_t* roff = nr_s + 1;             // [LOC_SCATTER_ROWS] offsets of the rows from the tile's first on
   const int P = v.P;
   const uint32_t xcd = bid & (LOC_XCDS - 1);
   const uint32_t base = bid * LOC_TILE;
+  const uint32_t last = min(base + (uint32_t)LOC_TILE, v.n) - 1u;  // the tile's last position
+  if (threadIdx.x == 0) *nr_s = 0u;
+  // the tile's first row: the last row that starts at or before `base`, one 64-way search of `offset` per wave (every lane
+  // probes the start of its share of the candidate rows [row0, row0 + cnt); offsets ascend, so the lanes whose share starts
+  // at or before `base` are a prefix, counted by a ballot: three dependent loads for 8 192 rows where a binary search has 13)
+  uint32_t row0 = 0;
+  for (uint32_t cnt = v.nrows; cnt > 1u;) {
+    const uint32_t step = (cnt + 63u) >> 6;
+    const uint32_t q = (threadIdx.x & 63u) * step;
+    const bool ok = q < cnt && v.offset[row0 + min(q, cnt - 1u)] <= base;
+    const uint32_t k = max(1u, (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ok))) - 1u;  // (lane 0: offset[row0] <= base)
+    row0 += k * step;
+    cnt = min(step, cnt - k * step);
+  }
   // exclusive scan of the bucket totals: LOC_BPT consecutive buckets per thread
   const int b0 = threadIdx.x * LOC_BPT;
   uint32_t tt[LOC_BPT], ro[LOC_BPT];
@@ -516,24 +533,89 @@ __device__ __forceinline__ void loc_scatter_block(const LocView& v, const uint32
     ex += tt[q];
   }
   if (bid == 0 && threadIdx.x == 0) v.bstart[P] = total;
-  // the tile's pairs are loaded only now: held across the scan they kept the kernel above 32 registers
-  uint64_t raw[PER];
-  uint32_t pk[PER], rw[PER];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) {
-    const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1);  // clamped: the loads stay unconditional
-    raw[e] = v.raw[i];
-    pk[e] = v.packed[i];
-    rw[e] = v.rowid[i];
+  // the rows that cover the tile, from its first row on: their offsets into LDS.  The row that holds the tile's last
+  // position says how many of them there are; if it lies beyond the staging area nobody does, and the pairs search `offset`
+  for (uint32_t q = threadIdx.x; q < (uint32_t)LOC_SCATTER_ROWS; q += THREADS) {
+    const uint32_t r = row0 + q;
+    if (r < v.nrows) {
+      const uint32_t a = v.offset[r], b = v.offset[r + 1];
+      roff[q] = a;
+      if (a <= last && b > last) *nr_s = q + 1u;
+    }
   }
   __syncthreads();
+  // the row of every pair: the last row that starts at or before its position (rows without nonzeros share their
+  // successor's offset), kept as the tag's low bits
+  const uint32_t nr = (uint32_t)__builtin_amdgcn_readfirstlane((int)*nr_s);
+  uint32_t rb[PER];
+  {
+    uint32_t lo[PER], hi[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      lo[e] = nr ? 0u : row0;
+      hi[e] = nr ? nr - 1u : v.nrows - 1u;
+    }
+    if (nr) {
+      for (uint32_t step = nr; step > 1u; step = (step + 1u) >> 1) {  // ceil(log2 nr) rounds, PER searches interleaved
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+          if (lo[e] < hi[e]) {
+            const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1u);
+            const uint32_t mid = (lo[e] + hi[e] + 1u) >> 1;
+            if (roff[mid] <= i) lo[e] = mid; else hi[e] = mid - 1u;
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < PER; ++e) {
+        const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1u);
+        while (lo[e] < hi[e]) {
+          const uint32_t mid = (lo[e] + hi[e] + 1u) >> 1;
+          if (v.offset[mid] <= i) lo[e] = mid; else hi[e] = mid - 1u;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < PER; ++e) rb[e] = ((nr ? row0 : 0u) + lo[e]) & ((1u << v.tb) - 1u);
+  }
+  __syncthreads();  // the rows' offsets are done with: the splitters take their place
+  for (int b = threadIdx.x; b < P; b += THREADS) {
+    sk[b] = b < P - 1 ? v.spl_key[b] : ~0ULL;  // spl[P-1] = +inf
+    sp[b] = b < P - 1 ? v.spl_pos[b] : ~0u;
+  }
+  // the tile's pairs are loaded only now: held across the scan they kept the kernel above 32 registers
+  uint64_t key[PER];
+#pragma unroll
+  for (int e = 0; e < PER; ++e) {
+    const uint32_t i = min(base + e * THREADS + threadIdx.x, v.n - 1u);  // clamped: the loads stay unconditional
+    key[e] = make_key(v.raw[i], v.max_index);
+  }
+  __syncthreads();
+  // the bucket of every pair: k_loc_count's search over again, comparison for comparison — first b with (key, i) < spl[b] —
+  // so that a pair is written into the bucket it was counted in
+  int lo[PER], hi[PER];
+#pragma unroll
+  for (int e = 0; e < PER; ++e) { lo[e] = 0; hi[e] = P - 1; }
+  for (int step = P; step > 1; step = (step + 1) >> 1) {
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      if (lo[e] < hi[e]) {
+        const uint32_t i = base + e * THREADS + threadIdx.x;
+        const int mid = (lo[e] + hi[e]) >> 1;
+        if (comp_less(key[e], i << v.tb, sk[mid], sp[mid])) hi[e] = mid; else lo[e] = mid + 1;
+      }
+    }
+  }
+  // the pair's slot inside its (tile, bucket) run: dealt out by the bucket's cursor in whatever order the lanes arrive — the
+  // bucket is sorted next on the unique composite (key, tag)
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     const uint32_t i = base + e * THREADS + threadIdx.x;
     if (i < v.n) {
-      const uint32_t dst = off[pk[e] >> 16] + (pk[e] & 0xFFFFu);
-      v.bkeys[dst] = make_key(raw[e], v.max_index);
-      v.bpos[dst] = (i << v.tb) | (rw[e] & ((1u << v.tb) - 1u));
+      const uint32_t dst = atomicAdd(&off[lo[e]], 1u);
+      v.bkeys[dst] = key[e];
+      v.bpos[dst] = (i << v.tb) | rb[e];
     }
   }
 }

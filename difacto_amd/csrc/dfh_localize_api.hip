@@ -82,13 +82,11 @@ int localize_impl(dfh_batch* b, uint64_t max_index, dfh_table* probe) {
     v.tb = N > 1 ? std::min(16, __builtin_clz(N - 1)) : 16;  // (N - 1) << tb fits 32 bits
     v.nrows = (uint32_t)b->nrows;
     v.offset = b->d_offset;
-    v.rowid = b->d_pos;
     v.smp_key = b->d_smp_key;
     v.smp_pos = b->d_smp_pos;
     v.smp_rank = b->d_smp_rank;
     v.spl_key = b->d_spl_key;
     v.spl_pos = b->d_spl_pos;
-    v.packed = b->d_packed;
     v.run_off = b->d_run_off;
     v.btotal = b->d_btotal;
     v.bstart = b->d_bstart;
