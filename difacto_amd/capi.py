@@ -47,6 +47,7 @@ SYMBOLS = [
     "dfh_rowbuf_load_slices",
     "dfh_lz4_compress", "dfh_crb_create", "dfh_crb_destroy", "dfh_crb_encode_host", "dfh_crb_encode_textchunk", "dfh_crb_record",
     "dfh_eval_create", "dfh_eval_destroy", "dfh_eval_reset", "dfh_eval_append_batch", "dfh_eval_append_host", "dfh_eval_finish",
+    "dfh_eval_group_by_slot", "dfh_eval_append_host_groups", "dfh_eval_finish_groups", "dfh_eval_read_groups",
     "dfh_predtext_create", "dfh_predtext_destroy", "dfh_predtext_reset", "dfh_predtext_append_batch", "dfh_predtext_append_host",
     "dfh_predtext_count", "dfh_predtext_values", "dfh_predtext_format", "dfh_predtext_read", "dfh_predtext_tile",
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
@@ -82,6 +83,12 @@ class EvalResult(C.Structure):
     """dfh_eval_result: the exact whole-set metrics (auc2 = 2 x pairs ranked right + tied pairs)"""
     _fields_ = [("n", C.c_uint64), ("n_pos", C.c_uint64), ("n_neg", C.c_uint64), ("n_nan", C.c_uint64), ("auc2", C.c_uint64),
                 ("correct", C.c_uint64), ("objv", C.c_double)]
+
+
+class EvalGroupsResult(C.Structure):
+    """dfh_eval_groups_result: the summary over the groups (gAUC = gauc_num / rows_mixed)"""
+    _fields_ = [("n_groups", C.c_uint64), ("n_mixed", C.c_uint64), ("rows_mixed", C.c_uint64), ("n_nogroup", C.c_uint64),
+                ("gauc_num", C.c_double)]
 
 
 class Slice(C.Structure):
@@ -223,6 +230,10 @@ def lib():
     L.dfh_eval_append_batch.argtypes = [vp, vp]
     L.dfh_eval_append_host.argtypes = [vp, vp, vp, sz]
     L.dfh_eval_finish.argtypes = [vp, PP(EvalResult)]
+    L.dfh_eval_group_by_slot.argtypes = [vp, C.c_int]
+    L.dfh_eval_append_host_groups.argtypes = [vp, vp, vp, vp, vp, sz]
+    L.dfh_eval_finish_groups.argtypes = [vp, PP(EvalGroupsResult)]
+    L.dfh_eval_read_groups.argtypes = [vp, C.c_uint64, C.c_uint64] + [vp] * 7
     L.dfh_predtext_create.argtypes = [vp, sz, PP(vp)]
     L.dfh_predtext_destroy.argtypes = [vp]
     L.dfh_predtext_reset.argtypes = [vp]
@@ -883,6 +894,35 @@ class Eval:
         r = EvalResult()
         _ck(lib().dfh_eval_finish(self.h, C.byref(r)))
         return r
+
+    GROUP_FIELDS = ("gid", "n", "n_pos", "n_nan", "auc2", "correct", "objv")
+
+    def group_by_slot(self, slot):
+        """-1: off; 0 .. 4095: rows carry a group (append_batch: the id of the first feature of that slot); empty evaluator only"""
+        _ck(lib().dfh_eval_group_by_slot(self.h, slot))
+
+    def append_host_groups(self, label, pred, gid, has_group=None):
+        label = np.ascontiguousarray(label, np.float32)
+        pred = np.ascontiguousarray(pred, np.float32)
+        gid = np.ascontiguousarray(gid, np.uint64)
+        assert label.shape == pred.shape == gid.shape and label.ndim == 1
+        if has_group is not None:
+            has_group = np.ascontiguousarray(has_group, np.uint8)
+            assert has_group.shape == label.shape
+        _ck(lib().dfh_eval_append_host_groups(self.h, _p(label), _p(pred), _p(gid), None if has_group is None else _p(has_group),
+                                              label.size))
+
+    def finish_groups(self):
+        """-> EvalGroupsResult; the per-group records stay on the device for read_groups (waits; nothing is consumed)"""
+        r = EvalGroupsResult()
+        _ck(lib().dfh_eval_finish_groups(self.h, C.byref(r)))
+        return r
+
+    def read_groups(self, first, count):
+        """records [first, first + count) of the last finish_groups, in ascending id -> {field: array}"""
+        out = {f: np.empty(count, np.float64 if f == "objv" else np.uint64) for f in self.GROUP_FIELDS}
+        _ck(lib().dfh_eval_read_groups(self.h, first, count, *[_p(out[f]) for f in self.GROUP_FIELDS]))
+        return out
 
     def close(self):
         if self.h:

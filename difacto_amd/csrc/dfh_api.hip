@@ -49,6 +49,7 @@ using namespace dfh;
 #include "dfh_owlqn.hip"         // l1 on w for learner = lbfgs, the orthant-wise forms of its vector passes: dfh_lbfgs.hip
 #include "dfh_bcd.hip"           // learner = bcd: the chunk set, the join, the communicator
 #include "dfh_eval.hip"          // whole-set evaluation, exact AUC, logloss and accuracy of the appended rows: the handles
+#include "dfh_eval_groups.hip"   // the same rows by group, per-group records and the grouped AUC: the evaluator, the batch's step
 #include "dfh_predtext.hip"      // prediction text, the bytes of fprintf("%.9g\n") for the appended values: the handles
 #include "dfh_dumptext.hip"      // a model table as sorted text, "<id>\t<w>[\t<V_j>]" per kept entry: the table calls, dfh_predtext_fmt.h
 #include "dfh_pairs.hip"         // each entry's top-k FM interaction partners, a blocked V V^T on MFMA that is never stored: the dump's entries

@@ -21,7 +21,7 @@
 // Everything between two launches is ordered by the stream alone: no block waits on another block, there are no floating-point
 // atomics (no atomics at all), and a reduction's order is a function of n only — the same appended sequence gives the same
 // bits in every field on every run, however it was cut into appends.  Vector stores and plain C++ only.  These kernels are not
-// in the timing registry (dfh_kernel_name) and no launch of a step changes.
+// in the timing registry (dfh_kernel_name) and no launch of a step changes.  The same rows BY GROUP: dfh_eval_groups.hip.
 struct dfh_eval {
   dfh_ctx* ctx = nullptr;
   float* d_pred = nullptr;    // [cap] the appended rows
@@ -31,6 +31,15 @@ struct dfh_eval {
   // finish's workspace, grown to what a finish needs, kept
   char* d_work = nullptr;
   size_t work_bytes = 0;
+  // by group (dfh_eval_groups.hip).  slot >= 0: every row held has a group id and a has-group byte beside it
+  int slot = -1;
+  uint64_t* d_gid = nullptr;   // [gcap]
+  uint8_t* d_has = nullptr;
+  size_t gcap = 0;
+  char* d_gpre = nullptr;      // finish_groups: the rows with a group per tile of appended rows, and their prefix
+  size_t gpre_bytes = 0;
+  char* d_rec = nullptr;       // the records of the last finish_groups, rec_n per field
+  size_t rec_bytes = 0, rec_n = 0;
 };
 
 namespace {
@@ -285,6 +294,11 @@ __global__ void __launch_bounds__(256) k_eval_final(const uint64_t* __restrict__
   }
 }
 
+// dfh_eval_groups.hip
+int gv_reserve(dfh_eval* e, size_t extra);
+int gv_rowgroup(dfh_eval* e, dfh_batch* b, size_t at);
+void gv_free(dfh_eval* e);
+
 inline size_t ev_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 void ev_free_retired(dfh_eval* e) {
@@ -360,6 +374,7 @@ int dfh_eval_destroy(dfh_eval* e) {
   if (e->d_pred) (void)hipFree(e->d_pred);
   if (e->d_label) (void)hipFree(e->d_label);
   if (e->d_work) (void)hipFree(e->d_work);
+  gv_free(e);
   delete e;
   return DFH_OK;
 }
@@ -378,8 +393,26 @@ int dfh_eval_append_batch(dfh_eval* e, dfh_batch* b) {
   // written by the batch object's NEXT load, on a preparation stream that waits for ev_free alone — and the step has
   // recorded ev_free already (main_end).  So, with pipelining on, ev_free is recorded again behind the copies: the next load
   // (prep_begin) waits for the latest record.  Call it before the next minibatch is loaded into the batch object.
-  const int rc = ev_append(e, b->d_label, b->d_pred, b->nrows, hipMemcpyDeviceToDevice);
+  const size_t at = e->n;
+  if (e->slot >= 0) {   // by group: the ids are read out of what the step left in the batch object
+    if (!b->stepped) {
+      set_error("dfh_eval_append_batch: with a group slot set the batch must have been stepped (dfh_sgd_step) since its load: the "
+                "rows' groups are read from its localized ids");
+      return DFH_ERR_STATE;
+    }
+    DFH_HIP(hipSetDevice(e->ctx->device));
+    const int rg = gv_reserve(e, b->nrows);
+    if (rg) return rg;
+  }
+  int rc = ev_append(e, b->d_label, b->d_pred, b->nrows, hipMemcpyDeviceToDevice);
   if (rc) return rc;
+  if (e->slot >= 0) {
+    rc = gv_rowgroup(e, b, at);
+    if (rc) {
+      e->n = at;   // the rows are not kept without their groups
+      return rc;
+    }
+  }
   if (b->nrows && e->ctx->pipeline) {
     DFH_HIP(hipEventRecord(b->ev_free, e->ctx->stream));
     b->free_pending = true;
@@ -391,6 +424,10 @@ int dfh_eval_append_host(dfh_eval* e, const float* label, const float* pred, siz
   DFH_ARG(e, "dfh_eval_append_host: NULL argument");
   DFH_ARG(n < EV_MAX_ROWS && e->n + (uint64_t)n < EV_MAX_ROWS, "dfh_eval_append_host: an evaluator holds fewer than 2^32 - 16 rows");
   DFH_ARG(n == 0 || (label && pred), "dfh_eval_append_host: NULL argument");
+  if (e->slot >= 0) {
+    set_error("dfh_eval_append_host: a group slot is set, these rows would have no group ids; use dfh_eval_append_host_groups");
+    return DFH_ERR_STATE;
+  }
   const int rc = ev_append(e, label, pred, n, hipMemcpyHostToDevice);
   if (rc) return rc;
   DFH_HIP(hipStreamSynchronize(e->ctx->stream));   // the caller's arrays are free on return

@@ -71,6 +71,16 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
         << "exact_metrics=1 with task=train and no data_val: there is nothing to evaluate; name a validation file with "
            "data_val=<file>, or leave exact_metrics out";
   }
+  // exact_metrics_group: the same
+  CHECK(param_.exact_metrics_group >= -1 && param_.exact_metrics_group <= 4095)
+      << "exact_metrics_group=" << param_.exact_metrics_group << " is not one of -1 (off, the default) and 0 .. 4095, the low 12 "
+         "bits of the ids that name a row's group";
+  CHECK(param_.exact_metrics_group < 0 || param_.exact_metrics == 1)
+      << "exact_metrics_group=" << param_.exact_metrics_group << " without exact_metrics=1: the groups are those of the rows the "
+         "whole-set evaluation keeps on the device; add exact_metrics=1, or leave exact_metrics_group out";
+  CHECK(param_.exact_metrics_group_out.empty() || param_.exact_metrics_group >= 0)
+      << "exact_metrics_group_out without exact_metrics_group: there are no groups to write; name the slot with "
+         "exact_metrics_group=<0 .. 4095>, or leave exact_metrics_group_out out";
   // pred_write: checked before anything touches the device, like data_cache
   CHECK(param_.pred_write == "host" || param_.pred_write == "device")
       << "pred_write=" << param_.pred_write << " is not one of host (the default) and device";
@@ -254,6 +264,7 @@ void SGDLearner::RunEpoch(int epoch, int job_type, sgd::Progress* prog) {
   if (exact) {
     if (!eval_) DFH_CALL(dfh_eval_create(DeviceContext::Get(), 0, &eval_));
     DFH_CALL(dfh_eval_reset(eval_));
+    if (param_.exact_metrics_group >= 0) DFH_CALL(dfh_eval_group_by_slot(eval_, param_.exact_metrics_group));
   }
   tracker_->Issue(jobs);
   while (tracker_->NumRemains()) std::this_thread::sleep_for(std::chrono::microseconds(200));
@@ -280,6 +291,54 @@ void SGDLearner::LogExactMetrics(const char* what) {
   }
   LOG(INFO) << what << "rows=" << r.n << " pos=" << r.n_pos << " neg=" << r.n_neg << " nan=" << r.n_nan << " auc2=" << r.auc2
             << " auc=" << num[0] << " logloss=" << num[1] << " accuracy=" << num[2];
+  if (param_.exact_metrics_group >= 0) LogGroupMetrics(what);
+}
+
+// exact_metrics_group: the summary as one more log line; exact_metrics_group_out: the records come down a block at a time and
+// are formatted here, one line per group in ascending id
+void SGDLearner::LogGroupMetrics(const char* what) {
+  dfh_eval_groups_result g;
+  DFH_CALL(dfh_eval_finish_groups(CHECK_NOTNULL(eval_), &g));
+  char gauc[40];
+  if (g.rows_mixed) {
+    snprintf(gauc, sizeof(gauc), "%.17g", g.gauc_num / static_cast<double>(g.rows_mixed));
+  } else {
+    snprintf(gauc, sizeof(gauc), "undefined");
+  }
+  LOG(INFO) << what << "groups=" << g.n_groups << " mixed=" << g.n_mixed << " rows_mixed=" << g.rows_mixed
+            << " nogroup=" << g.n_nogroup << " gauc=" << gauc;
+  if (param_.exact_metrics_group_out.empty()) return;
+  const std::string& path = param_.exact_metrics_group_out;
+  FILE* f = fopen(path.c_str(), "w");
+  CHECK(f) << "cannot open " << path << " for writing";
+  const uint64_t kBlock = 1 << 16;
+  std::vector<uint64_t> u(6 * kBlock);
+  std::vector<double> objv(kBlock);
+  for (uint64_t first = 0; first < g.n_groups; first += kBlock) {
+    const uint64_t cnt = std::min<uint64_t>(kBlock, g.n_groups - first);
+    uint64_t *gid = u.data(), *n = gid + kBlock, *pos = n + kBlock, *nan = pos + kBlock, *auc2 = nan + kBlock, *cor = auc2 + kBlock;
+    DFH_CALL(dfh_eval_read_groups(eval_, first, cnt, gid, n, pos, nan, auc2, cor, objv.data()));
+    for (uint64_t i = 0; i < cnt; ++i) {
+      const uint64_t rows = n[i] - nan[i], neg = rows - pos[i];
+      char num[3][40];
+      if (pos[i] && neg) {
+        snprintf(num[0], sizeof(num[0]), "%.17g", static_cast<double>(auc2[i]) / (2.0 * pos[i] * neg));
+      } else {
+        snprintf(num[0], sizeof(num[0]), "undefined");
+      }
+      if (rows) {
+        snprintf(num[1], sizeof(num[1]), "%.17g", objv[i] / rows);
+        snprintf(num[2], sizeof(num[2]), "%.17g", static_cast<double>(cor[i]) / rows);
+      } else {
+        snprintf(num[1], sizeof(num[1]), "undefined");
+        snprintf(num[2], sizeof(num[2]), "undefined");
+      }
+      CHECK_GT(fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\t%s\t%s\n", (unsigned long long)gid[i], (unsigned long long)n[i],
+                       (unsigned long long)pos[i], (unsigned long long)neg, (unsigned long long)nan[i],
+                       (unsigned long long)auc2[i], num[0], num[1], num[2]), 0) << "cannot write " << path;
+    }
+  }
+  CHECK_EQ(fclose(f), 0) << "cannot write " << path;
 }
 
 // task = predict (src/main.cc:61-62 is a TODO in the reference; sgd_param.h:24-28: "model_in ... should be specified if it

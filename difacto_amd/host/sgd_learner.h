@@ -78,6 +78,8 @@ class SGDLearner : public Learner {
   const std::string& JobFormat() const;
   /*! \brief exact_metrics = 1: the whole-set figures of the pass that has just ended, as one log line behind `what` */
   void LogExactMetrics(const char* what);
+  /*! \brief exact_metrics_group: the summary over the groups as one more log line, the table to exact_metrics_group_out */
+  void LogGroupMetrics(const char* what);
   /*! \brief the data a job reads: data_in for training, data_val for validation, either for prediction */
   const std::string& JobData(const sgd::Job& job) const;
   void IterateData(const sgd::Job& job, sgd::Progress* prog);

@@ -43,6 +43,12 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   // exact_metrics = 1 (a key of this build): validation epochs and task = predict keep every prediction and label on the device
   // and report the exact AUC, logloss and accuracy of the whole set in one more log line (dfh_eval); nothing else changes
   int exact_metrics;         // 0 (default) | 1
+  // exact_metrics_group (keys of this build; with exact_metrics = 1): a row's GROUP is the id of its first feature whose id has
+  // this value in its low 12 bits (the feature group of the criteo and adfea formats: a user, a site, a campaign).  One more
+  // log line reports the groups and the grouped AUC (the row-weighted mean of the AUC inside each group that has both labels);
+  // exact_metrics_group_out gets one line per group after each evaluated pass, the last pass wins (csrc/dfh_eval_groups.hip)
+  int exact_metrics_group;              // -1 (default: nothing new runs) | 0 .. 4095
+  std::string exact_metrics_group_out;  // "" | the file
   // explain_out (keys of this build; task = predict, one process, the fused loop, V_dim > 0): one more line per data row, in
   // file order like pred_out: "<inter>" and "\t<id_i>:<id_j>:<c>" per pair — the explain_topk pairs of the row's features with
   // the largest contribution c = x_i x_j <V_i, V_j> to its logit, and inter = the sum over all of its pairs
@@ -67,6 +73,8 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
     DMLC_DECLARE_FIELD(data_cache).set_default("");
     DMLC_DECLARE_FIELD(data_cache_max_gb).set_default(0);
     DMLC_DECLARE_FIELD(exact_metrics).set_default(0);
+    DMLC_DECLARE_FIELD(exact_metrics_group).set_default(-1);
+    DMLC_DECLARE_FIELD(exact_metrics_group_out).set_default("");
     DMLC_DECLARE_FIELD(explain_out).set_default("");
     DMLC_DECLARE_FIELD(explain_topk).set_default(10);
     DMLC_DECLARE_FIELD(explain_by).set_default("abs");

@@ -856,6 +856,41 @@ int dfh_eval_append_batch(dfh_eval* e, dfh_batch* b);
 int dfh_eval_append_host(dfh_eval* e, const float* label, const float* pred, size_t n);
 int dfh_eval_finish(dfh_eval* e, dfh_eval_result* out);
 
+/* ------------------------------------------------ whole-set evaluation by group (exact_metrics_group) */
+/* The same evaluator keeps one optional 64-bit GROUP id per row (a user, a site, a campaign; 9 B more per row) and reports the
+ * fields of dfh_eval_result for every distinct id, over that id's rows alone, and the grouped AUC of the set
+ * (csrc/dfh_eval_groups.hip).  Rows without a group are counted in n_nogroup and belong to no group; dfh_eval_finish covers
+ * every row and returns the bits it returns with grouping off.
+ *   - per group n, n_pos, n_nan, auc2, correct, objv follow dfh_eval_result's rules (n_neg = n - n_pos - n_nan); auc2 counts the
+ *     pairs of a positive and a negative OF THE GROUP, exact; objv is summed in fp64 in a fixed order
+ *   - a group is MIXED when n_pos > 0 and n_neg > 0;  gAUC = gauc_num / rows_mixed (undefined when rows_mixed = 0) with
+ *     gauc_num = the sum over the mixed groups, in ascending id in a fixed order, of (n_pos + n_neg) auc2 / (2 n_pos n_neg)
+ *   - the same appended sequence gives the same bits in every field on every run, however it was cut into appends
+ * dfh_eval_group_by_slot: slot = -1 (off, the default) or 0 .. 4095; legal only while the evaluator holds no rows
+ * (DFH_ERR_STATE otherwise); dfh_eval_reset keeps it.  With a slot set, dfh_eval_append_batch also stores the rows' groups: a
+ * row's group is the id of its FIRST position whose id has (id & 4095) == slot, the id being reverse_bytes(feaids[index[j]]) as
+ * task = dump prints it (the low 12 bits are the feature group of the criteo and adfea formats); a row with no such position
+ * has no group.  The ids are read from what the batch's last step left on the device, so the batch must have been stepped
+ * since its load (DFH_ERR_STATE otherwise); dfh_eval_append_host is refused (DFH_ERR_STATE).
+ * dfh_eval_append_host_groups takes host arrays and needs grouping on (any slot; DFH_ERR_STATE otherwise); has_group is a byte
+ * per row (nonzero: gid[i] is the row's group), NULL: every row has a group.  Every 64-bit value is an id.
+ * dfh_eval_finish_groups waits, changes nothing that was appended and leaves the records in device memory;
+ * dfh_eval_read_groups copies records [first, first + count) of the last dfh_eval_finish_groups, in ascending id; any pointer
+ * may be NULL; first + count beyond n_groups is DFH_ERR_ARG.  Limits and errors as above. */
+typedef struct {
+  uint64_t n_groups;     /* distinct ids                                           */
+  uint64_t n_mixed;      /* groups with n_pos > 0 and n_neg > 0                    */
+  uint64_t rows_mixed;   /* the sum of n_pos + n_neg over the mixed groups         */
+  uint64_t n_nogroup;    /* rows without a group                                   */
+  double   gauc_num;     /* gAUC = gauc_num / rows_mixed                           */
+} dfh_eval_groups_result;
+int dfh_eval_group_by_slot(dfh_eval* e, int slot);
+int dfh_eval_append_host_groups(dfh_eval* e, const float* label, const float* pred, const uint64_t* gid, const uint8_t* has_group,
+                                size_t n);
+int dfh_eval_finish_groups(dfh_eval* e, dfh_eval_groups_result* out);
+int dfh_eval_read_groups(dfh_eval* e, uint64_t first, uint64_t count, uint64_t* gid, uint64_t* n, uint64_t* n_pos, uint64_t* n_nan,
+                         uint64_t* auc2, uint64_t* correct, double* objv);
+
 /* ------------------------------------------------ prediction text (pred_write = device) */
 /* A dfh_predtext keeps every value appended since the last reset in device memory (4 B per value; the array grows by doubling,
  * earlier content survives) and turns them into the text fprintf("%.9g\n", v) writes for each, byte for byte, concatenated in
