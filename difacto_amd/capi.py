@@ -53,9 +53,10 @@ SYMBOLS = [
     "dfh_batch_key_view_info", "dfh_batch_get_key_view",
     "dfh_dump_open", "dfh_dump_close", "dfh_dump_shape", "dfh_dump_format", "dfh_dump_read", "dfh_dump_entries", "dfh_dump_ids", "dfh_dump_tile", "dfh_dump_pairs",
     "dfh_explain_create", "dfh_explain_destroy", "dfh_explain_reset", "dfh_explain_append_batch", "dfh_explain_count", "dfh_explain_read",
-    "dfh_explain_read_positions",
+    "dfh_explain_read_positions", "dfh_explain_format", "dfh_explain_read_text", "dfh_explain_text_nonfinite", "dfh_explain_text_tile",
     "dfh_recommend_create", "dfh_recommend_destroy", "dfh_recommend_reset", "dfh_recommend_add_items", "dfh_recommend_item_count",
     "dfh_recommend_append_batch", "dfh_recommend_count", "dfh_recommend_read",
+    "dfh_recommend_format", "dfh_recommend_read_text", "dfh_recommend_text_nonfinite", "dfh_recommend_text_tile",
     "dfh_rowstore_create", "dfh_rowstore_destroy", "dfh_rowstore_append_host", "dfh_rowstore_append_textchunk", "dfh_rowstore_shape",
     "dfh_rowstore_order", "dfh_rowstore_get_order", "dfh_rowstore_read", "dfh_crb_encode_rowstore",
 ]
@@ -268,6 +269,11 @@ def lib():
     L.dfh_recommend_append_batch.argtypes = [vp, vp, vp]
     L.dfh_recommend_count.argtypes = [vp, PP(C.c_uint64)]
     L.dfh_recommend_read.argtypes = [vp, vp, vp, vp, PP(C.c_uint64)]
+    for name in ("dfh_explain", "dfh_recommend"):
+        getattr(L, name + "_format").argtypes = [vp, PP(sz), PP(C.c_uint64)]
+        getattr(L, name + "_read_text").argtypes = [vp, vp]
+        getattr(L, name + "_text_nonfinite").argtypes = [vp, PP(C.c_uint64)]
+        getattr(L, name + "_text_tile").argtypes = [vp]
     L.dfh_rowbuf_load_slices.argtypes = [vp, sz, vp, i32, PP(Slice)]
     L.dfh_batch_gather_rows.argtypes = [vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.dfh_batch_prepare_rows.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_uint64]
@@ -994,6 +1000,33 @@ DUMP_IDS_FEATURE, DUMP_IDS_KEY = 0, 1
 PAIRS_ABS, PAIRS_POS = 0, 1
 
 
+class _ListText:
+    """the lines of an Explain or a Recommend formatted on the device (dfh_explain_format / dfh_recommend_format and their kin)"""
+    _c = None   # "dfh_explain" / "dfh_recommend"
+
+    @property
+    def text_tile(self):
+        """the rows a block of the format kernels takes (by topk)"""
+        return int(getattr(lib(), self._c + "_text_tile")(self.h))
+
+    def format(self):
+        """-> (text bytes, irregular) of everything appended since the last reset (waits; nothing is consumed).  The text is
+        valid when irregular == 0, else it is b'' and the caller formats read() itself"""
+        nb, irr = C.c_size_t(0), C.c_uint64(0)
+        _ck(getattr(lib(), self._c + "_format")(self.h, C.byref(nb), C.byref(irr)))
+        if irr.value or nb.value == 0:
+            return b"", irr.value
+        buf = C.create_string_buffer(nb.value)
+        _ck(getattr(lib(), self._c + "_read_text")(self.h, buf))
+        return buf.raw, irr.value
+
+    def text_nonfinite(self):
+        """read()'s nonfinite as the last format read it back (no wait)"""
+        nf = C.c_uint64(0)
+        _ck(getattr(lib(), self._c + "_text_nonfinite")(self.h, C.byref(nf)))
+        return nf.value
+
+
 class ModelDump:
     """a table's kept entries in ascending order of their printed id, and their text "<id>\\t<w>[\\t<V_j>]\\n" formatted on the
     device (dfh_dump).  The table must stay open and unchanged while the dump is"""
@@ -1065,9 +1098,11 @@ class ModelDump:
             self.h = None
 
 
-class Explain:
+class Explain(_ListText):
     """each appended row's topk strongest FM interaction pairs c_ij = x_i x_j <V_i, V_j> over its positions with V, and the sum
     of all of them (dfh_explain); by |c| (PAIRS_ABS) or c (PAIRS_POS)"""
+
+    _c = "dfh_explain"
 
     def __init__(self, ctx, topk=10, by=PAIRS_ABS, capacity_hint=0):
         self.ctx = ctx
@@ -1109,9 +1144,11 @@ class Explain:
             self.h = None
 
 
-class Recommend:
+class Recommend(_ListText):
     """a catalogue of item rows and, per appended query row, the topk items with the largest b_i + <S_q, S_i>, handed out with
     the logit of the concatenated row (dfh_recommend)"""
+
+    _c = "dfh_recommend"
 
     def __init__(self, ctx, topk=10, capacity_hint=0):
         self.ctx = ctx

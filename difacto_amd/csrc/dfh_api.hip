@@ -55,4 +55,5 @@ using namespace dfh;
 #include "dfh_pairs.hip"         // each entry's top-k FM interaction partners, a blocked V V^T on MFMA that is never stored: the dump's entries
 #include "dfh_explain.hip"       // each row's top-k FM interaction pairs, a wave per row and a 32 x 32 Gram tile per panel pair on MFMA: the batch's step, pr_* (dfh_pairs.hip)
 #include "dfh_recommend.hip"     // each row's top-k catalogue items, a rectangular S_q S_i^T + b_i on MFMA that is never stored: the batch's step, pr_* (dfh_pairs.hip)
+#include "dfh_listtext.hip"      // the lines of explain_out and recommend_out formatted on the device, ragged lines of lists: the two objects above, dt_grow (dfh_dumptext.hip)
 #include "dfh_rowstore.hip"      // a whole data set's rows in HBM and its shuffled blocks: the encoder, the parsed and decoded chunks

@@ -43,6 +43,8 @@
 //                is reverse_bytes(feaids[index[position]]), as task = dump dump_ids = feature prints it.
 // Plain C++, vector stores, no scratch.  Timed as DFH_K_EXPLAIN.
 
+struct LtWork;   // dfh_listtext.hip: the workspace of dfh_explain_format, made by the first format
+
 struct dfh_explain {
   dfh_ctx* ctx = nullptr;
   uint32_t K = 0;
@@ -53,9 +55,12 @@ struct dfh_explain {
   uint32_t* d_cpos = nullptr;        // [cpos_cap] the compaction's workspace: one append's kernel after another uses it, in stream order
   size_t cpos_cap = 0;
   unsigned long long* d_nf = nullptr;   // non-finite pairs since the last reset
+  LtWork* text = nullptr;
+  bool formatted = false;               // text holds the lines of everything appended
 };
 
 namespace {
+void lt_release(LtWork* w);   // dfh_listtext.hip
 constexpr uint32_t EX_P = 32, EX_KC = 16, EX_LS = 20;   // positions per panel; floats of d per staged chunk; LDS row stride in floats
 constexpr uint32_t EX_KMAX = 32, EX_WAVES = 4;
 constexpr uint64_t EX_MAX_ROWS = 0xFFFFFFF0ULL;
@@ -362,6 +367,7 @@ int dfh_explain_destroy(dfh_explain* e) {
   if (e->d_out) (void)hipFree(e->d_out);
   if (e->d_cpos) (void)hipFree(e->d_cpos);
   if (e->d_nf) (void)hipFree(e->d_nf);
+  lt_release(e->text);
   delete e;
   return DFH_OK;
 }
@@ -371,6 +377,7 @@ int dfh_explain_reset(dfh_explain* e) {
   DFH_HIP(hipSetDevice(e->ctx->device));
   DFH_HIP(hipMemsetAsync(e->d_nf, 0, sizeof(unsigned long long), e->ctx->stream));   // behind the kernels that still count
   e->n = 0;   // the arrays stay; later appends are queued behind whatever still reads them
+  e->formatted = false;
   return DFH_OK;
 }
 
@@ -430,6 +437,7 @@ int dfh_explain_append_batch(dfh_explain* e, dfh_batch* b, dfh_table* t) {
     DFH_HIP(hipGetLastError());
   }
   e->n += rows;
+  e->formatted = false;
   // The kernel runs on the context's stream, behind the batch's step, and reads the batch's arrays; the batch object's NEXT load
   // runs on a preparation stream that waits for ev_free alone (the hazard dfh_eval_append_batch documents): with pipelining on,
   // ev_free is recorded again behind the kernel.  Call it before the next minibatch is loaded into the batch object.

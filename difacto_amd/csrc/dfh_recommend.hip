@@ -64,6 +64,8 @@ struct dfh_recommend {
   size_t part_cap = 0;
   std::vector<void*> retired;        // arrays a growth replaced: queued kernels and copies may still use them
   unsigned long long* d_nf = nullptr;
+  LtWork* text = nullptr;            // dfh_listtext.hip: the workspace of dfh_recommend_format, made by the first format
+  bool formatted = false;            // text holds the lines of every query appended
 };
 
 namespace {
@@ -476,6 +478,7 @@ int dfh_recommend_destroy(dfh_recommend* r) {
   if (r->d_aq) (void)hipFree(r->d_aq);
   if (r->d_part) (void)hipFree(r->d_part);
   if (r->d_nf) (void)hipFree(r->d_nf);
+  lt_release(r->text);
   delete r;
   return DFH_OK;
 }
@@ -485,6 +488,7 @@ int dfh_recommend_reset(dfh_recommend* r) {
   DFH_HIP(hipSetDevice(r->ctx->device));
   DFH_HIP(hipMemsetAsync(r->d_nf, 0, sizeof(unsigned long long), r->ctx->stream));   // behind the kernels that still count
   r->n = 0;   // the catalogue and the arrays stay
+  r->formatted = false;
   return DFH_OK;
 }
 
@@ -556,6 +560,7 @@ int dfh_recommend_append_batch(dfh_recommend* r, dfh_batch* b, dfh_table* t) {
            (const float*)r->d_aq, o.item, o.logit, o.n);
   DFH_HIP(hipGetLastError());
   r->n += rows;
+  r->formatted = false;
   return rc_batch_used(c, b);
 }
 

@@ -428,11 +428,48 @@ void SGDLearner::ClosePredUnit() {
   DFH_CALL(dfh_predtext_reset(pt));
 }
 
+// pred_write = device for explain_out / recommend_out, as ClosePredUnit does it: unit u - 1 may still be on its way to the file
+// out of the other buffer; its write overlaps this unit's download, and ends before this unit's write begins
+std::vector<char>* SGDLearner::NextListText(ListText* t, size_t nbytes) {
+  std::vector<char>* text = &t->text[t->cur];
+  t->cur ^= 1;
+  text->resize(nbytes);
+  return text;
+}
+
+void SGDLearner::WriteListText(ListText* t, std::vector<char>* text, FILE* f, const std::string* name) {
+  t->Wait();
+  t->write = std::async(std::launch::async, [f, name, text] {
+    CHECK_EQ(fwrite(text->data(), 1, text->size(), f), text->size()) << "cannot write " << *name;
+  });
+}
+
 // explain_out: one line per row of the unit, "<inter>" then "\t<id_i>:<id_j>:<c>" per pair, behind the lines of the units before
 void SGDLearner::CloseExplainUnit() {
   dfh_explain* e = CHECK_NOTNULL(explain_);
   const size_t n = explain_unit_n_, K = static_cast<size_t>(param_.explain_topk);
   explain_unit_n_ = 0;
+  if (param_.pred_write == "device") {   // the lines come from the device; the non-finite count rides in the format's round trip
+    size_t nbytes = 0;
+    uint64_t irregular = 0, nf = 0;
+    DFH_CALL(dfh_explain_format(e, &nbytes, &irregular));
+    if (irregular == 0) {
+      DFH_CALL(dfh_explain_text_nonfinite(e, &nf));
+      if (nf)
+        LOG(WARNING) << "explain_out: " << nf << " pairs of this unit have a contribution that is not finite; they are in no "
+                        "line and in no total";
+      std::vector<char>* text = NextListText(&explain_text_, nbytes);
+      DFH_CALL(dfh_explain_read_text(e, text->data()));
+      WriteListText(&explain_text_, text, CHECK_NOTNULL(explain_file_), &param_.explain_out);
+      explain_text_.counts.dev_rows += n;
+      ++explain_text_.counts.dev_units;
+      DFH_CALL(dfh_explain_reset(e));
+      return;
+    }
+    explain_text_.Wait();   // a float the device does not format: the whole unit as pred_write = host writes it, behind the unit before
+    explain_text_.counts.host_rows += n;
+    ++explain_text_.counts.host_units;
+  }
   std::vector<uint32_t> cnt(n);
   std::vector<uint64_t> ids_i(n * K), ids_j(n * K);
   std::vector<float> c(n * K), inter(n);
@@ -460,6 +497,27 @@ void SGDLearner::CloseRecommendUnit() {
   dfh_recommend* r = CHECK_NOTNULL(recommend_);
   const size_t n = recommend_unit_n_, K = static_cast<size_t>(param_.recommend_topk);
   recommend_unit_n_ = 0;
+  if (param_.pred_write == "device") {   // as CloseExplainUnit
+    size_t nbytes = 0;
+    uint64_t irregular = 0, nf = 0;
+    DFH_CALL(dfh_recommend_format(r, &nbytes, &irregular));
+    if (irregular == 0) {
+      DFH_CALL(dfh_recommend_text_nonfinite(r, &nf));
+      if (nf)
+        LOG(WARNING) << "recommend_out: " << nf << " (row, item) pairs of this unit have a score that is not finite; they are in "
+                        "no line";
+      std::vector<char>* text = NextListText(&recommend_text_, nbytes);
+      DFH_CALL(dfh_recommend_read_text(r, text->data()));
+      WriteListText(&recommend_text_, text, CHECK_NOTNULL(recommend_file_), &param_.recommend_out);
+      recommend_text_.counts.dev_rows += n;
+      ++recommend_text_.counts.dev_units;
+      DFH_CALL(dfh_recommend_reset(r));
+      return;
+    }
+    recommend_text_.Wait();
+    recommend_text_.counts.host_rows += n;
+    ++recommend_text_.counts.host_units;
+  }
   std::vector<uint32_t> cnt(n), items(n * K);
   std::vector<float> logits(n * K);
   uint64_t nonfinite = 0;
@@ -678,7 +736,7 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     if (!predtext_) DFH_CALL(dfh_predtext_create(ctx, 0, &predtext_));
     DFH_CALL(dfh_predtext_reset(predtext_));
     pred_unit_n_ = 0;
-    pred_counts_ = PredCounts();
+    pred_counts_ = explain_text_.counts = recommend_text_.counts = PredCounts();
   }
   const bool catalogue = catalogue_pass_;   // recommend_out: this job reads items_in; its minibatches become items, nothing is written
   const bool explain = predict && !catalogue && param_.explain_out.size();
@@ -817,6 +875,8 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
   }
   if (explain && explain_unit_n_) CloseExplainUnit();
   if (recommend && recommend_unit_n_) CloseRecommendUnit();
+  explain_text_.Wait();   // a unit closes at the end of every data part: the files are complete when the job returns
+  recommend_text_.Wait();
   if (src.pred_feed) {   // a unit closes at the end of every data part
     if (pred_unit_n_) ClosePredUnit();
     WaitPredWrite();
@@ -829,6 +889,14 @@ void SGDLearner::RunFused(const sgd::Job& job, const FusedSource& src, const Sgd
     LOG(INFO) << "pred_write=device: " << pred_counts_.dev_rows << " rows in " << pred_counts_.dev_units
               << " units formatted on the device, " << pred_counts_.host_rows << " rows in " << pred_counts_.host_units
               << " units on the host";
+    if (explain)
+      LOG(INFO) << "explain_out: pred_write=device: " << explain_text_.counts.dev_rows << " rows in " << explain_text_.counts.dev_units
+                << " units formatted on the device, " << explain_text_.counts.host_rows << " rows in " << explain_text_.counts.host_units
+                << " units on the host";
+    if (recommend)
+      LOG(INFO) << "recommend_out: pred_write=device: " << recommend_text_.counts.dev_rows << " rows in "
+                << recommend_text_.counts.dev_units << " units formatted on the device, " << recommend_text_.counts.host_rows
+                << " rows in " << recommend_text_.counts.host_units << " units on the host";
   }
   ring_.Drain(progress);
 }

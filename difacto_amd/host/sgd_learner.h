@@ -129,6 +129,19 @@ class SGDLearner : public Learner {
   size_t recommend_unit_n_ = 0;
   bool catalogue_pass_ = false;
   struct PredCounts { size_t dev_rows = 0, dev_units = 0, host_rows = 0, host_units = 0; } pred_counts_;
+  // pred_write = device for explain_out / recommend_out: a key's two text buffers (one being written to its file while the next
+  // unit is downloaded into the other), the write under way, and the job's counts for its log line
+  struct ListText {
+    std::vector<char> text[2];
+    int cur = 0;
+    std::future<void> write;
+    PredCounts counts;
+    void Wait() { if (write.valid()) write.get(); }
+  } explain_text_, recommend_text_;
+  /*! \brief the next buffer of t, sized for a unit's text; the caller downloads into it and hands it to WriteListText */
+  std::vector<char>* NextListText(ListText* t, size_t nbytes);
+  /*! \brief waits for the unit before, then starts writing the buffer to f on a thread */
+  void WriteListText(ListText* t, std::vector<char>* text, FILE* f, const std::string* name);
 };
 
 }  // namespace difacto

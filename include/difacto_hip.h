@@ -1013,6 +1013,23 @@ int dfh_explain_read(dfh_explain* e, uint32_t* n /*[count]*/, uint64_t* ids_i /*
                      float* c /*[count*topk]*/, float* inter /*[count]*/, uint64_t* nonfinite);
 /* the same pairs as positions inside their rows (0-based, i < j), for a caller that holds the rows; synchronises */
 int dfh_explain_read_positions(dfh_explain* e, uint32_t* pos_i /*[count*topk]*/, uint32_t* pos_j /*[count*topk]*/);
+/* The lines of explain_out, formatted on the device from the lists where they lie (csrc/dfh_listtext.hip; the arithmetic, exact
+ * and integer only: csrc/dfh_listtext_fmt.h).  Row r: "%.9g" of inter[r], then "\t%llu:%llu:%.9g" of ids_i, ids_j, c for each of
+ * its n[r] pairs, then "\n"; at most 15 + 58 topk + 1 bytes.  Everything appended since the last reset, in append order: two
+ * launches and a scan between them, then ONE host round trip for *nbytes (the text's length), *irregular (the floats the device
+ * does not format: anything but +-0 and 2^-64 <= |v| < 2^32, see dfh_predtext above; > 0: the text is not to be used, and the
+ * caller formats the unit from dfh_explain_read) and the non-finite count.  It changes nothing: more may be appended, a later
+ * format covers all of it, and the read calls above stay valid beside it.  Device memory: 15 + 58 topk + 5 bytes per row, kept.
+ * DFH_ERR_CAPACITY for a workspace that fails to allocate, with the bytes needed in the message. */
+int dfh_explain_format(dfh_explain* e, size_t* nbytes, uint64_t* irregular);
+/* the text of the last format into dst [nbytes] (downloaded into page-locked memory of the object's, then copied); valid when
+ * that format reported irregular == 0.  DFH_ERR_STATE before a format, and after an append or a reset since the last one. */
+int dfh_explain_read_text(dfh_explain* e, char* dst);
+/* dfh_explain_read's *nonfinite as the last format read it back, in that format's round trip: no wait, no download of the lists.
+ * DFH_ERR_STATE as dfh_explain_read_text. */
+int dfh_explain_text_nonfinite(dfh_explain* e, uint64_t* nonfinite);
+/* the rows a block of the format kernels takes: min(1024, floor(32768 / (15 + 58 topk + 1))) (for tests) */
+int dfh_explain_text_tile(dfh_explain* e);
 
 /* ------------------------------------------------ each row's best catalogue items (recommend_out of task = predict) */
 /* A dfh_recommend holds a CATALOGUE of item rows and, for every query row appended since the last reset, the topk (1 .. 32)
@@ -1045,6 +1062,14 @@ int dfh_recommend_read(dfh_recommend* r, uint32_t* n /*[count]*/, uint32_t* item
                        uint64_t* nonfinite);
 /* drops the queries and the non-finite count; the catalogue stays */
 int dfh_recommend_reset(dfh_recommend* r);
+/* The lines of recommend_out, formatted on the device like dfh_explain_format's.  Row q: "%u:%.9g" of items, logits for each of
+ * its n[q] entries, joined by "\t" with none before the first, then "\n" (n = 0: the single byte "\n"); at most 27 topk + 1
+ * bytes.  The four calls have the semantics of their dfh_explain namesakes; device memory: 27 topk + 5 bytes per query row. */
+int dfh_recommend_format(dfh_recommend* r, size_t* nbytes, uint64_t* irregular);
+int dfh_recommend_read_text(dfh_recommend* r, char* dst);
+int dfh_recommend_text_nonfinite(dfh_recommend* r, uint64_t* nonfinite);
+/* min(1024, floor(32768 / (27 topk + 1))) */
+int dfh_recommend_text_tile(dfh_recommend* r);
 
 /* raw device memory for hosts without a HIP runtime of their own */
 int dfh_malloc(dfh_ctx* ctx, size_t bytes, void** dptr);
