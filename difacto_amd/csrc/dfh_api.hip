@@ -49,11 +49,12 @@ using namespace dfh;
 #include "dfh_owlqn.hip"         // l1 on w for learner = lbfgs, the orthant-wise forms of its vector passes: dfh_lbfgs.hip
 #include "dfh_bcd.hip"           // learner = bcd: the chunk set, the join, the communicator
 #include "dfh_eval.hip"          // whole-set evaluation, exact AUC, logloss and accuracy of the appended rows: the handles
-#include "dfh_eval_groups.hip"   // the same rows by group, per-group records and the grouped AUC: the evaluator, the batch's step
-#include "dfh_predtext.hip"      // prediction text, the bytes of fprintf("%.9g\n") for the appended values: the handles
-#include "dfh_dumptext.hip"      // a model table as sorted text, "<id>\t<w>[\t<V_j>]" per kept entry: the table calls, dfh_predtext_fmt.h
-#include "dfh_pairs.hip"         // each entry's top-k FM interaction partners, a blocked V V^T on MFMA that is never stored: the dump's entries
-#include "dfh_explain.hip"       // each row's top-k FM interaction pairs, a wave per row and a 32 x 32 Gram tile per panel pair on MFMA: the batch's step, pr_* (dfh_pairs.hip)
-#include "dfh_recommend.hip"     // each row's top-k catalogue items, a rectangular S_q S_i^T + b_i on MFMA that is never stored: the batch's step, pr_* (dfh_pairs.hip)
-#include "dfh_listtext.hip"      // the lines of explain_out and recommend_out formatted on the device, ragged lines of lists: the two objects above, dt_grow (dfh_dumptext.hip)
+#include "dfh_textout.hip"       // what the device formatters share, workspace, two-pass driver, download, the kernels' common parts, and dev_grow: the handles
+#include "dfh_eval_groups.hip"   // the same rows by group, per-group records and the grouped AUC: the evaluator, the batch's step, dev_grow
+#include "dfh_predtext.hip"      // prediction text, the bytes of fprintf("%.9g\n") for the appended values: dfh_textout.hip
+#include "dfh_dumptext.hip"      // a model table as sorted text, "<id>\t<w>[\t<V_j>]" per kept entry: the table calls, dfh_textout.hip, dfh_predtext_fmt.h
+#include "dfh_pairs.hip"         // each entry's top-k FM interaction partners, a blocked V V^T on MFMA that is never stored: the dump's entries, dev_grow
+#include "dfh_explain.hip"       // each row's top-k FM interaction pairs, a wave per row and a 32 x 32 Gram tile per panel pair on MFMA: the batch's step, pr_* (dfh_pairs.hip), TextWork
+#include "dfh_recommend.hip"     // each row's top-k catalogue items, a rectangular S_q S_i^T + b_i on MFMA that is never stored: the batch's step, pr_* (dfh_pairs.hip), TextWork
+#include "dfh_listtext.hip"      // the lines of explain_out and recommend_out formatted on the device, ragged lines of lists: the two objects above, dfh_textout.hip
 #include "dfh_rowstore.hip"      // a whole data set's rows in HBM and its shuffled blocks: the encoder, the parsed and decoded chunks

@@ -83,14 +83,7 @@ DFH_PT_FN Field dt_field(uint32_t bits) {
   return F;
 }
 
-DFH_PT_FN void dt_put_field(unsigned char* p, const Field& F) {
-#pragma unroll
-  for (uint32_t b = 0; b < 8; ++b)
-    if (b < F.len) p[b] = (unsigned char)(F.lo >> (8 * b));
-#pragma unroll
-  for (uint32_t b = 0; b < 8; ++b)
-    if (8 + b < F.len) p[8 + b] = (unsigned char)(F.hi >> (8 * b));
-}
+DFH_PT_FN void dt_put_field(unsigned char* p, const Field& F) { dfh_pt::pt_put(p, F.lo, F.hi, F.len); }
 
 // One whole line into dst (room for dt_max_line(V_dim) bytes), serially: what the device lays out with a scan over the lanes
 // of an entry.  Returns the line's length; *irregular grows by the values that were not formatted (the line is then not valid:

@@ -484,22 +484,6 @@ void gv_free(dfh_eval* e) {
   if (e->d_rec) (void)hipFree(e->d_rec);
 }
 
-// a block of the evaluator that only grows; nothing queued uses it when a finish asks (the last one has waited)
-int gv_grow(char** p, size_t* have, size_t bytes, const char* what) {
-  if (bytes <= *have) return DFH_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  if (hipMalloc((void**)p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    set_error(std::string("dfh_eval_finish_groups: no device memory for ") + what + " (" + std::to_string(bytes) + " bytes needed)");
-    return DFH_ERR_CAPACITY;
-  }
-  *have = bytes;
-  return DFH_OK;
-}
-
 GRec gv_rec(char* p, size_t G) {
   uint64_t* w = (uint64_t*)p;
   return GRec{w, w + G, w + 2 * G, w + 3 * G, w + 4 * G, w + 5 * G, (double*)(w + 6 * G)};
@@ -567,7 +551,7 @@ int dfh_eval_finish_groups(dfh_eval* e, dfh_eval_groups_result* out) {
   const uint32_t ntn = (uint32_t)((n + GV_TILE - 1) / GV_TILE);
   uint32_t *cnt = nullptr, *pre = nullptr;
   if (n) {
-    int rc = gv_grow(&e->d_gpre, &e->gpre_bytes, ev_pad((size_t)ntn * 4) + ev_pad(((size_t)ntn + 1) * 4), "the tiles' row counts");
+    int rc = dev_grow(&e->d_gpre, &e->gpre_bytes, ev_pad((size_t)ntn * 4) + ev_pad(((size_t)ntn + 1) * 4), "dfh_eval_finish_groups", "the tiles' row counts");
     if (rc) return rc;
     cnt = (uint32_t*)e->d_gpre;
     pre = (uint32_t*)(e->d_gpre + ev_pad((size_t)ntn * 4));
@@ -598,7 +582,7 @@ int dfh_eval_finish_groups(dfh_eval* e, dfh_eval_groups_result* out) {
   const size_t o_hp = o_pg + ev_pad((size_t)nt * 8), o_tp = o_hp + ev_pad((size_t)nt * sizeof(GSum));
   const size_t o_id = o_tp + ev_pad((size_t)nt * sizeof(GSum)), o_temp = o_id + ev_pad((size_t)nt * 8);
   const size_t bytes = o_temp + ev_pad(tb + 16);
-  int rc = gv_grow(&e->d_work, &e->work_bytes, bytes, ("ranking " + std::to_string(m) + " rows by group").c_str());
+  int rc = dev_grow(&e->d_work, &e->work_bytes, bytes, "dfh_eval_finish_groups", ("ranking " + std::to_string(m) + " rows by group").c_str());
   if (rc) return rc;
   char* w = e->d_work;
   GHdr* hdr = (GHdr*)(w + o_hdr);
@@ -620,7 +604,7 @@ int dfh_eval_finish_groups(dfh_eval* e, dfh_eval_groups_result* out) {
   DFH_HIP(hipStreamSynchronize(s));
   const size_t G = tot.y;
   // 3. the records and the summary
-  rc = gv_grow(&e->d_rec, &e->rec_bytes, G * 7 * 8, ("the records of " + std::to_string(G) + " groups").c_str());
+  rc = dev_grow(&e->d_rec, &e->rec_bytes, G * 7 * 8, "dfh_eval_finish_groups", ("the records of " + std::to_string(G) + " groups").c_str());
   if (rc) return rc;
   const GRec rec = gv_rec(e->d_rec, G);
   DFH_HIP(hipMemsetAsync(hp, 0, (size_t)nt * sizeof(GSum), s));

@@ -43,8 +43,6 @@
 //                is reverse_bytes(feaids[index[position]]), as task = dump dump_ids = feature prints it.
 // Plain C++, vector stores, no scratch.  Timed as DFH_K_EXPLAIN.
 
-struct LtWork;   // dfh_listtext.hip: the workspace of dfh_explain_format, made by the first format
-
 struct dfh_explain {
   dfh_ctx* ctx = nullptr;
   uint32_t K = 0;
@@ -55,12 +53,11 @@ struct dfh_explain {
   uint32_t* d_cpos = nullptr;        // [cpos_cap] the compaction's workspace: one append's kernel after another uses it, in stream order
   size_t cpos_cap = 0;
   unsigned long long* d_nf = nullptr;   // non-finite pairs since the last reset
-  LtWork* text = nullptr;
+  TextWork text;                        // the workspace of dfh_explain_format (dfh_listtext.hip over dfh_textout.hip)
   bool formatted = false;               // text holds the lines of everything appended
 };
 
 namespace {
-void lt_release(LtWork* w);   // dfh_listtext.hip
 constexpr uint32_t EX_P = 32, EX_KC = 16, EX_LS = 20;   // positions per panel; floats of d per staged chunk; LDS row stride in floats
 constexpr uint32_t EX_KMAX = 32, EX_WAVES = 4;
 constexpr uint64_t EX_MAX_ROWS = 0xFFFFFFF0ULL;
@@ -367,7 +364,7 @@ int dfh_explain_destroy(dfh_explain* e) {
   if (e->d_out) (void)hipFree(e->d_out);
   if (e->d_cpos) (void)hipFree(e->d_cpos);
   if (e->d_nf) (void)hipFree(e->d_nf);
-  lt_release(e->text);
+  to_release(&e->text);
   delete e;
   return DFH_OK;
 }

@@ -28,16 +28,6 @@ static_assert(LT_EX_ENTRY == 58 && LT_RC_ENTRY == 27, "the entries' bounds follo
 DFH_PT_FN uint64_t lt_explain_max_line(uint64_t K) { return LT_MAX_VALUE + LT_EX_ENTRY * K + 1; }
 DFH_PT_FN uint64_t lt_recommend_max_line(uint64_t K) { return LT_RC_ENTRY * K + 1; }
 
-// n <= 16 bytes of {lo, hi}, the first in the lowest byte of lo
-DFH_PT_FN void lt_put_bytes(unsigned char* p, uint64_t lo, uint64_t hi, uint32_t n) {
-#pragma unroll
-  for (uint32_t b = 0; b < 8; ++b)
-    if (b < n) p[b] = (unsigned char)(lo >> (8 * b));
-#pragma unroll
-  for (uint32_t b = 0; b < 8; ++b)
-    if (8 + b < n) p[8 + b] = (unsigned char)(hi >> (8 * b));
-}
-
 // ':' and the text of %.9g: dt_field with the ':' where its '\t' is.  len 2 .. 16; 0: the value is not regular
 DFH_PT_FN dfh_dt::Field lt_value(uint32_t bits) {
   dfh_dt::Field F = dfh_dt::dt_field(bits);
@@ -114,7 +104,7 @@ DFH_PT_FN uint32_t lt_explain_line(unsigned char* dst, uint32_t inter_bits, uint
                                    const uint32_t* c_bits, uint32_t* irregular) {
   const dfh_pt::Line H = lt_head(inter_bits);
   if (H.len == 0) ++*irregular;
-  lt_put_bytes(dst, H.lo, H.hi, H.len);
+  dfh_pt::pt_put(dst, H.lo, H.hi, H.len);
   uint32_t at = H.len;
   for (uint32_t j = 0; j < n; ++j) {
     const ExEntry E = lt_explain_entry(ids_i[j], ids_j[j], c_bits[j]);

@@ -275,27 +275,23 @@ int pairs_build(dfh_dump* p) {
   uint32_t* flags = nullptr;
   size_t need = 0;
   DFH_HIP(rocprim::exclusive_scan(nullptr, need, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
-  int rc = dt_grow(&flags, &fcap, (size_t)n + 1, who, "the has-V flags");
-  if (!rc) rc = dt_grow(&r.epos, &ecap, (size_t)n + 1, who, "the entries' positions");
-  if (!rc) rc = dt_grow(&r.map, &mcap, (size_t)nV, who, "the positions' entries");
-  if (!rc) rc = dt_grow(&r.P, &pcap, (size_t)r.rows * r.kd, who, "the packed V rows");
-  if (!rc) rc = dt_grow(&r.d_nf, &ncap, 1, who, "the non-finite count");
-  if (!rc) {
-    char* tmp = static_cast<char*>(p->d_tmp);
-    rc = dt_grow(&tmp, &p->tmp_bytes, std::max<size_t>(need, 256), who, "the scan");
-    p->d_tmp = tmp;
-  }
+  int rc = dev_grow(&flags, &fcap, (size_t)n + 1, who, "the has-V flags");
+  if (!rc) rc = dev_grow(&r.epos, &ecap, (size_t)n + 1, who, "the entries' positions");
+  if (!rc) rc = dev_grow(&r.map, &mcap, (size_t)nV, who, "the positions' entries");
+  if (!rc) rc = dev_grow(&r.P, &pcap, (size_t)r.rows * r.kd, who, "the packed V rows");
+  if (!rc) rc = dev_grow(&r.d_nf, &ncap, 1, who, "the non-finite count");
+  if (!rc) rc = dev_grow(&p->text.d_tmp, &p->text.tmp_bytes, std::max<size_t>(need, 256), who, "the scan");
   hipError_t e = hipSuccess;
   if (!rc) {
     TimeScope ts(p->ctx, DFH_K_PAIRS_PACK);
     const TableView& v = p->t->v;
-    size_t tb = p->tmp_bytes;
+    size_t tb = p->text.tmp_bytes;
     e = hipMemsetAsync(r.P, 0, (size_t)r.rows * r.kd * sizeof(float), s);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_pairs_flags, dim3((unsigned)grid_for_threads((size_t)n + 1, p->ctx)), dim3(256), 0, s, (const uint32_t*)p->d_row, n, flags);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = rocprim::exclusive_scan(p->d_tmp, tb, flags, r.epos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(p->text.d_tmp, tb, flags, r.epos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_pairs_pack, dim3((unsigned)grid_for_threads((size_t)n * (r.kd / 4), p->ctx)), dim3(256), 0, s, (const float*)v.va, p->k,
                          (uint32_t)v.kp, r.kd, (const uint32_t*)p->d_row, (const uint32_t*)r.epos, n, r.P, r.map);
@@ -355,8 +351,8 @@ extern "C" int dfh_dump_pairs(dfh_dump* p, uint64_t first, size_t count, int top
   S = std::max(1u, std::min(std::min(S, CT), PR_SMAX));
   const char* who = "dfh_dump_pairs";
   const size_t out_bytes = count * K * (sizeof(uint64_t) + sizeof(float)) + count * sizeof(uint32_t);
-  int rc = dt_grow(&r.out, &r.out_cap, out_bytes, who, "the lists");
-  if (!rc && QT) rc = dt_grow(&r.part, &r.part_cap, (size_t)QT * S * PR_T * K, who, "the splits' partial lists");
+  int rc = dev_grow(&r.out, &r.out_cap, out_bytes, who, "the lists");
+  if (!rc && QT) rc = dev_grow(&r.part, &r.part_cap, (size_t)QT * S * PR_T * K, who, "the splits' partial lists");
   if (rc) return rc;
   uint64_t* o_id = reinterpret_cast<uint64_t*>(r.out);   // 8 B, then the 4 B arrays
   float* o_score = reinterpret_cast<float*>(o_id + count * K);

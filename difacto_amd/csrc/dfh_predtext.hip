@@ -4,18 +4,11 @@
 // are copies queued on the context's stream, a replaced array is freed behind the next wait.
 // The arithmetic is dfh_predtext_fmt.h: exact, integer only, for the REGULAR values (+-0 and 2^-64 <= |v| < 2^32).  Anything
 // else is counted, and the caller formats such a set on the host — the idiom of the parse and decode kernels.
-// dfh_predtext_format queues
-//   k_predtext<0>   a block per tile of PT_TILE values, a lane per value and round: the line's length; the tile's bytes, and the
-//                   irregular values of the tile added to the one counter the blocks share (an atomic per block that has any)
-//   rocprim::exclusive_scan over the tiles' bytes
-//   k_predtext<1>   a block per tile again: the lines are formatted ONCE MORE (nothing but 4 B per value is carried between the
-//                   passes: a 16 B slot per value would cost 33 B of traffic per value to save ~250 integer instructions) and
-//                   laid out in LDS at their scanned offsets, the image shifted by the tile's first byte mod 16; then the block
-//                   writes the image with aligned 16 B stores, and only the tile's unaligned head and tail byte by byte (two
-//                   neighbouring tiles meet inside one 16 B word: each writes its own bytes of it)
-// and reads back {bytes, irregular} — one host round trip.  The launches are ordered by the stream alone: no block waits for
-// another.  Plain C++, no scratch.  These kernels are not in the timing registry (dfh_kernel_name) and no launch of a step
-// changes.
+// dfh_predtext_format is the two passes of dfh_textout.hip with k_predtext: a tile is PT_TILE values, a lane per value and round,
+// and NO per-value length is carried between the passes: the emit pass formats the lines once more and places a round's lines
+// with one block scan (a 16 B slot per value would cost 33 B of traffic per value to save ~250 integer instructions; 4 B per
+// value would still be a write and a read that the scan makes unnecessary).  Its image is PT_TILE * 16 + 16 bytes.  These
+// kernels are not in the timing registry (dfh_kernel_name) and no launch of a step changes.
 #include "dfh_predtext_fmt.h"
 
 struct dfh_predtext {
@@ -23,18 +16,8 @@ struct dfh_predtext {
   float* d_val = nullptr;       // [cap] the appended values
   size_t cap = 0, n = 0, hint = 0;
   std::vector<void*> retired;   // arrays a growth replaced: copies out of them may still be queued, freed behind the next wait
-  // format's workspace, grown to what a format needs, kept
-  char* d_text = nullptr;       // [text_cap] the text of the last format
-  size_t text_cap = 0, text_bytes = 0;
-  uint64_t *d_tile = nullptr, *d_tile_scan = nullptr;   // [tile_cap] bytes per tile (and a 0), their exclusive scan (the last: all bytes)
-  size_t tile_cap = 0, scan_cap = 0;
-  void* d_tmp = nullptr;        // rocprim's
-  size_t tmp_bytes = 0;
-  uint32_t* d_irr = nullptr;    // the irregular values of the last format
-  uint64_t* h_head = nullptr;   // page-locked {bytes, irregular}
-  char* h_text = nullptr;       // page-locked: read's download lands here
-  size_t h_text_cap = 0;
-  bool formatted = false;       // d_text holds the text of everything appended
+  TextWork text;                // format's workspace (dfh_textout.hip)
+  bool formatted = false;       // text holds the text of everything appended
 };
 
 namespace {
@@ -67,11 +50,7 @@ __global__ void __launch_bounds__(256) k_predtext(const uint32_t* __restrict__ v
     Reduce().reduce(bytes, tb, s_red);
     __syncthreads();
     Reduce().reduce(irr, ti, s_red);
-    if (threadIdx.x == 0) {
-      tile_bytes[blockIdx.x] = tb;
-      if (blockIdx.x == 0) tile_bytes[gridDim.x] = 0;
-      if (ti) atomicAdd(irregular, ti);
-    }
+    if (threadIdx.x == 0) to_tile_out(tb, ti, tile_bytes, irregular);
     return;
   }
   __shared__ typename Scan::storage_type s_scan;
@@ -88,22 +67,11 @@ __global__ void __launch_bounds__(256) k_predtext(const uint32_t* __restrict__ v
     if (i < n) L = dfh_pt::pt_format(vals[i]);
     uint32_t before = 0, total = 0;
     Scan().exclusive_scan(L.len, before, 0u, total, s_scan);
-    unsigned char* p = img + run + before;   // run + before + len <= 15 + PT_TILE * 16
-#pragma unroll
-    for (uint32_t b = 0; b < 8; ++b)
-      if (b < L.len) p[b] = (unsigned char)(L.lo >> (8 * b));
-#pragma unroll
-    for (uint32_t b = 0; b < 8; ++b)
-      if (8 + b < L.len) p[8 + b] = (unsigned char)(L.hi >> (8 * b));
+    dfh_pt::pt_put(img + run + before, L.lo, L.hi, L.len);   // run + before + len <= 15 + PT_TILE * 16
     run += total;
     __syncthreads();   // s_scan is used again; after the last round: the image is complete
   }
-  const uint64_t a0 = (g_first + 15) & ~15ULL, a1 = g_end & ~15ULL;   // the aligned words lie in [a0, a1)
-  const uint64_t head_end = a0 < g_end ? a0 : g_end;
-  for (uint64_t q = g_first + threadIdx.x; q < head_end; q += 256) out[q] = img[q - g_img];
-  for (uint64_t q = a0 + 16ULL * threadIdx.x; q < a1; q += 16ULL * 256)
-    *reinterpret_cast<uint4*>(out + q) = *reinterpret_cast<const uint4*>(img + (q - g_img));
-  for (uint64_t q = (a1 > head_end ? a1 : head_end) + threadIdx.x; q < g_end; q += 256) out[q] = img[q - g_img];
+  to_store(out, img, g_first, g_end, g_img);
 }
 
 void pt_free_retired(dfh_predtext* p) {
@@ -148,23 +116,6 @@ int pt_append(dfh_predtext* p, const float* v, size_t n, hipMemcpyKind kind) {
   p->formatted = false;
   return DFH_OK;
 }
-
-// a workspace array of at least `count` T (only a format uses them, and the last one has waited for its work)
-template <typename T>
-int pt_grow(T** ptr, size_t* cap, size_t count, const char* what) {
-  if (count <= *cap) return DFH_OK;
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(ptr), count * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    *ptr = nullptr;
-    set_error(std::string("dfh_predtext_format: no device memory for ") + what + " (" + std::to_string(count * sizeof(T)) + " bytes needed)");
-    return DFH_ERR_CAPACITY;
-  }
-  *cap = count;
-  return DFH_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -179,14 +130,6 @@ int dfh_predtext_create(dfh_ctx* ctx, size_t capacity_hint, dfh_predtext** out) 
   }
   p->ctx = ctx;
   p->hint = capacity_hint;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_irr), sizeof(uint32_t));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&p->h_head), 2 * sizeof(uint64_t), hipHostMallocDefault);
-  if (e != hipSuccess) {
-    set_error(std::string("dfh_predtext_create: ") + hipGetErrorString(e));
-    dfh_predtext_destroy(p);
-    return DFH_ERR_HIP;
-  }
   *out = p;
   return DFH_OK;
 }
@@ -197,13 +140,7 @@ int dfh_predtext_destroy(dfh_predtext* p) {
   (void)hipStreamSynchronize(p->ctx->stream);   // queued copies and kernels read and write the arrays
   pt_free_retired(p);
   if (p->d_val) (void)hipFree(p->d_val);
-  if (p->d_text) (void)hipFree(p->d_text);
-  if (p->d_tile) (void)hipFree(p->d_tile);
-  if (p->d_tile_scan) (void)hipFree(p->d_tile_scan);
-  if (p->d_tmp) (void)hipFree(p->d_tmp);
-  if (p->d_irr) (void)hipFree(p->d_irr);
-  if (p->h_head) (void)hipHostFree(p->h_head);
-  if (p->h_text) (void)hipHostFree(p->h_text);
+  to_release(&p->text);
   delete p;
   return DFH_OK;
 }
@@ -264,69 +201,27 @@ int dfh_predtext_format(dfh_predtext* p, size_t* nbytes, uint64_t* irregular) {
   hipStream_t s = p->ctx->stream;
   DFH_HIP(hipSetDevice(p->ctx->device));
   p->formatted = false;
-  p->text_bytes = 0;
-  const size_t n = p->n;
-  if (n == 0) {
-    DFH_HIP(hipStreamSynchronize(s));
-    pt_free_retired(p);
-    p->formatted = true;
-    return DFH_OK;
-  }
-  const size_t ntiles = (n + PT_TILE - 1) / PT_TILE;
-  size_t need = 0;
-  DFH_HIP(rocprim::exclusive_scan(nullptr, need, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, ntiles + 1, rocprim::plus<uint64_t>(), s));
-  int rc = pt_grow(&p->d_text, &p->text_cap, n * dfh_pt::PT_MAX_LINE, "the text");
-  if (!rc) rc = pt_grow(&p->d_tile, &p->tile_cap, ntiles + 1, "the tiles' byte counts");
-  if (!rc) rc = pt_grow(&p->d_tile_scan, &p->scan_cap, ntiles + 1, "the tiles' offsets");
-  if (!rc) {
-    char* tmp = static_cast<char*>(p->d_tmp);
-    rc = pt_grow(&tmp, &p->tmp_bytes, std::max<size_t>(need, 256), "the scan");
-    p->d_tmp = tmp;
-  }
-  if (rc) return rc;
-  DFH_HIP(hipMemsetAsync(p->d_irr, 0, sizeof(uint32_t), s));
   const uint32_t* vals = reinterpret_cast<const uint32_t*>(p->d_val);
-  hipLaunchKernelGGL(k_predtext<0>, dim3((unsigned)ntiles), dim3(256), 0, s, vals, (uint64_t)n, p->d_tile, (const uint64_t*)nullptr,
-                     (unsigned char*)nullptr, p->d_irr);
-  DFH_HIP(hipGetLastError());
-  size_t tb = p->tmp_bytes;
-  DFH_HIP(rocprim::exclusive_scan(p->d_tmp, tb, p->d_tile, p->d_tile_scan, (uint64_t)0, ntiles + 1, rocprim::plus<uint64_t>(), s));
-  hipLaunchKernelGGL(k_predtext<1>, dim3((unsigned)ntiles), dim3(256), 0, s, vals, (uint64_t)n, (uint64_t*)nullptr, p->d_tile_scan,
-                     reinterpret_cast<unsigned char*>(p->d_text), (uint32_t*)nullptr);
-  DFH_HIP(hipGetLastError());
-  p->h_head[0] = p->h_head[1] = 0;
-  DFH_HIP(hipMemcpyAsync(&p->h_head[0], p->d_tile_scan + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  DFH_HIP(hipMemcpyAsync(&p->h_head[1], p->d_irr, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  DFH_HIP(hipStreamSynchronize(s));
-  pt_free_retired(p);
-  p->text_bytes = (size_t)p->h_head[0];
+  const uint64_t n = p->n;
+  const int rc = to_format(p->ctx, &p->text, p->n, PT_TILE, dfh_pt::PT_MAX_LINE, false, nullptr, "dfh_predtext_format",
+                           [&](int emit, unsigned ntiles, const TextPass& a) {
+                             hipLaunchKernelGGL(emit ? k_predtext<1> : k_predtext<0>, dim3(ntiles), dim3(256), 0, s, vals, n, a.tile_bytes,
+                                                a.tile_scan, a.out, a.irregular);
+                           },
+                           nbytes, irregular);
+  if (rc) return rc;
+  pt_free_retired(p);   // behind the format's wait
   p->formatted = true;
-  *nbytes = p->text_bytes;
-  *irregular = p->h_head[1];
   return DFH_OK;
 }
 
 int dfh_predtext_read(dfh_predtext* p, char* dst) {
-  DFH_ARG(p && (dst || p->text_bytes == 0), "dfh_predtext_read: NULL argument");
+  DFH_ARG(p && (dst || p->text.text_bytes == 0), "dfh_predtext_read: NULL argument");
   if (!p->formatted) {
     set_error("dfh_predtext_read: nothing formatted (call dfh_predtext_format after the last append)");
     return DFH_ERR_STATE;
   }
-  const size_t nb = p->text_bytes;
-  if (nb == 0) return DFH_OK;
-  DFH_HIP(hipSetDevice(p->ctx->device));
-  if (nb > p->h_text_cap) {   // the download lands in page-locked memory of the object's, kept
-    if (p->h_text) DFH_HIP(hipHostFree(p->h_text));
-    p->h_text = nullptr;
-    p->h_text_cap = 0;
-    const size_t c = nb + nb / 4;
-    DFH_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_text), c, hipHostMallocDefault));
-    p->h_text_cap = c;
-  }
-  DFH_HIP(hipMemcpyAsync(p->h_text, p->d_text, nb, hipMemcpyDeviceToHost, p->ctx->stream));
-  DFH_HIP(hipStreamSynchronize(p->ctx->stream));
-  memcpy(dst, p->h_text, nb);
-  return DFH_OK;
+  return to_read(p->ctx, &p->text, dst);
 }
 
 int dfh_predtext_tile(void) { return (int)PT_TILE; }

@@ -40,6 +40,16 @@ struct Line {
 
 constexpr uint32_t PT_MAX_LINE = 16;
 
+// n <= 16 bytes of {lo, hi} to p[0 .. n), the first in the lowest byte of lo
+DFH_PT_FN void pt_put(unsigned char* p, uint64_t lo, uint64_t hi, uint32_t n) {
+#pragma unroll
+  for (uint32_t b = 0; b < 8; ++b)
+    if (b < n) p[b] = (unsigned char)(lo >> (8 * b));
+#pragma unroll
+  for (uint32_t b = 0; b < 8; ++b)
+    if (8 + b < n) p[8 + b] = (unsigned char)(hi >> (8 * b));
+}
+
 // the integer part of m 10^q 2^e (0 <= q <= 29, -87 <= e <= 6) and whether round-half-even takes it one up
 DFH_PT_FN uint64_t pt_scaled(uint32_t m, int e, uint32_t q, bool* up) {
   static constexpr uint64_t P10[20] = {1ULL, 10ULL, 100ULL, 1000ULL, 10000ULL, 100000ULL, 1000000ULL, 10000000ULL, 100000000ULL,

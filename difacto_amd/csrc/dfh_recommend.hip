@@ -64,7 +64,7 @@ struct dfh_recommend {
   size_t part_cap = 0;
   std::vector<void*> retired;        // arrays a growth replaced: queued kernels and copies may still use them
   unsigned long long* d_nf = nullptr;
-  LtWork* text = nullptr;            // dfh_listtext.hip: the workspace of dfh_recommend_format, made by the first format
+  TextWork text;                     // the workspace of dfh_recommend_format (dfh_listtext.hip over dfh_textout.hip)
   bool formatted = false;            // text holds the lines of every query appended
 };
 
@@ -478,7 +478,7 @@ int dfh_recommend_destroy(dfh_recommend* r) {
   if (r->d_aq) (void)hipFree(r->d_aq);
   if (r->d_part) (void)hipFree(r->d_part);
   if (r->d_nf) (void)hipFree(r->d_nf);
-  lt_release(r->text);
+  to_release(&r->text);
   delete r;
   return DFH_OK;
 }

@@ -8,18 +8,25 @@ task=dump alternated H D H D H D (`--rounds` pairs):
   H  dump_write=host    every unit formatted by the host's fprintf from dfh_dump_entries
   D  dump_write=device  every unit formatted by the device (csrc/dfh_dumptext.hip)
 
+With --parent PATH (a build/difacto of the parent commit) the pair is P D instead, every round starting one variant later:
+
+  P  the parent's binary, dump_write=device
+
+and the summary says whether D's median entries/s is at least P's slowest round.
+
 Per run: entries/s and MB/s by the task's own clock (from dfh_dump_open to the renamed file: the "dumped in" seconds of its log
 line; the model's load is reported beside it), the process's wall seconds, its host CPU seconds (user + sys), its peak
 resident set and the largest resident set while it dumps (after the load), and whether dump_out has the bytes of the first run's.  Every run has a time limit of its own and nothing more is
 started after a run that fails.  One JSON object per run and a summary on stdout.
 
-usage: dump_ab.py [--entries 1000000] [--v-dim 64] [--rounds 3] [--unit-rows 0]"""
+usage: dump_ab.py [--parent PATH] [--entries 1000000] [--v-dim 64] [--rounds 3] [--unit-rows 0]"""
 import argparse
 import hashlib
 import json
 import os
 import re
 import shutil
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -122,6 +129,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entries", type=int, default=1000000)
     ap.add_argument("--v-dim", type=int, default=64)
+    ap.add_argument("--parent", default="", help="build/difacto of the parent commit: its dump_write=device P alternated with this tree's D, no H")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--unit-rows", type=int, default=0, help="dump_unit_rows (0: the default)")
@@ -140,11 +148,15 @@ def measure(a, d):
     print(json.dumps(dict(model=True, entries=a.entries, V_dim=a.v_dim, model_file_mb=size / 1e6, seconds=time.time() - t0)), flush=True)
     exe = os.path.join(R, "build", "difacto")
     unit = ["dump_unit_rows=%d" % a.unit_rows] if a.unit_rows else []
-    runs, want = {"host": [], "device": []}, None
+    variants = [("host", exe, "host"), ("device", exe, "device")]
+    if a.parent:   # P and D alternated, every round one variant later: no variant always runs behind the same one
+        variants = [("parent", a.parent, "device"), ("device", exe, "device")]
+    runs, want = {name: [] for name, _, _ in variants}, None
     for rnd in range(a.rounds):
-        for how in ("host", "device"):
-            o = run([exe, "task=dump", "model_in=" + model, "dump_out=" + out, "dump_write=" + how] + unit, a.timeout)
-            o.update(variant=how, round=rnd)
+        k = rnd % len(variants) if a.parent else 0
+        for name, binary, how in variants[k:] + variants[:k]:
+            o = run([binary, "task=dump", "model_in=" + model, "dump_out=" + out, "dump_write=" + how] + unit, a.timeout)
+            o.update(variant=name, round=rnd)
             if o["rc"] == 0:
                 got = digest(out)
                 want = want or got
@@ -152,13 +164,18 @@ def measure(a, d):
                 os.remove(out)
             print(json.dumps(o), flush=True)
             if o["rc"] != 0 or "dump_s" not in o:
-                sys.exit("dump_write=%s failed (exit %d)" % (how, o["rc"]))   # nothing more is started after a failed run
-            runs[how].append(o)
+                sys.exit("%s (dump_write=%s) failed (exit %d)" % (name, how, o["rc"]))   # nothing more is started after a failed run
+            runs[name].append(o)
     summary = dict(summary=True, entries=a.entries, V_dim=a.v_dim, dump_out_bytes=want[1])
-    for how, rs in runs.items():
-        summary[how] = {k: sorted(round(o[k], 3) for o in rs) for k in ("entries_per_s", "mb_per_s", "dump_s", "load_s", "wall_s", "cpu_s", "peak_rss_mb", "dump_phase_rss_mb")}
-        summary[how]["same_bytes_as_first"] = all(o["same_bytes_as_first"] for o in rs)
-    summary["device_not_slower_in_every_pair"] = all(dv["dump_s"] <= h["dump_s"] for h, dv in zip(runs["host"], runs["device"]))
+    for name, rs in runs.items():
+        summary[name] = {k: sorted(round(o[k], 3) for o in rs) for k in ("entries_per_s", "mb_per_s", "dump_s", "load_s", "wall_s", "cpu_s", "peak_rss_mb", "dump_phase_rss_mb")}
+        summary[name]["same_bytes_as_first"] = all(o["same_bytes_as_first"] for o in rs)
+    if a.parent:
+        rate = [o["entries_per_s"] for o in runs["device"]]
+        summary["device_median_entries_per_s"] = statistics.median(rate)
+        summary["device_median_not_below_parent_min"] = statistics.median(rate) >= min(o["entries_per_s"] for o in runs["parent"])
+    else:
+        summary["device_not_slower_in_every_pair"] = all(dv["dump_s"] <= h["dump_s"] for h, dv in zip(runs["host"], runs["device"]))
     summary["table_bytes"] = runs["device"][0].get("table_bytes")
     print(json.dumps(summary), flush=True)
 
