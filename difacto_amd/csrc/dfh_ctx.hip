@@ -23,6 +23,8 @@ const IntOption kIntOptions[] = {
     {"upd_interleave", &dfh_ctx::upd_interleave, 0, 64, "upd_interleave must be in [0, 64]"},
     {"pairs_split", &dfh_ctx::pairs_split, 0, 64, "pairs_split must be in [0, 64] (0: chosen from the grid)"},
     {"rec_split", &dfh_ctx::rec_split, 0, 64, "rec_split must be in [0, 64] (0: chosen from the grid)"},
+    {"rec_precision", &dfh_ctx::rec_precision, 0, 1, "rec_precision must be 0 (fp32, the default) or 1 (a bf16 candidate sweep, exact fp32 re-ranking)"},
+    {"rec_shortlist", &dfh_ctx::rec_shortlist, 0, 64, "rec_shortlist must be in [0, 64] (0: min(64, max(16, 4 topk)))"},
     {"event_flags", &dfh_ctx::event_flags, 0, 1, "event_flags must be 0 (default events) or 1 (no system-scope fence); set before batches are created"},
 };
 }  // namespace
@@ -271,7 +273,7 @@ int dfh_ctx_get_timing(dfh_ctx* c, int reset, double* total_ms, uint64_t* calls)
 }
 
 const char* dfh_kernel_name(int id) {
-  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc", "pairs_pack", "pairs_sweep", "pairs_merge", "explain", "rec_embed", "rec_sweep", "rec_merge"};
+  static const char* names[DFH_K_COUNT] = {"localize", "lookup", "forward", "backward", "pull_rows", "push_grad", "misc", "auc", "pairs_pack", "pairs_sweep", "pairs_merge", "explain", "rec_embed", "rec_sweep", "rec_merge", "rec_convert", "rec_cand", "rec_rescore"};
   return (id >= 0 && id < DFH_K_COUNT) ? names[id] : "?";
 }
 

@@ -46,6 +46,8 @@ struct dfh_ctx {
   int event_flags = 1;
   int pairs_split = 0;         // dfh_dump_pairs: candidate splits of the sweep's grid (0: by the grid; tests and measuring)
   int rec_split = 0;           // dfh_recommend_append_batch: item splits of the sweep's grid (0: by the grid; tests and measuring)
+  int rec_precision = 0;       // dfh_recommend_create: 0 the fp32 sweep, 1 a bf16 candidate sweep and an exact fp32 re-ranking
+  int rec_shortlist = 0;       // dfh_recommend_create, rec_precision = 1: candidates per row (0: min(64, max(16, 4 topk)))
   int prep_priority = -1;      // preparation streams: -1 lowest, 0 default, 1 highest stream priority
   // The single-queue step (dfh_riders.hip): no preparation stream.  dfh_localize on a batch object only NOTES the work
   // (pend, in call order); the stages of the sample sort then ride, one per launch and minibatch, as extra blocks of the

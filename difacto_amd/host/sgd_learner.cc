@@ -117,7 +117,16 @@ KWArgs SGDLearner::Init(const KWArgs& kwargs) {
   CHECK(param_.items_in.empty() || param_.recommend_out.size())
       << "items_in without recommend_out: the ranked items have nowhere to go; name the file with recommend_out=<file>, or leave "
          "items_in out";
+  CHECK(param_.recommend_precision == "fp32" || param_.recommend_precision == "bf16")
+      << "recommend_precision=" << param_.recommend_precision << " is not one of fp32 (the default) and bf16";
+  CHECK(param_.recommend_out.size() || (param_.recommend_precision == "fp32" && param_.recommend_shortlist == 0))
+      << "recommend_precision / recommend_shortlist without recommend_out: there is no list to compute; name the file with "
+         "recommend_out=<file>, or leave them out";
   if (param_.recommend_out.size()) {
+    CHECK(param_.recommend_shortlist == 0 ||
+          (param_.recommend_precision == "bf16" && param_.recommend_shortlist >= param_.recommend_topk && param_.recommend_shortlist <= 64))
+        << "recommend_shortlist=" << param_.recommend_shortlist << " is not 0 or, with recommend_precision=bf16, a number of "
+           "candidates between recommend_topk=" << param_.recommend_topk << " and 64";
     CHECK(param_.task == "predict") << "recommend_out with task=" << param_.task << ": the items are ranked for the rows "
                                        "task=predict scores; use task=predict with model_in, or leave recommend_out out";
     CHECK(!IsDistributed()) << "recommend_out with a sharded store (DMLC_ROLE is set): a sharded step leaves the rows of other "
@@ -540,7 +549,11 @@ void SGDLearner::CloseRecommendUnit() {
 // recommend_out: the catalogue pass.  The job's loop runs over items_in as one part, in file order; the model is untouched, as
 // in any prediction job
 void SGDLearner::ReadCatalogue(const sgd::Job& job) {
-  if (!recommend_) DFH_CALL(dfh_recommend_create(DeviceContext::Get(), param_.recommend_topk, 0, &recommend_));
+  if (!recommend_) {
+    DFH_CALL(dfh_ctx_set_option(DeviceContext::Get(), "rec_precision", param_.recommend_precision == "bf16"));
+    DFH_CALL(dfh_ctx_set_option(DeviceContext::Get(), "rec_shortlist", param_.recommend_shortlist));
+    DFH_CALL(dfh_recommend_create(DeviceContext::Get(), param_.recommend_topk, 0, &recommend_));
+  }
   sgd::Job cj = job;
   cj.part_idx = 0;
   cj.num_parts = 1;

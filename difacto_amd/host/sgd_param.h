@@ -64,6 +64,11 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
   std::string items_in_format;  // "" (default: data_format)
   std::string recommend_out;    // predict: "" (default: nothing new runs) | the file
   int recommend_topk;           // 1 .. 32 items per row
+  // recommend_precision = bf16: the R x M sweep runs on bf16 MFMA and only finds recommend_shortlist candidates per row, which
+  // are then scored and ranked exactly as fp32 does: every logit printed is fp32's for that pair; an item of fp32's list is
+  // missing only where bf16 rounding kept it off the short list (the context's "rec_precision" / "rec_shortlist")
+  std::string recommend_precision;  // "fp32" (default) | "bf16"
+  int recommend_shortlist;          // bf16: 0 (default: min(64, max(16, 4 recommend_topk))) | recommend_topk .. 64
   DMLC_DECLARE_PARAMETER(SGDLearnerParam) {
     DMLC_DECLARE_FIELD(task).set_default("train");
     DMLC_DECLARE_FIELD(pred_out).set_default("");
@@ -82,6 +87,8 @@ struct SGDLearnerParam : public dmlc::Parameter<SGDLearnerParam> {
     DMLC_DECLARE_FIELD(items_in_format).set_default("");
     DMLC_DECLARE_FIELD(recommend_out).set_default("");
     DMLC_DECLARE_FIELD(recommend_topk).set_default(10);
+    DMLC_DECLARE_FIELD(recommend_precision).set_default("fp32");
+    DMLC_DECLARE_FIELD(recommend_shortlist).set_default(0);
     DMLC_DECLARE_FIELD(data_format).set_default("libsvm");
     DMLC_DECLARE_FIELD(data_in);
     DMLC_DECLARE_FIELD(data_val).set_default("");

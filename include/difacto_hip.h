@@ -106,7 +106,14 @@ int dfh_ctx_set_pipeline(dfh_ctx* ctx, int enable);
  *                                       (default 0; measurement switch)
  *   "pairs_split"       0 .. 64         dfh_dump_pairs: the candidate splits of the sweep's grid; 0 (default) = chosen so that a
  *                                       small model still fills the chip.  No bit of the output depends on it (tests, measuring)
- *   "rec_split"         0 .. 64         dfh_recommend_append_batch: the item splits of the sweep's grid, with the same meaning */
+ *   "rec_split"         0 .. 64         dfh_recommend_append_batch: the item splits of the sweep's grid, with the same meaning
+ *   "rec_precision"     0 | 1           dfh_recommend_create (fixed for the object's life): 0 (default) the fp32 sweep; 1 a bf16
+ *                                       candidate sweep on v_mfma_f32_32x32x16_bf16 and an exact fp32 re-ranking of the short list:
+ *                                       every (item, logit) handed out has the fp32 path's bits for that pair; the list is the
+ *                                       exact top of the short list, so it is the fp32 list whenever that list's items all reach
+ *                                       the short list; on bf16-exact inputs the whole output equals the fp32 path's
+ *   "rec_shortlist"     0 .. 64         dfh_recommend_create, "rec_precision" = 1: the candidates kept per row; 0 (default) =
+ *                                       min(64, max(16, 4 topk)); a value in 1 .. topk - 1 is refused at creation (DFH_ERR_ARG) */
 int dfh_ctx_set_option(dfh_ctx* ctx, const char* name, int value);
 
 /* optional per-kernel timing with HIP events recorded on the context's stream
@@ -116,6 +123,7 @@ enum {
   DFH_K_PAIRS_PACK, DFH_K_PAIRS_SWEEP, DFH_K_PAIRS_MERGE,   /* dfh_dump_pairs' three stages */
   DFH_K_EXPLAIN,                                            /* dfh_explain_append_batch's kernel */
   DFH_K_REC_EMBED, DFH_K_REC_SWEEP, DFH_K_REC_MERGE,        /* dfh_recommend_*'s three kernels */
+  DFH_K_REC_CONVERT, DFH_K_REC_CAND, DFH_K_REC_RESCORE,     /* "rec_precision" = 1: the bf16 operand, the candidate sweep, the re-rank */
   DFH_K_COUNT
 };
 int dfh_ctx_set_timing(dfh_ctx* ctx, int enable);
@@ -1040,6 +1048,10 @@ int dfh_explain_text_tile(dfh_explain* e);
  * M items when M < topk.  Everything is fp32; the R x M scores are one GEMM on MFMA that is never stored.  An item whose s is
  * not finite enters no list; such (query, item) pairs are counted.  No bit of the output depends on how the catalogue was cut
  * into batches or on "rec_split" (dfh_ctx_set_option, 0 .. 64: the item splits of the sweep's grid, 0 = chosen from the grid).
+ * With "rec_precision" = 1 at creation the sweep runs on bf16 MFMA and keeps "rec_shortlist" candidates per row, which are scored
+ * and ranked exactly as above (the guarantees: the option table of dfh_ctx_set_option); 2 roundup(V_dim + 3, 16) more bytes per
+ * item; creation is refused (DFH_ERR_ARG) for 0 < "rec_shortlist" < topk.  *nonfinite then counts the pairs whose bf16 score is
+ * not finite plus the candidates whose exact score is not finite.
  * Device memory: 4 roundup(V_dim + 1, 8) bytes per item (the array grows by doubling; capacity_hint: the items of the first
  * allocation) and 8 topk + 4 bytes per query row.
  * Errors: DFH_ERR_ARG for NULL arguments, topk outside [1, 32], a table other than the catalogue's; DFH_ERR_STATE when the

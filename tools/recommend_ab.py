@@ -16,7 +16,12 @@ and how many query rows get the same item set from both (the two sum in differen
 per run; a summary with the sweep's share of the fp32 matrix peak: 2 R M kd flop executed (kd = roundup(V_dim + 1, 8)) and
 2 R M (V_dim + 1) useful, over the sweep's span; the peak is `--peak-tflops`.  Nothing more is started after a run that fails.
 
-usage: recommend_ab.py [--rows 100000] [--items 1000000] [--v-dim 64] [--topk 10] [--rounds 3] [--batch 10000] [--rec-split 0]"""
+`--precision bf16` (with `--shortlist`) adds, in every round between A and B, variant A_bf16: a second capi.Recommend created
+under rec_precision = 1 over the same catalogue, the same rows through it, its spans (rec_embed, rec_convert, rec_cand,
+rec_rescore) and `recall`: the share of A's (row, item) pairs that A_bf16 returns.  `--no-torch` leaves B out.
+
+usage: recommend_ab.py [--rows 100000] [--items 1000000] [--v-dim 64] [--topk 10] [--rounds 3] [--batch 10000] [--rec-split 0]
+                       [--precision fp32|bf16] [--shortlist 0] [--no-torch]"""
 import argparse
 import json
 import os
@@ -70,6 +75,9 @@ def main():
     ap.add_argument("--q-chunk", type=int, default=8192)
     ap.add_argument("--c-chunk", type=int, default=65536)
     ap.add_argument("--rec-split", type=int, default=0, help="the sweep's item splits (0: chosen from the grid)")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="bf16: variant A_bf16 beside A, with its recall")
+    ap.add_argument("--shortlist", type=int, default=0, help="rec_shortlist of A_bf16 (0: min(64, max(16, 4 topk)))")
+    ap.add_argument("--no-torch", action="store_true", help="leave the torch yardstick B out")
     ap.add_argument("--peak-tflops", type=float, default=157.3, help="fp32 matrix peak of the box (MI355X: 157.3)")
     a = ap.parse_args()
     import torch
@@ -102,6 +110,15 @@ def main():
 
     ctx.set_option("rec_split", a.rec_split)
     rec = capi.Recommend(ctx, K, capacity_hint=M)
+    recb = None
+    if a.precision == "bf16":   # the options are read at creation
+        ctx.set_option("rec_precision", 1)
+        ctx.set_option("rec_shortlist", a.shortlist)
+        recb = capi.Recommend(ctx, K, capacity_hint=M)
+        ctx.set_option("rec_precision", 0)
+        feed(iidx, recb.add_items)
+        feed(qidx[:a.batch], recb.append_batch)
+        recb.read()
     ctx.set_timing(True)
     t0 = time.time()
     feed(iidx, rec.add_items)
@@ -125,7 +142,8 @@ def main():
     Q, I = operands(qidx, True), operands(iidx, False)
     feed(qidx[:a.batch], rec.append_batch)   # warm-up of both
     rec.read()
-    torch_topk(torch, Q[:4096], I[:min(M, 2 * a.c_chunk)], K, a.q_chunk, a.c_chunk)
+    if not a.no_torch:
+        torch_topk(torch, Q[:4096], I[:min(M, 2 * a.c_chunk)], K, a.q_chunk, a.c_chunk)
     ctx.get_timing(reset=True)
     print(json.dumps(dict(setup=True, rows=nq, items=M, V_dim=k, topk=K, batch=a.batch, rec_split=a.rec_split, catalogue_wall_s=cat_wall,
                           catalogue_rec_embed_ms=tm["rec_embed"][0])), flush=True)
@@ -142,6 +160,24 @@ def main():
         o["kernels_s"] = sum(o[x + "_ms"] for x in names) / 1e3
         print(json.dumps(o), flush=True)
         runs["A"].append(o)
+        if recb is not None:
+            recb.reset()
+            t0 = time.time()
+            feed(qidx, recb.append_batch)
+            gb = recb.read()
+            wall = time.time() - t0
+            tm = ctx.get_timing(reset=True)
+            nb = ("rec_embed", "rec_convert", "rec_cand", "rec_rescore")
+            slot = np.arange(K)
+            same = (got["items"][:, :, None] == gb["items"][:, None, :]) & (slot[None, None, :] < gb["n"][:, None, None])
+            kept = int((same.any(2) & (slot[None, :] < got["n"][:, None])).sum())
+            o = dict(variant="A_bf16", round=rnd, shortlist=a.shortlist, wall_s=wall, rows_per_s=nq / wall, nonfinite=gb["nonfinite"],
+                     recall=kept / max(int(got["n"].sum()), 1), **{x + "_ms": tm[x][0] for x in nb})
+            o["kernels_s"] = sum(o[x + "_ms"] for x in nb) / 1e3
+            print(json.dumps(o), flush=True)
+            runs.setdefault("A_bf16", []).append(o)
+        if a.no_torch:
+            continue
         idx, sec = torch_topk(torch, Q, I, K, a.q_chunk, a.c_chunk)
         same = (np.sort(got["items"].astype(np.int64), 1) == np.sort(idx.cpu().numpy(), 1)).all(1).mean()
         o = dict(variant="B", round=rnd, wall_s=sec, rows_with_the_same_item_set=float(same))
@@ -150,6 +186,12 @@ def main():
     kd = (k + 1 + 7) // 8 * 8
     sweep = sorted(o["rec_sweep_ms"] / 1e3 for o in runs["A"])
     flop, useful = 2.0 * nq * M * kd, 2.0 * nq * M * (k + 1)
+    if recb is not None:
+        print(json.dumps(dict(summary_bf16=True, shortlist=a.shortlist, kernels_s=sorted(round(o["kernels_s"], 4) for o in runs["A_bf16"]),
+                              wall_s=sorted(round(o["wall_s"], 4) for o in runs["A_bf16"]), recall=[round(o["recall"], 5) for o in runs["A_bf16"]],
+                              fp32_kernels_s=sorted(round(o["kernels_s"], 4) for o in runs["A"]),
+                              fp32_wall_s=sorted(round(o["wall_s"], 4) for o in runs["A"]))), flush=True)
+        recb.close()
     print(json.dumps(dict(summary=True, rows=nq, items=M, V_dim=k, kd=kd, topk=K,
                           A_kernels_s=sorted(round(o["kernels_s"], 4) for o in runs["A"]),
                           A_wall_s=sorted(round(o["wall_s"], 4) for o in runs["A"]), B_wall_s=sorted(round(o["wall_s"], 4) for o in runs["B"]),
