@@ -49,10 +49,14 @@ def load(tb, ids, w, has, V):
     tb.import_(rev(ids[:M_KEYS]), scal, has[:M_KEYS], np.concatenate([V[:M_KEYS], np.zeros_like(V[:M_KEYS])], 1) if V.shape[1] else None)
 
 
-def rows_of(rng, R, exact=True, dup=()):
-    """R rows of 0 .. 12 ids (row 1 is empty) -> offset, key number and x per position; dup: (a, b) pairs, row a repeats row b"""
-    lens = rng.integers(1, 13, R)
-    lens[1:2] = 0
+def rows_of(rng, R, exact=True, dup=(), lens=None):
+    """R rows of 0 .. 12 ids (row 1 is empty), or of the given lengths -> offset, key number and x per position; dup: (a, b)
+    pairs, row a repeats row b"""
+    if lens is None:
+        lens = rng.integers(1, 13, R)
+        lens[1:2] = 0
+    lens = np.array(lens, np.int64)
+    assert len(lens) == R
     for a, b in dup:
         lens[a] = lens[b]
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
